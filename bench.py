@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- 2-layer R-GCN forward+backward throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, ms_per_step, ...), nothing else.
+`--full` adds what the headline does not need: the per-launch timers and the rooflines built on them, the collective
+breakdown (N > 1), the sustained leg, the secondary config lines, the CPU baseline and the detail file (bench_detail.json).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs): the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload S1 (SURVEY.md 8d / BASELINE.md): N = 1,000,000 nodes, R0 = 50 relations (layer R = 101),
 E = 10,000,000 base triples from a splitmix64 stream (seed 0), augmented with inverses and self loops
@@ -167,17 +173,45 @@ def _backend_version(backend):
         return f"{backend} (version query failed: {type(exc).__name__})"
 
 
-def make_step(l1, l2, X):
+def make_step(l1, l2, X, keep=None):
     """THE timed step: layer 1 (horizontal flag) with its ReLU fused, layer 2 (vertical flag), loss = mean(out^2), backward to X and
-    to both layers' parameters (tests/test_gpu_parity.py::test_bench_step_composition_vs_cpu_port checks exactly this callable)"""
+    to both layers' parameters (tests/test_gpu_parity.py::test_bench_step_composition_vs_cpu_port checks exactly this callable).
+    keep: a dict that receives the step's output as keep["out"] (--dump-outputs); None keeps nothing alive between steps"""
     def step():
         for p in (X, l1.weights, l1.bias, l2.weights, l2.bias):
             p.grad = None
         out = l2(l1.forward_activated(X, "relu", private=True))
+        if keep is not None:
+            keep["out"] = out
         loss = _MeanSquare.apply(out)
         loss.backward()
         return loss
     return step
+
+
+DUMP_ROWS = 65536            # rows of the N x d outputs that --dump-outputs writes (a fixed sample, seed 0)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, out, X, l1, l2):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, float32 -- the loss, the layer-2 output and
+    dL/dX on a fixed sample of rows (the same rows in every run with the same arguments; their indices, as float64, in rows.npy) and every
+    parameter gradient whole.  With more than one rank this is rank 0's view: out and dL/dX are joined, the weight gradients are the
+    rows of the relations rank 0 owns."""
+    N, d = out.shape
+    n_rows = min(N, DUMP_ROWS, max(1, (16 << 20) // (4 * d)))
+    rows = np.sort(np.random.default_rng(0).choice(N, size=n_rows, replace=False))
+    idx = torch.from_numpy(rows).to(out.device)
+    arrays = {"loss": loss.detach().reshape(1), "out": out.detach()[idx], "x_grad": X.grad[idx],
+              "l1_weights_grad": l1.weights.grad, "l1_bias_grad": l1.bias.grad,
+              "l2_weights_grad": l2.weights.grad, "l2_bias_grad": l2.bias.grad}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    arrays["rows"] = rows.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes (limit {DUMP_LIMIT_BYTES})"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def build_layers(N, R0, E, d, seed, device, group, keep):
@@ -381,14 +415,20 @@ def main():
     ap.add_argument("--edges", type=int, default=10_000_000)
     ap.add_argument("--hidden", type=int, default=16)
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank its own relations/triples (round 1's mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-s1", action="store_true", help="CPU baseline at 1/10 scale only")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary lines for BASELINE configs 1-4")
+    ap.add_argument("--full", action="store_true", help="also the per-launch timers and rooflines, the collective breakdown (N > 1), the "
+                    "sustained leg, the secondary config lines, the CPU baseline and the detail file; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, a seeded sample of the N x d rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cpu-s1", action="store_true", help="--full: CPU baseline at 1/10 scale only")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the secondary lines for BASELINE configs 1-4")
     ap.add_argument("--check-unsharded", action="store_true", help="N > 1, strong mode: rank 0 also runs the step on the whole graph and the line "
                     "reports the largest relative difference of loss / dX / dW (tests; not part of the timed region)")
     ap.add_argument("--sustained-steps", type=int, default=400,
-                    help="N = 1: untimed-for-the-headline extra leg after the K timed steps (clocks / thermals over ~1 s); 0: skip")
+                    help="--full, N = 1: untimed-for-the-headline extra leg after the K timed steps (clocks / thermals over ~1 s); 0: skip")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run, and pass
@@ -444,7 +484,8 @@ def main():
     graph_build_ms = 1e3 * (time.perf_counter() - t_b)
     my_messages = l1._graph.num_messages
 
-    step = make_step(l1, l2, X)
+    last = {} if args.dump_outputs else None
+    step = make_step(l1, l2, X, keep=last)
 
     def fence():
         torch.cuda.synchronize()
@@ -488,31 +529,46 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # The per-launch timers (HIP events on the launch stream around every launch of the path's kernels: the roofline's `avg_launch_ms`) are
-    # SAMPLED: every `sample_every`-th step of the timed region carries them.  An event pair costs ~9 us of GPU time -- the launches on either
-    # side cannot overlap their tails and heads -- and with all four launches of every step bracketed the timed region measured the timers
-    # (1.845 ms per step against 1.81 for the same loop without them, tools/prof_overhead.py).
-    sample_every = max(1, min(4, args.steps // 4))
-    n_sampled = len(range(0, args.steps, sample_every))
-    _native.profile_start()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        _native.profile_enable(k % sample_every == 0)
-        marks[k].record()                 # HIP events on the launch stream: per-step GPU time (median / min below)
-        step()
-    marks[args.steps].record()
-    fence()
-    elapsed = time.perf_counter() - t0
-    _native.profile_enable(True)
-    prof = _native.profile_stop()
-    per_step = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
+    prof, per_step, n_sampled, sample_every = {}, None, 0, 0
+    if args.full:
+        # The per-launch timers (HIP events on the launch stream around every launch of the path's kernels: the roofline's `avg_launch_ms`) are
+        # SAMPLED: every `sample_every`-th step of the timed region carries them.  An event pair costs ~9 us of GPU time -- the launches on either
+        # side cannot overlap their tails and heads -- and with all four launches of every step bracketed the timed region measured the timers
+        # (1.845 ms per step against 1.81 for the same loop without them, tools/prof_overhead.py).
+        sample_every = max(1, min(4, args.steps // 4))
+        n_sampled = len(range(0, args.steps, sample_every))
+        _native.profile_start()
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            _native.profile_enable(k % sample_every == 0)
+            marks[k].record()                 # HIP events on the launch stream: per-step GPU time (median / min below)
+            loss = step()
+        marks[args.steps].record()
+        fence()
+        elapsed = time.perf_counter() - t0
+        _native.profile_enable(True)
+        prof = _native.profile_stop()
+        per_step = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
+    else:
+        # a plain run: the K steps and nothing between them (no per-step events, no per-launch timers)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loss = step()
+        fence()
+        elapsed = time.perf_counter() - t0
 
     t = torch.tensor([elapsed], device=device, dtype=torch.float64)
     if group is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
     ms = 1e3 * elapsed / args.steps
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last["out"], X, l1, l2)
+    del loss
+    if last is not None:
+        last.clear()
 
     shard_check = None
     if group is not None and args.check_unsharded and mode == "strong":
@@ -533,7 +589,7 @@ def main():
             del u1, u2, Xu
         fence()
 
-    if group is not None:
+    if group is not None and args.full:
         # what the collectives cost: (a) the step without them (RGCN_DIST_COMM=none: same kernels, wrong numbers),
         # (b) the four N x d collectives of one step on their own
         # (a bench-local patch of the join -- there is no such transport in torch_rgcn.dist: nothing else can switch the sums off)
@@ -573,7 +629,7 @@ def main():
                               "2(G-1)/G x 64 MB spread over G-1 links (DESIGN.md section 6)"})
 
     sustained = None
-    if world == 1 and group is None and args.sustained_steps > 0:
+    if args.full and world == 1 and group is None and args.sustained_steps > 0:
         # the timed region is K steps (~45 ms at the defaults): a second, longer leg of the SAME step shows whether the figure holds
         # once clocks and temperature have settled.  Reported next to the headline, never instead of it.
         n_s = args.sustained_steps
@@ -665,8 +721,6 @@ def main():
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
                "scaling": "weak" if mode == "weak" else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "per_gpu_edges_per_s": value / world,
-               "step_ms_median": round(float(np.median(per_step)), 4), "step_ms_min": round(float(np.min(per_step)), 4),
-               "step_ms_p95": round(float(np.percentile(per_step, 95)), 4), "sustained": sustained,
                "graph_build_ms": round(graph_build_ms, 2), "csrc_sha": _native.csrc_sha(),
                "config": {"workload": (f"S1: N={N} nodes, E={E} base triples" + ("/GPU" if mode == "weak" else "") +
                                        f", R0={R0} relations" + ("/GPU" if mode == "weak" else "") +
@@ -676,23 +730,26 @@ def main():
                                       (f"relation-sharded x{world} (LPT on message counts, ONE seed-0 graph), "
                                        if mode == "strong" else f"relation-sharded x{world} (each rank its own relations), ")
                                       + f"N x {d} fp32 partials joined by {comm['collective']}"},
-               "step_hbm_algorithmic_GBs": round(step_alg / (ms * 1e-3) / 1e9, 1),
-               "launch_timers": {"sampled_steps": n_sampled, "of_steps": args.steps,
-                                 "note": "HIP event pairs around the path's launches (avg_launch_ms of the rooflines) in every "
-                                         f"{sample_every}-th step of the timed region: a pair costs ~9 us of GPU time"},
-               "roofline": roof}
+               "step_hbm_algorithmic_GBs": round(step_alg / (ms * 1e-3) / 1e9, 1)}
+        if args.full:
+            res.update({"step_ms_median": round(float(np.median(per_step)), 4), "step_ms_min": round(float(np.min(per_step)), 4),
+                        "step_ms_p95": round(float(np.percentile(per_step, 95)), 4), "sustained": sustained,
+                        "launch_timers": {"sampled_steps": n_sampled, "of_steps": args.steps,
+                                          "note": "HIP event pairs around the path's launches (avg_launch_ms of the rooflines) in every "
+                                                  f"{sample_every}-th step of the timed region: a pair costs ~9 us of GPU time"},
+                        "roofline": roof})
         if comm is not None:
             res["comm"] = comm
         if shard_check is not None:
             res["sharded_vs_unsharded"] = shard_check
-        if world == 1 and group is None and not args.no_configs:
+        if args.full and world == 1 and group is None and not args.no_configs:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
                 import config_bench
                 res["configs"] = config_bench.secondary_lines()
             except Exception as exc:  # noqa: BLE001  (secondary lines must never cost the headline number)
                 res["configs"] = f"failed: {type(exc).__name__}: {exc}"[:300]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del l1, l2, X
             torch.cuda.empty_cache()
             res["cpu_baseline"] = cpu_baseline(full_scale=not args.no_cpu_s1 and host_ram_gb() >= 32.0 and
@@ -701,8 +758,10 @@ def main():
         res = None
     if group is not None:
         dist.destroy_process_group()   # RCCL prints its banner here; keep the JSON line last
-    if res is not None:
+    if res is not None and args.full:
         emit(res)
+    elif res is not None:
+        print(compact_line(_no_nan(res)), flush=True)
 
 
 if __name__ == "__main__":

@@ -223,7 +223,7 @@ def _run_bench(extra_args, env_extra=None, world=2):
     env = dict(os.environ, RGCN_BENCH_ONE_DEVICE="1", RGCN_DIST_BACKEND="gloo", **(env_extra or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--nodes", "200000", "--edges", "1000000", "--rels", "20"] + extra_args
+           "--nodes", "200000", "--edges", "1000000", "--rels", "20", "--full"] + extra_args
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         env["RGCN_BENCH_DETAIL"] = os.path.join(tmp, "detail.json")
@@ -311,7 +311,7 @@ def test_plain_bench_command_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RGCN_BENCH_ONE_DEVICE="1", RGCN_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--nodes", "100000",
-           "--edges", "500000", "--rels", "10"]
+           "--edges", "500000", "--rels", "10", "--full"]
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         env["RGCN_BENCH_DETAIL"] = os.path.join(tmp, "detail.json")

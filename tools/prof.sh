@@ -105,7 +105,7 @@ case "$MODE" in
       [ "${KEEP_RAW:-0}" = "1" ] || rm -rf "$OUT/$L"          # the raw traces run to tens of MB per line: gpurun copies back 64 MiB at most
     done ;;
   bench)
-    CMD="python bench.py --no-cpu-baseline --no-configs"
+    CMD="python bench.py --full --no-cpu-baseline --no-configs"
     trace_run "$OUT/trace" $CMD
     cp "$OUT/trace/stdout.txt" "$OUT/bench_under_rocprof.json"
     summarise "$OUT/trace" "" "$OUT/kernel_stats.csv" "" "$CMD"

@@ -4,5 +4,5 @@
 cd "$GRAFT_REPO_ROOT"
 for C in 767 600 500; do
   echo "== RGCN_OWN_ROWS_CAP=$C"
-  RGCN_OWN_ROWS_CAP=$C timeout 300 python bench.py --no-configs --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['roofline']['forward']['avg_launch_ms'], d['roofline']['backward']['avg_launch_ms'])"
+  RGCN_OWN_ROWS_CAP=$C timeout 300 python bench.py --full --no-configs --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['roofline']['forward']['avg_launch_ms'], d['roofline']['backward']['avg_launch_ms'])"
 done
