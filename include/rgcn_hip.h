@@ -366,6 +366,14 @@ RGCN_API int32_t rgcn_bwd_own_max_rows(void);
 RGCN_API int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_packed, float *dX, float *dW, const void *rec,
                               const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
                               int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
+/* rgcn_bwd_own_bf16: the same backward on bf16 storage (replaces layers.py:293-301's duals for a layer called with bf16 features):
+ * G [n_src][16], X [n_dst][16] and dX [n_dst][16] are bf16 (uint16_t bit patterns).  G is gathered as 32-byte rows and widened; every product
+ * and sum is fp32 (the dX tile fp64 in LDS), dX is rounded to bf16 once (round to nearest even, NaN stays NaN).  Wt_packed, dW and dbias stay
+ * fp32.  Records, own_ptr, unit_rel and dbias as rgcn_bwd_own_f32; flags = 0 (no ReLU mask: the caller masks G); n_src < 2^26 (the records
+ * address rows as src << 6). */
+RGCN_API int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float *Wt_packed, uint16_t *dX, float *dW, const void *rec,
+                               const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
+                               int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
 /* Soft-window plans (round 6), built on the device: the relation-tile plan of rgcn_spmm_blk_f32 / rgcn_bwd_own_f32 in the order those
  * kernels are fast on -- what replaces the reference's per-forward stack_matrices -> sum_sparse -> sparse COO pipeline (utils.py:143-166, :71-97;
  * layers.py:255-279) for them.  Messages (dst <- src, rel, val; alive may be NULL) are bucketed by (dst / tile_rows, rel), every bucket padded to a
@@ -403,6 +411,31 @@ RGCN_API int32_t rgcn_spmm_blk_max_rows(void);
 RGCN_API int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const float *bias, float *out, const void *rec,
                                const int32_t *run_ptr, int64_t n_tiles, int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags,
                                const int32_t *units, int64_t n_units, int64_t n_split, void *stream);
+/* rgcn_spmm_blk_bf16: the same forward on bf16 storage (layers.py:293-301 for a layer called with bf16 features): X [n_src][16]
+ * and out [n_dst][16] are bf16 (uint16_t bit patterns), W_packed and bias fp32.  X rows are gathered as 32 bytes and widened; every product
+ * and sum is fp32 (the tile fp64 in LDS), out is rounded to bf16 once (round to nearest even, NaN stays NaN).  Plans with hub pieces
+ * (n_split > 0) add the pieces' fp32 rows into `scratch` ([n_dst][16] floats; may be NULL when n_split = 0) and round it in a second launch --
+ * never bf16 atomics.  flags: RGCN_F_RELU (not with hub pieces); n_src < 2^26 (the records address rows as src << 6). */
+RGCN_API int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, const float *bias, uint16_t *out, float *scratch, const void *rec,
+                                const int32_t *run_ptr, int64_t n_tiles, int32_t tile_rows, int64_t n_dst, int64_t n_src, int32_t R,
+                                int32_t flags, const int32_t *units, int64_t n_units, int64_t n_split, void *stream);
+/* bf16 storage on the wave-owned plans (layers.py:286-306 for a layer called with bf16 features): X / G and out are bf16
+ * (uint16_t bit patterns), weights, bias, dW and db fp32; every product and sum fp32, outputs rounded once (round to nearest even, NaN stays
+ * NaN).  Rows are gathered as bf16 and widened.
+ *   rgcn_spmm_bf16    out [n_dst][d_out] = bias + sum val X[src] W_r on a plan with PACKED slots (rgcn_spmm_f32's work units; n_src < 2^24),
+ *                     widths multiples of 16 up to 64, W_packed = rgcn_pack_w16_f32 (16 x 16) or rgcn_pack_w_blocks_f32 fragments.  Hub
+ *                     pieces (n_split > 0) add fp32 rows into `scratch` ([n_dst][d_out] floats; may be NULL when n_split = 0), rounded in a
+ *                     second launch -- never bf16 atomics.  flags: RGCN_F_RELU (not with hub pieces).  The feature gradient is the same call
+ *                     on the transposed plan with the transposed weights.
+ *   rgcn_wgrad_bf16   dW [R][d_in][d_out] (fp32, zeroed first) += val X[src]^T G[dst] on the relation-major plan, as rgcn_wgrad_f32.
+ *   rgcn_colsum_bf16  db [d] = column sums of G [n][d] (fp32; d a multiple of 4, at most 256); scratch as rgcn_colsum_f32. */
+RGCN_API int rgcn_spmm_bf16(const uint16_t *X, const float *W_packed, const float *bias, uint16_t *out, float *scratch,
+                            const int32_t *p_pack, const int32_t *chunk_rel, const int32_t *units, int64_t n_units, int64_t n_split,
+                            int32_t tile_rows, int64_t n_dst, int64_t n_src, int32_t d_in, int32_t d_out, int32_t flags, void *stream);
+RGCN_API int rgcn_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dW, const int32_t *p_src, const int32_t *p_dst,
+                             const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items, int32_t R,
+                             int32_t d_in, int32_t d_out, void *stream);
+RGCN_API int rgcn_colsum_bf16(const uint16_t *G, float *db, float *scratch, int64_t n, int32_t d, void *stream);
 /* The same for graphs whose (tile, relation) buckets are sparse (AM: 267 relations), on the RELATION-major plan of the
  * two-pass path: one wave per work item gathers G[p_src] and X[p_dst] once per message and produces
  *   Y[slot, :] = val G[p_src] W_r^T   (slot order; pass 2 = rgcn_segment_gather_sum_f32 sums them per destination -> dX)

@@ -483,7 +483,10 @@ __global__ __launch_bounds__(64 * BLK_NW) void bwd_blk_d16_kernel(
 // whose relations do not fit the one-pass CSR kernel's LDS (AM as shipped, layer 2: R = 267 -- 31 messages per bucket on 930-row tiles
 // instead of ~2 on 64-row ones); until round 5 that layer's forward was two passes over a [M, 16] intermediate (0.40 + 0.22 ms).
 // TQ = ceil(tile_rows / 256): float4 of the tile a thread converts and stores per tile.
-template <bool RELU, int TQ>
+// BF (rgcn_spmm_blk_bf16): bit 1 = X holds bf16 rows (32 bytes: the record's byte offset src << 6 halved, an 8-byte gather per
+// lane, widened), bit 2 = out holds bf16 rows (rounded once, in the epilogue).  Pieces of hub tiles always add fp32 rows (the launcher hands
+// such plans an fp32 scratch and rounds it afterwards).  BF = 0 is the fp32 kernel as it was.
+template <bool RELU, int TQ, int BF = 0>
 __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
     const float *__restrict__ X, const float *__restrict__ Wp, const float *__restrict__ bias, float *__restrict__ out,
     const char *__restrict__ rec, const int *__restrict__ run_ptr, int n_tiles, int tile_rows, int n_dst, int R,
@@ -558,8 +561,12 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        const unsigned og = w0_[j] | kofs;
-        g_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(X) + og);
+        if constexpr ((BF & 1) != 0) {
+          g_[j] = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(X) + ((w0_[j] >> 1) | (kofs >> 1))));
+        } else {
+          const unsigned og = w0_[j] | kofs;
+          g_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(X) + og);
+        }
         w_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(Wp) + (size_t)hd_[j] * 1024 + w_lane);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -624,12 +631,17 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
         const double2 d0 = td2[2 * idx], d1 = td2[2 * idx + 1];
         float4 a = make_float4((float)d0.x, (float)d0.y, (float)d1.x, (float)d1.y);
         if (with_bias) { a.x += bv.x; a.y += bv.y; a.z += bv.z; a.w += bv.w; }
+        if constexpr ((BF & 2) != 0) {      // (no pieces on this form)
+          if (RELU) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+          reinterpret_cast<uint2 *>(out)[(size_t)row0 * 4 + idx] = bf16x4_round(a);
+        } else {
         float4 *o = reinterpret_cast<float4 *>(out + (size_t)row0 * 16) + idx;
         if (shared) {       // a piece of a hub tile: the pieces' rows are summed in memory (out was zeroed; no ReLU on such plans)
           atomicAdd(&o->x, a.x); atomicAdd(&o->y, a.y); atomicAdd(&o->z, a.z); atomicAdd(&o->w, a.w);
         } else {
           if (RELU) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
           *o = a;
+        }
         }
       }
     }
@@ -805,6 +817,75 @@ extern "C" int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const fl
     else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS>, r[5]));
     else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS>, r[6]));
     else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS>, r[7]));
+  }
+  return RGCN_OK;
+}
+
+namespace {
+// fp32 rows -> bf16 rows (the hub pieces' scratch of rgcn_spmm_blk_bf16): one rounding per element
+__global__ __launch_bounds__(WG) void round_rows_bf16_kernel(const float4 *__restrict__ src, uint2 *__restrict__ dst, long long n4) {
+  for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n4; i += (long long)gridDim.x * WG) dst[i] = bf16x4_round(src[i]);
+}
+}  // namespace
+
+extern "C" int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, const float *bias, uint16_t *out, float *scratch, const void *rec,
+                                  const int32_t *run_ptr, int64_t n_tiles, int32_t tile_rows, int64_t n_dst, int64_t n_src, int32_t R,
+                                  int32_t flags, const int32_t *units, int64_t n_units, int64_t n_split, void *stream) {
+  if (!X || !W_packed || !out || !rec || !run_ptr || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 || n_dst > INT32_MAX ||
+      n_src <= 0 || n_src >= (int64_t(1) << 26) || (units && (n_units < n_tiles || n_split < 0 || n_units > INT32_MAX))) {
+    rgcn_set_error("spmm_blk_bf16: bad argument (the records address source rows as src << 6 in 32 bits: n_src < 2^26)");
+    return RGCN_EINVAL;
+  }
+  if (tile_rows > rgcn_spmm_blk_max_rows()) { rgcn_set_error("spmm_blk_bf16: tiles of at most %d rows (got %d)", rgcn_spmm_blk_max_rows(), tile_rows); return RGCN_EUNSUPPORTED; }
+  if (!units) { n_units = n_tiles; n_split = 0; }
+  const bool relu = (flags & RGCN_F_RELU) != 0;
+  if (relu && n_split) { rgcn_set_error("spmm_blk_bf16: relu in the epilogue needs tiles that are not cut into shared pieces"); return RGCN_EUNSUPPORTED; }
+  if (n_split && !scratch) { rgcn_set_error("spmm_blk_bf16: a plan with hub pieces needs the fp32 scratch (n_dst x 16 floats)"); return RGCN_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  static int n_cu = 0;
+  if (!n_cu) {
+    int dev = 0, v = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+    n_cu = v > 0 ? v : 256;
+  }
+  // hub pieces add fp32 rows into the scratch (zeroed), rounded to bf16 once afterwards: never bf16 atomics (rounded at every add)
+  float *dst32 = n_split ? scratch : reinterpret_cast<float *>(out);
+  if (n_split) HIP_TRY(zero_async(scratch, (size_t)n_dst * 16 * sizeof(float), st));
+  const size_t lds = (size_t)tile_rows * 128 + 64;
+  const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
+  const float *Xf = reinterpret_cast<const float *>(X);
+  auto launch = [&](auto kern, bool &raised) -> hipError_t {
+    if (lds > 64 * 1024 && !raised) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BLK_LDS_MAX);
+      if (e != hipSuccess) return e;
+      raised = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * BLK_FWD_NW), lds, st, Xf, W_packed, bias, dst32, static_cast<const char *>(rec), run_ptr,
+                       (int)n_tiles, tile_rows, (int)n_dst, R, reinterpret_cast<const int4 *>(units), (int)n_units);
+    return hipGetLastError();
+  };
+  static bool r[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
+  const int tq = (tile_rows + 255) / 256;
+  if (n_split) {
+    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 1>, r[0]));
+    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 1>, r[1]));
+    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 1>, r[2]));
+    else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 1>, r[3]));
+    const long long n4 = n_dst * 4;
+    hipLaunchKernelGGL(round_rows_bf16_kernel, dim3((unsigned)std::min<long long>((n4 + WG - 1) / WG, 4096)), dim3(WG), 0, st,
+                       reinterpret_cast<const float4 *>(scratch), reinterpret_cast<uint2 *>(out), n4);
+    HIP_TRY(hipGetLastError());
+  } else if (relu) {
+    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS, 3>, r[4]));
+    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS, 3>, r[5]));
+    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS, 3>, r[6]));
+    else HIP_TRY(launch(spmm_blk_d16_kernel<true, 4 * BLK_FWD_TQS, 3>, r[7]));
+  } else {
+    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 3>, r[8]));
+    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 3>, r[9]));
+    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 3>, r[10]));
+    else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 3>, r[11]));
   }
   return RGCN_OK;
 }

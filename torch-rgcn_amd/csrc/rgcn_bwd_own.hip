@@ -57,7 +57,10 @@ size_t bwd_own_lds(int rows) { return (size_t)rows * 192 + (size_t)OWN_NW * BW_S
 
 // Timing experiments (ablation library only, make abl; wrong results): ABL bits 2 no dW part, 4 the accumulator index is always 0,
 // 8 no dX tile update, 16 loads only
-template <bool RELU, int NW, int K, int ABL = 0>
+// BF (rgcn_bwd_own_bf16): G, X and dX hold bf16 rows (32 bytes); G is gathered 8 bytes per lane (the record's byte offset
+// src << 6 halved) and widened, the X tile in LDS stays fp32, dX is rounded once on the way out; dW and the bias gradient stay fp32.
+// BF = false is the fp32 kernel as it was.
+template <bool RELU, int NW, int K, int ABL = 0, bool BF = false>
 __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     const float *__restrict__ G, const float *__restrict__ X, const float *__restrict__ Wtp, float *__restrict__ dX,
     float *__restrict__ dWout, const char *__restrict__ rec, const int *__restrict__ own_ptr, int n_tiles, int tile_rows, int n_dst,
@@ -90,7 +93,10 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     const int idx = tid + q * NT;
     if (idx < tile_rows * 4) {
       float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < nrows * 4) x0 = reinterpret_cast<const float4 *>(X + (size_t)row0 * 16)[idx];
+      if (idx < nrows * 4) {
+        if constexpr (BF) x0 = bf16x4_widen(reinterpret_cast<const uint2 *>(X)[(size_t)row0 * 4 + idx]);
+        else x0 = reinterpret_cast<const float4 *>(X + (size_t)row0 * 16)[idx];
+      }
       xt4[idx] = x0;
     }
   }
@@ -147,8 +153,12 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        const unsigned og = w0_[j] | kofs;
-        g_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(G) + og);
+        if constexpr (BF) {
+          g_[j] = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(G) + ((w0_[j] >> 1) | (kofs >> 1))));
+        } else {
+          const unsigned og = w0_[j] | kofs;
+          g_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(G) + og);
+        }
         w_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(Wtp) + (size_t)(hd_[j] & 0xFFFF) * 1024 + w_lane);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -242,11 +252,21 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       c1n = __builtin_amdgcn_readfirstlane(own_ptr[(size_t)tn * NW + wave + 1]);
 #pragma unroll
       for (int q = 0; q < TQ; ++q)
-        if (tid + q * NT < nrn * 4) xn[q] = reinterpret_cast<const float4 *>(X + (size_t)row0n * 16)[tid + q * NT];
+        if (tid + q * NT < nrn * 4) {
+          if constexpr (BF) {     // (the raw bf16 bits ride in .x / .y across the barrier, widened when the tile is installed)
+            const uint2 u = reinterpret_cast<const uint2 *>(X)[(size_t)row0n * 4 + tid + q * NT];
+            xn[q] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), 0.f, 0.f);
+          } else {
+            xn[q] = reinterpret_cast<const float4 *>(X + (size_t)row0n * 16)[tid + q * NT];
+          }
+        }
       if (c0n < c1n) request_idx(c0n, c1n - 1);
     }
     float4 gn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g_i < g_n4) gn = reinterpret_cast<const float4 *>(G)[g_i];
+    if (g_i < g_n4) {
+      if constexpr (BF) gn = bf16x4_widen(reinterpret_cast<const uint2 *>(G)[g_i]);
+      else gn = reinterpret_cast<const float4 *>(G)[g_i];
+    }
     g_i += g_step;
     lds_barrier();                                                 // every wave has finished adding to the dX tile
     gs.x += gn.x; gs.y += gn.y; gs.z += gn.z; gs.w += gn.w;
@@ -263,7 +283,8 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
           const float4 x = xt4[idx];
           a.x = x.x > 0.f ? a.x : 0.f; a.y = x.y > 0.f ? a.y : 0.f; a.z = x.z > 0.f ? a.z : 0.f; a.w = x.w > 0.f ? a.w : 0.f;
         }
-        reinterpret_cast<float4 *>(dX + (size_t)row0 * 16)[idx] = a;
+        if constexpr (BF) reinterpret_cast<uint2 *>(dX)[(size_t)row0 * 4 + idx] = bf16x4_round(a);
+        else reinterpret_cast<float4 *>(dX + (size_t)row0 * 16)[idx] = a;
       }
     }
     if (tn >= n_tiles) break;
@@ -273,7 +294,8 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       if (idx < tile_rows * 4) {
         dxz[2 * idx] = make_float4(0.f, 0.f, 0.f, 0.f);
         dxz[2 * idx + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        xt4[idx] = xn[q];
+        if constexpr (BF) xt4[idx] = bf16x4_widen(uint2{__float_as_uint(xn[q].x), __float_as_uint(xn[q].y)});
+        else xt4[idx] = xn[q];
       }
     }
     lds_barrier();                                                 // the next tile is installed (nobody waits for the dX stores)
@@ -281,7 +303,9 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
   }
   if (dbias) {
     for (; g_i < g_n4; g_i += g_step) {
-      const float4 gn = reinterpret_cast<const float4 *>(G)[g_i];
+      float4 gn;
+      if constexpr (BF) gn = bf16x4_widen(reinterpret_cast<const uint2 *>(G)[g_i]);
+      else gn = reinterpret_cast<const float4 *>(G)[g_i];
       gs.x += gn.x; gs.y += gn.y; gs.z += gn.z; gs.w += gn.w;
     }
     // thread tid holds features 4 (tid & 3) .. + 3: fold the 16 lanes of a wave that share (lane & 3), then the waves through the scratch
@@ -374,5 +398,49 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
   static bool r0 = false, r1 = false;
   if (flags & RGCN_F_RELU) HIP_TRY(launch(bwd_own_d16_kernel<true, OWN_NW, OWN_K>, r0));
   else HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K>, r1));
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float *Wt_packed, uint16_t *dX, float *dW, const void *rec,
+                                 const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
+                                 int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
+  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !own_ptr || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
+      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || n_src <= 0 || n_src >= (int64_t(1) << 26) || flags != 0) {
+    rgcn_set_error("bwd_own_bf16: bad argument (the records address G rows as src << 6 in 32 bits: n_src < 2^26; no flags)");
+    return RGCN_EINVAL;
+  }
+  if (tile_rows > rgcn_bwd_own_max_rows()) {
+    rgcn_set_error("bwd_own_bf16: tiles of at most %d rows (got %d)", rgcn_bwd_own_max_rows(), tile_rows);
+    return RGCN_EUNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  static int n_cu = 0;
+  if (!n_cu) {
+    int dev = 0, v = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+    n_cu = v > 0 ? v : 256;
+  }
+  if (dbias == dW + (size_t)R * 256) {
+    HIP_TRY(zero_async(dW, ((size_t)R * 256 + 16) * sizeof(float), st));
+  } else {
+    HIP_TRY(zero_async(dW, (size_t)R * 256 * sizeof(float), st));
+    if (dbias) HIP_TRY(zero_async(dbias, 16 * sizeof(float), st));
+  }
+  const size_t lds = bwd_own_lds(tile_rows);
+  const unsigned n_blocks = (unsigned)std::min<int64_t>(n_tiles, n_cu);
+  auto launch = [&](auto kern, bool &raised) -> hipError_t {
+    if (lds > 64 * 1024 && !raised) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, OWN_LDS_MAX);
+      if (e != hipSuccess) return e;
+      raised = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, reinterpret_cast<const float *>(G), reinterpret_cast<const float *>(X),
+                       Wt_packed, reinterpret_cast<float *>(dX), dW, static_cast<const char *>(rec), own_ptr, (int)n_tiles, tile_rows, (int)n_dst,
+                       dbias, (int)n_src, unit_rel);
+    return hipGetLastError();
+  };
+  static bool r1 = false;
+  HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>, r1));
   return RGCN_OK;
 }

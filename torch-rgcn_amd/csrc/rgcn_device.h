@@ -59,6 +59,19 @@ __device__ __forceinline__ int dpp_i(int old, int src) {
 // SQ_LDS_IDX_ACTIVE in spmm_d16_kernel); swizzled, 16 consecutive rows cover all 64 banks.  i = float4 index (4 row + q).
 __device__ __forceinline__ int tile_swz(int i) { return i ^ ((i >> 4) & 3); }
 
+// bf16 storage: a lane's quarter row (features 4k .. 4k+3) is 8 bytes.  Widening is a 16-bit shift; rounding is a plain
+// conversion (v_cvt_pk_bf16_f32: round to nearest even, a NaN stays NaN -- not the integer (u + 0x7FFF + lsb) >> 16 trick).
+__device__ __forceinline__ float4 bf16x4_widen(uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xFFFF0000u));
+}
+__device__ __forceinline__ unsigned bf16x2_round(float lo, float hi) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t{lo, hi}), bf16x2_t));
+}
+__device__ __forceinline__ uint2 bf16x4_round(float4 a) { return uint2{bf16x2_round(a.x, a.y), bf16x2_round(a.z, a.w)}; }
+
 constexpr int ROW_SHR = 0x110;  // + n : lane m reads lane m-n of its 16-lane row
 constexpr int ROW_SHL = 0x100;  // + n : lane m reads lane m+n
 

@@ -39,7 +39,9 @@ struct D16Stage {
 
 // PACKED: slots come as 8 bytes {src | dst_local << 24, val} and W_rel as pre-swizzled fragments
 // (one float4 per lane), i.e. 4 VMEM instructions per chunk instead of 8.
-template <int U, bool PACKED>
+// BF (rgcn_spmm_bf16; PACKED only): bit 1 = X holds bf16 rows (an 8-byte gather per lane at src << 5, widened), bit 2 = out
+// holds bf16 rows (rounded once; never with hub pieces, whose fp32 rows go to the launcher's scratch).  BF = 0: the fp32 kernel as it was.
+template <int U, bool PACKED, int BF = 0>
 __global__ __launch_bounds__(WG) void spmm_d16_kernel(
     const float *__restrict__ X, const float *__restrict__ W, const float *__restrict__ bias,
     float *__restrict__ out, const int *__restrict__ p_src, const int *__restrict__ p_dst,
@@ -89,7 +91,9 @@ __global__ __launch_bounds__(WG) void spmm_d16_kernel(
     auto gather = [&](D16Stage<U> &g) {
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        if (PACKED)       // packed slots: source ids < 2^24 -> a 32-bit byte offset from the uniform base (scalar-base load form)
+        if constexpr ((BF & 1) != 0)
+          g.x[j] = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(X) + (((unsigned)g.s[j] << 5) | ((unsigned)k << 3))));
+        else if (PACKED)  // packed slots: source ids < 2^24 -> a 32-bit byte offset from the uniform base (scalar-base load form)
           g.x[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(X) + (((unsigned)g.s[j] << 6) | ((unsigned)k << 4)));
         else
           g.x[j] = *reinterpret_cast<const float4 *>(X + (size_t)g.s[j] * 16 + 4 * k);
@@ -148,7 +152,8 @@ __global__ __launch_bounds__(WG) void spmm_d16_kernel(
     float4 a = reinterpret_cast<const float4 *>(tile)[tile_swz(i)];
     a.x += bv.x; a.y += bv.y; a.z += bv.z; a.w += bv.w;
     if (relu_out) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
-    o4[i] = a;
+    if constexpr ((BF & 2) != 0) reinterpret_cast<uint2 *>(out)[(size_t)row0 * 4 + i] = bf16x4_round(a);
+    else o4[i] = a;
   }
 }
 
@@ -174,7 +179,8 @@ __global__ __launch_bounds__(WG) void pack_w_blocks_kernel(const float *__restri
   Wp[i] = W[((size_t)r * 16 * NI + 16 * ib + 4 * kk + c) * (16 * NJ) + 16 * jb + o];
 }
 
-template <int NI, int NJ, int U>
+// BF: as spmm_d16_kernel (rgcn_spmm_bf16)
+template <int NI, int NJ, int U, int BF = 0>
 __global__ __launch_bounds__(WG) void spmm_wide_kernel(
     const float *__restrict__ X, const float *__restrict__ Wp, const float *__restrict__ bias,
     float *__restrict__ out, const int2 *__restrict__ p_pack, const int *__restrict__ chunk_rel,
@@ -214,7 +220,12 @@ __global__ __launch_bounds__(WG) void spmm_wide_kernel(
 #pragma unroll
       for (int j = 0; j < U; ++j) {
 #pragma unroll
-        for (int ib = 0; ib < NI; ++ib) x[j][ib] = *reinterpret_cast<const float4 *>(X + (size_t)s[j] * DI + 16 * ib + 4 * k);
+        for (int ib = 0; ib < NI; ++ib) {
+          if constexpr ((BF & 1) != 0)
+            x[j][ib] = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(X) + (size_t)s[j] * DI + 16 * ib + 4 * k));
+          else
+            x[j][ib] = *reinterpret_cast<const float4 *>(X + (size_t)s[j] * DI + 16 * ib + 4 * k);
+        }
         const float4 *wr = reinterpret_cast<const float4 *>(Wp) + (size_t)r[j] * (NI * NJ * 64) + lane;
 #pragma unroll
         for (int ib = 0; ib < NI; ++ib)
@@ -257,12 +268,17 @@ __global__ __launch_bounds__(WG) void spmm_wide_kernel(
       const float4 bv = reinterpret_cast<const float4 *>(bias)[i % (DO / 4)];
       a.x += bv.x; a.y += bv.y; a.z += bv.z; a.w += bv.w;
     }
+    if constexpr ((BF & 2) != 0) {   // (no pieces on this form)
+      if (relu_out) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+      reinterpret_cast<uint2 *>(out)[(size_t)row0 * (DO / 4) + i] = bf16x4_round(a);
+    } else {
     if (shared) {   // piece of a hub tile: out was zeroed by the launcher, pieces are summed atomically
       float *o = reinterpret_cast<float *>(o4 + i);
       atomicAdd(o, a.x); atomicAdd(o + 1, a.y); atomicAdd(o + 2, a.z); atomicAdd(o + 3, a.w);
     } else {
       if (relu_out) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
       o4[i] = a;
+    }
     }
   }
 }
@@ -474,7 +490,8 @@ __global__ __launch_bounds__(WG) void spmm_generic_kernel(
 // ------------------------------------------------------------------ weight gradient, any d
 // One wave per work item (a run of chunks with one relation).  grid.y enumerates
 // (row-tile group, column-tile group) blocks of dW[r].
-template <int NIT, int NJT>
+// BF (rgcn_wgrad_bf16): X and G hold bf16 elements (widened on load); BF = false: the fp32 kernel as it was
+template <int NIT, int NJT, bool BF = false>
 __global__ __launch_bounds__(WG) void wgrad_generic_kernel(
     const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ dW,
     const int *__restrict__ p_src, const int *__restrict__ p_dst, const float *__restrict__ p_val,
@@ -507,12 +524,18 @@ __global__ __launch_bounds__(WG) void wgrad_generic_kernel(
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
         const int f = i0 + it * 16 + m;
-        a[it] = (live && f < d_in) ? X[(size_t)s * d_in + f] * v : 0.f;
+        if constexpr (BF)
+          a[it] = (live && f < d_in) ? __uint_as_float((unsigned)reinterpret_cast<const uint16_t *>(X)[(size_t)s * d_in + f] << 16) * v : 0.f;
+        else
+          a[it] = (live && f < d_in) ? X[(size_t)s * d_in + f] * v : 0.f;
       }
 #pragma unroll
       for (int jt = 0; jt < NJT; ++jt) {
         const int col = j0 + jt * 16 + m;
-        b[jt] = (live && col < d_out) ? G[(size_t)d * d_out + col] : 0.f;
+        if constexpr (BF)
+          b[jt] = (live && col < d_out) ? __uint_as_float((unsigned)reinterpret_cast<const uint16_t *>(G)[(size_t)d * d_out + col] << 16) : 0.f;
+        else
+          b[jt] = (live && col < d_out) ? G[(size_t)d * d_out + col] : 0.f;
       }
 #pragma unroll
       for (int it = 0; it < NIT; ++it)
@@ -542,7 +565,8 @@ __global__ __launch_bounds__(WG) void wgrad_generic_kernel(
 // sixteen (c,c') register pairs cover the whole 16x16 outer product:
 //     acc[c][c'] (block b, reg i, lane-col j)  +=  val * X[src_b][4i+c] * G[dst_b][4j+c']
 // The 16 blocks keep accumulating over all chunks of the work item and are summed once at the end.
-template <int U>
+// BF (rgcn_wgrad_bf16): X and G hold bf16 rows (8-byte quarter rows, widened); BF = false: the fp32 kernel as it was
+template <int U, bool BF = false>
 __global__ __launch_bounds__(WG) void wgrad_d16_kernel(
     const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ dW,
     const int *__restrict__ p_src, const int *__restrict__ p_dst, const float *__restrict__ p_val,
@@ -578,8 +602,13 @@ __global__ __launch_bounds__(WG) void wgrad_d16_kernel(
     float4 x[U], g[U];
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      x[j] = *reinterpret_cast<const float4 *>(X + (size_t)s[j] * 16 + 4 * q);
-      g[j] = *reinterpret_cast<const float4 *>(G + (size_t)max(d[j], 0) * 16 + 4 * q);   // pads: dst = -1, val = 0
+      if constexpr (BF) {
+        x[j] = bf16x4_widen(reinterpret_cast<const uint2 *>(X)[(size_t)s[j] * 4 + q]);
+        g[j] = bf16x4_widen(reinterpret_cast<const uint2 *>(G)[(size_t)max(d[j], 0) * 4 + q]);
+      } else {
+        x[j] = *reinterpret_cast<const float4 *>(X + (size_t)s[j] * 16 + 4 * q);
+        g[j] = *reinterpret_cast<const float4 *>(G + (size_t)max(d[j], 0) * 16 + 4 * q);   // pads: dst = -1, val = 0
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1014,7 +1043,8 @@ __global__ __launch_bounds__(WG) void diag_wgrad_kernel(
 // ------------------------------------------------------------------ column sum (bias gradient)
 // Two stages, no atomics, fixed summation order (bit-reproducible): stage A -- every workgroup streams its rows (float4 per
 // thread when d % 4 == 0) and leaves one partial row in `partial[block][d]`; stage B -- one workgroup sums the partial rows.
-template <bool VEC4>
+// BF (rgcn_colsum_bf16, VEC4 only): G holds bf16 rows (8 bytes per 4 columns, widened); BF = false: the fp32 kernel as it was
+template <bool VEC4, bool BF = false>
 __global__ __launch_bounds__(WG) void colsum_a_kernel(const float *__restrict__ G, float *__restrict__ partial, long long n, int d) {
   __shared__ float part[WG * 4];
   const int tid = threadIdx.x;
@@ -1027,7 +1057,9 @@ __global__ __launch_bounds__(WG) void colsum_a_kernel(const float *__restrict__ 
     if (grp < groups && cc < lanes)
       for (long long row = (long long)blockIdx.x * groups + grp; row < n; row += (long long)gridDim.x * groups) {
         if (VEC4) {
-          const float4 x = *reinterpret_cast<const float4 *>(G + (size_t)row * d + 4 * cc);
+          float4 x;
+          if constexpr (BF) x = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(G) + (size_t)row * d + 4 * cc));
+          else x = *reinterpret_cast<const float4 *>(G + (size_t)row * d + 4 * cc);
           a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
         } else {
           a.x += G[(size_t)row * d + cc];
@@ -1736,6 +1768,119 @@ extern "C" int rgcn_colsum_f32(const float *G, float *db, float *scratch, int64_
   const unsigned gx = (unsigned)std::min<int64_t>((n + groups - 1) / groups, max_part);
   if (vec4) hipLaunchKernelGGL(colsum_a_kernel<true>, dim3(gx), dim3(WG), 0, st, G, scratch, (long long)n, d);
   else hipLaunchKernelGGL(colsum_a_kernel<false>, dim3(gx), dim3(WG), 0, st, G, scratch, (long long)n, d);
+  hipLaunchKernelGGL(colsum_b_kernel, dim3(1), dim3(WG), 0, st, scratch, db, (int)gx, d);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+namespace {
+// fp32 values -> bf16 (the hub pieces' scratch of rgcn_spmm_bf16): one rounding per element, 4 per thread
+__global__ __launch_bounds__(WG) void round4_bf16_kernel(const float4 *__restrict__ src, uint2 *__restrict__ dst, long long n4) {
+  for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n4; i += (long long)gridDim.x * WG) dst[i] = bf16x4_round(src[i]);
+}
+}  // namespace
+
+extern "C" int rgcn_spmm_bf16(const uint16_t *X, const float *W_packed, const float *bias, uint16_t *out, float *scratch,
+                              const int32_t *p_pack, const int32_t *chunk_rel, const int32_t *units, int64_t n_units, int64_t n_split,
+                              int32_t tile_rows, int64_t n_dst, int64_t n_src, int32_t d_in, int32_t d_out, int32_t flags, void *stream) {
+  const bool relu = (flags & RGCN_F_RELU) != 0;
+  if (!X || !W_packed || !out || !p_pack || (n_units && (!units || !chunk_rel)) || tile_rows <= 0 || n_dst < 0 || n_units < 0 ||
+      n_split < 0 || n_src < 0 || n_src >= (int64_t(1) << 24) || d_in % 16 || d_out % 16 || d_in <= 0 || d_out <= 0 || d_in > 64 ||
+      d_out > 64 || (relu && n_split) || (n_split && !scratch)) {
+    rgcn_set_error("spmm_bf16: bad argument (packed slots: n_src < 2^24; widths multiples of 16 up to 64; hub pieces need the fp32 scratch "
+                   "and no relu)");
+    return RGCN_EINVAL;
+  }
+  if (n_units == 0) return RGCN_OK;
+  const size_t lds = (size_t)SPMM_WAVES * tile_rows * d_out * sizeof(float);
+  if (lds > LDS_TILE_BYTES) {
+    rgcn_set_error("spmm_bf16: %d waves x tile_rows*d_out*4 = %zu exceeds the %d-byte LDS budget", SPMM_WAVES, lds, LDS_TILE_BYTES);
+    return RGCN_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // hub pieces add fp32 rows into the zeroed scratch, rounded to bf16 once afterwards: never bf16 atomics (rounded at every add)
+  float *dst32 = n_split ? scratch : reinterpret_cast<float *>(out);
+  if (n_split) HIP_TRY(zero_async(scratch, (size_t)n_dst * d_out * sizeof(float), st));
+  dim3 grid((unsigned)((n_units + SPMM_WAVES - 1) / SPMM_WAVES)), block(WG);
+  const int nt = (int)n_units, ro = relu ? 1 : 0;
+  const float *Xf = reinterpret_cast<const float *>(X);
+  const int2 *pk = reinterpret_cast<const int2 *>(p_pack);
+  const int4 *up = reinterpret_cast<const int4 *>(units);
+#define RGCN_BF_D16(B)                                                                                                     \
+  hipLaunchKernelGGL((spmm_d16_kernel<4, true, B>), grid, block, lds, st, Xf, W_packed, bias, dst32, nullptr, nullptr, nullptr, pk, \
+                     chunk_rel, up, nt, tile_rows, (int)n_dst, ro)
+#define RGCN_BF_WIDE(NIC, NJC, UC, B)                                                                                      \
+  hipLaunchKernelGGL((spmm_wide_kernel<NIC, NJC, UC, B>), grid, block, lds, st, Xf, W_packed, bias, dst32, pk, chunk_rel, up, nt,    \
+                     tile_rows, (int)n_dst, ro)
+#define RGCN_BF_ROW(NIC, B)                                                                      \
+  switch (d_out / 16) {                                                                          \
+    case 1: RGCN_BF_WIDE(NIC, 1, 2, B); break;                                                   \
+    case 2: RGCN_BF_WIDE(NIC, 2, (NIC <= 2 ? 2 : 1), B); break;                                  \
+    case 3: RGCN_BF_WIDE(NIC, 3, 1, B); break;                                                   \
+    default: RGCN_BF_WIDE(NIC, 4, 1, B); break;                                                  \
+  }
+#define RGCN_BF_ALL(B)                                                                           \
+  if (d_in == 16 && d_out == 16) {                                                               \
+    RGCN_BF_D16(B);                                                                              \
+  } else {                                                                                       \
+    switch (d_in / 16) {                                                                         \
+      case 1: RGCN_BF_ROW(1, B) break;                                                           \
+      case 2: RGCN_BF_ROW(2, B) break;                                                           \
+      case 3: RGCN_BF_ROW(3, B) break;                                                           \
+      default: RGCN_BF_ROW(4, B) break;                                                          \
+    }                                                                                            \
+  }
+  if (n_split) {
+    RGCN_BF_ALL(1)
+    const long long n4 = n_dst * d_out / 4;
+    HIP_TRY(hipGetLastError());
+    if (n4) hipLaunchKernelGGL(round4_bf16_kernel, dim3((unsigned)std::min<long long>((n4 + WG - 1) / WG, 4096)), dim3(WG), 0, st,
+                               reinterpret_cast<const float4 *>(scratch), reinterpret_cast<uint2 *>(out), n4);
+  } else {
+    RGCN_BF_ALL(3)
+  }
+#undef RGCN_BF_ALL
+#undef RGCN_BF_ROW
+#undef RGCN_BF_WIDE
+#undef RGCN_BF_D16
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dW, const int32_t *p_src, const int32_t *p_dst,
+                               const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items, int32_t R,
+                               int32_t d_in, int32_t d_out, void *stream) {
+  if (!X || !G || !dW || R <= 0 || d_in <= 0 || d_out <= 0 || n_items < 0 || (n_items && (!p_src || !p_dst || !p_val || !chunk_rel || !items))) {
+    rgcn_set_error("wgrad_bf16: bad argument");
+    return RGCN_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(zero_async(dW, (size_t)R * d_in * d_out * sizeof(float), st));
+  if (n_items == 0) return RGCN_OK;
+  const unsigned gx = (unsigned)((n_items + WG / 64 - 1) / (WG / 64));
+  const int2 *it2 = reinterpret_cast<const int2 *>(items);
+  const float *Xf = reinterpret_cast<const float *>(X), *Gf = reinterpret_cast<const float *>(G);
+  if (d_in == 16 && d_out == 16) {
+    hipLaunchKernelGGL((wgrad_d16_kernel<4, true>), dim3(gx), dim3(WG), 0, st, Xf, Gf, dW, p_src, p_dst, p_val, chunk_rel, it2, (int)n_items);
+  } else {
+    constexpr int NIT = 2, NJT = 4;
+    const int nig = (d_in + 16 * NIT - 1) / (16 * NIT), njg = (d_out + 16 * NJT - 1) / (16 * NJT);
+    hipLaunchKernelGGL((wgrad_generic_kernel<NIT, NJT, true>), dim3(gx, (unsigned)(nig * njg)), dim3(WG), 0, st, Xf, Gf, dW, p_src, p_dst,
+                       p_val, chunk_rel, it2, (int)n_items, d_in, d_out, njg);
+  }
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_colsum_bf16(const uint16_t *G, float *db, float *scratch, int64_t n, int32_t d, void *stream) {
+  if (!G || !db || !scratch || n < 0 || d <= 0 || d % 4 || d > 256) { rgcn_set_error("colsum_bf16: bad argument (d a multiple of 4, at most 256)"); return RGCN_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) { HIP_TRY(zero_async(db, (size_t)d * sizeof(float), st)); return RGCN_OK; }
+  const int lanes = d / 4;
+  const int groups = std::max(1, WG / lanes);
+  const int64_t max_part = d <= 32 ? 512 : (d <= 128 ? 128 : 64);
+  const unsigned gx = (unsigned)std::min<int64_t>((n + groups - 1) / groups, max_part);
+  hipLaunchKernelGGL((colsum_a_kernel<true, true>), dim3(gx), dim3(WG), 0, st, reinterpret_cast<const float *>(G), scratch, (long long)n, d);
   hipLaunchKernelGGL(colsum_b_kernel, dim3(1), dim3(WG), 0, st, scratch, db, (int)gx, d);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;

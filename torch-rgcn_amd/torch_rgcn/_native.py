@@ -1398,6 +1398,66 @@ def spmm_blk(X, W, bias, plan, relu=False):
     return out
 
 
+def spmm_bf16(X, W, bias, plan, relu=False):
+    """out [n_dst, d_out] bf16 = bias + sum val X[src] W[rel] for bf16 X on a wave-owned plan with packed slots (rgcn_spmm_bf16): widths multiples
+    of 16 up to 64, W and bias fp32, fp32 sums rounded once; hub pieces summed in an fp32 scratch.  relu on a plan with hub pieces is applied
+    after the rounding (exact)."""
+    _req(X, "features", torch.bfloat16); _req(W, "weights"); _req(bias, "bias")
+    R, d_in, d_out = W.shape
+    assert X.shape == (plan.n_src, d_in) and R == plan.num_rels and plan.pack is not None
+    Wp = pack_w16(W) if (d_in, d_out) == (16, 16) else pack_w_blocks(W)
+    out = torch.empty((plan.n_dst, d_out), device=X.device, dtype=torch.bfloat16)
+    scratch = torch.empty((plan.n_dst, d_out), device=X.device, dtype=torch.float32) if plan.n_split else None
+    fused = relu and not plan.n_split
+    with _on(X.device), _timed("spmm_bf16"):
+        _check(lib().rgcn_spmm_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(plan.pack), _dp(plan.chunk_rel), _dp(plan.units),
+                                    c_i64(plan.n_units), c_i64(plan.n_split), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src),
+                                    c_i32(d_in), c_i32(d_out), c_i32(F_RELU if fused else 0), _stream(X.device)), "spmm_bf16")
+    return torch.relu_(out) if (relu and not fused) else out
+
+
+def wgrad_bf16(X, G, plan, num_rels):
+    """dW [R, d_in, d_out] fp32 = sum val X[src]^T G[dst] for bf16 X and G on the relation-major plan (rgcn_wgrad_bf16)"""
+    _req(X, "features", torch.bfloat16); _req(G, "grad_output", torch.bfloat16)
+    d_in, d_out = X.shape[1], G.shape[1]
+    dW = torch.empty((num_rels, d_in, d_out), device=X.device, dtype=torch.float32)
+    with _on(X.device), _timed("wgrad_bf16"):
+        _check(lib().rgcn_wgrad_bf16(_dp(X), _dp(G), _dp(dW), _dp(plan.src), _dp(plan.dst), _dp(plan.val), _dp(plan.chunk_rel),
+                                     _dp(plan.items), c_i64(plan.n_items), c_i32(num_rels), c_i32(d_in), c_i32(d_out),
+                                     _stream(X.device)), "wgrad_bf16")
+    return dW
+
+
+def colsum_bf16(G):
+    """db [d] fp32 = column sums of bf16 G (rgcn_colsum_bf16)"""
+    _req(G, "grad_output", torch.bfloat16)
+    db = torch.empty(G.shape[1], device=G.device, dtype=torch.float32)
+    scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(c_i64(G.shape[0]), c_i32(G.shape[1]))), device=G.device, dtype=torch.float32)
+    with _on(G.device), _timed("colsum_bf16"):
+        _check(lib().rgcn_colsum_bf16(_dp(G), _dp(db), _dp(scratch), c_i64(G.shape[0]), c_i32(G.shape[1]), _stream(G.device)), "colsum_bf16")
+    return db
+
+
+def spmm_blk_bf16(X, W, bias, plan, relu=False):
+    """out [n_dst, 16] bf16 = bias + sum val X[src] W_r for bf16 features X (rgcn_spmm_blk_bf16): rows gathered as bf16, fp32 products and
+    sums, one rounding; W and bias fp32.  Hub pieces are summed in an fp32 scratch and rounded afterwards."""
+    _req(X, "features", torch.bfloat16); _req(W, "weights"); _req(bias, "bias")
+    assert W.shape[1:] == (16, 16) and X.shape == (plan.n_src, 16)
+    dev = X.device
+    Wp = pack_w16(W)
+    out = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.bfloat16)
+    rec = _blk_rec(plan)
+    units, n_units, n_split = _blk_units(plan)
+    if relu and n_split:
+        raise NativeLibraryError("spmm_blk_bf16: relu in the epilogue needs a plan without hub pieces")
+    scratch = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.float32) if n_split else None
+    with _on(dev), _timed("spmm_blk_bf16"):
+        _check(lib().rgcn_spmm_blk_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(rec), _dp(plan.run_ptr), c_i64(plan.n_tiles),
+                                        c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src), c_i32(W.shape[0]),
+                                        c_i32(F_RELU if relu else 0), _dp(units), c_i64(n_units), c_i64(n_split), _stream(dev)), "spmm_blk_bf16")
+    return out
+
+
 def _bwd_blk_plan(plan, diag4=False):
     return (plan.tile_rows > 160 or (plan.tile_rows > 64 and bwd_route() == "blk")) and \
         bool(lib().rgcn_bwd_blk_supported(c_i32(plan.tile_rows), c_i32(plan.num_rels), c_i32(F_DIAG4 if diag4 else 0)))
@@ -1507,6 +1567,24 @@ def bwd_own(G, X, W, plan, relu=False, want_db=False):
         _check(lib().rgcn_bwd_own_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel),
                                       c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
                                       c_i32(F_RELU if relu else 0), _dp(db) if want_db else None, c_i64(plan.n_src), _stream(dev)), "bwd_own")
+    return (dX, dW, db if want_db else None)
+
+
+def bwd_own_bf16(G, X, W, plan, relu=False, want_db=False):
+    """bwd_own for bf16 storage (rgcn_bwd_own_bf16): G and X bf16, dX bf16 (fp32 sums, one rounding), dW and db fp32"""
+    _req(G, "grad_output", torch.bfloat16); _req(X, "features", torch.bfloat16); _req(W, "weights")
+    assert W.shape[1:] == (16, 16) and G.shape == (plan.n_src, 16) and X.shape == (plan.n_dst, 16) and W.shape[0] == plan.num_rels
+    assert getattr(plan, "own_ptr", None) is not None, "bwd_own_bf16: a plan made with build_softwin_plan(own_waves=...)"
+    dev = G.device
+    Wtp = pack_w16t(W)
+    dX = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.bfloat16)
+    buf = torch.empty(W.numel() + 16, device=dev, dtype=torch.float32)
+    dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
+    rec = _blk_rec(plan)
+    with _on(dev), _timed("bwd_own_bf16"):
+        _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel),
+                                       c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
+                                       c_i32(F_RELU if relu else 0), _dp(db) if want_db else None, c_i64(plan.n_src), _stream(dev)), "bwd_own_bf16")
     return (dX, dW, db if want_db else None)
 
 

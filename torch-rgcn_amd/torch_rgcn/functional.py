@@ -353,6 +353,98 @@ class _RelationalMP(torch.autograd.Function):
         return (*res, None, None, None, None)         # gradient BEFORE the producer's ReLU
 
 
+# ----------------------------------------------------------------------------- bf16 storage
+# A featured layer called with bf16 features returns bf16; every product and sum is fp32 and the result is rounded to bf16 once.  The weights
+# arrive here as the dense fp32 W (bf16 parameters are widened by the layer, once per call; nothing here rounds a weight).
+
+
+def _bf16_native_plans(graph, d_in, d_out, relu):
+    """the native bf16 route at padded widths (d_in, d_out) <= 64, or None (RGCN_DETERMINISTIC=1, wider layers, plans without packed slots:
+    the upcast route).  ("win", forward plan, owner plan): S1-shaped graphs at width 16 -- the soft-window forward (rgcn_spmm_blk_bf16) and the
+    relation-owner backward (rgcn_bwd_own_bf16: dX, dW and db in one walk).  ("wave", forward plan, transposed plan): every other graph
+    (host-built, device-built, per-call LP graphs, hub-split plans; RGCN_SOFTWIN=0, RGCN_BWD_OWN=0) -- rgcn_spmm_bf16 forward and dX,
+    rgcn_wgrad_bf16 on the relation-major plan, rgcn_colsum_bf16."""
+    if max(d_in, d_out) > 64 or deterministic():
+        return None
+    if d_in == 16 and d_out == 16 and routes.get("bwd_own", "1") != "0" and hasattr(graph, "win_plan"):
+        fp = _fwd_win(graph, relu)
+        op = graph.win_plan("bwd_own") if fp is not None else None
+        if op is not None and not _native._blk_units(op)[2]:
+            return "win", fp, op
+    fp, bp = graph.fwd_plan(d_out), graph.bwd_plan(d_in)
+    if fp.pack is None or bp.pack is None or fp.n_src >= (1 << 24) or bp.n_src >= (1 << 24):
+        return None
+    return "wave", fp, bp
+
+
+def _pad16(t, rows_last2):
+    """zero-pad the trailing dimensions of t to multiples of 16 (bf16 or fp32; a torch pad, as _pad_blocks' resize3 for fp32)"""
+    pads = []
+    for n in reversed(rows_last2):
+        pads += [0, -n % 16]
+    return torch.nn.functional.pad(t, pads) if any(pads) else t
+
+
+class _RelationalMPBF16(torch.autograd.Function):
+    """relational_mp on bf16 features, native routes (see _bf16_native_plans): X and the upstream gradient are gathered as bf16 rows, W
+    and the bias are fp32, out and dX are rounded to bf16 once, dW and db are fp32 sums returned in W's / the bias's dtype"""
+
+    @staticmethod
+    def forward(ctx, X, W, bias, graph, relu, plans):
+        d_in, d_out = W.shape[1], W.shape[2]
+        ctx.dims, ctx.plans, ctx.relu, ctx.has_bias = (d_in, d_out), plans, bool(relu), bias is not None
+        ctx.w_dtype, ctx.b_dtype = W.dtype, None if bias is None else bias.dtype
+        Xp = dense(_pad16(X, (d_in,)))
+        Wp = dense(_pad16(W.detach().float(), (d_in, d_out)))
+        bp = None if bias is None else dense(_pad16(bias.detach().float(), (d_out,)))
+        ctx.graph = graph
+        if plans[0] == "win":
+            out = _native.spmm_blk_bf16(Xp, Wp, bp, plans[1], relu=bool(relu))
+        else:
+            out = _native.spmm_bf16(Xp, Wp, bp, plans[1], relu=bool(relu))
+        ctx.save_for_backward(Xp, Wp, out if relu else None)
+        return out if out.shape[1] == d_out else out[:, :d_out].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        Xp, Wp, out = ctx.saved_tensors
+        d_in, d_out = ctx.dims
+        g = dense(_pad16(g.to(torch.bfloat16), (d_out,)))
+        if ctx.relu:
+            g = torch.ops.aten.threshold_backward(g, out, 0.0)        # a mask: exact in bf16
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.plans[0] == "win":
+            dX, dW, db = _native.bwd_own_bf16(g, Xp, Wp, ctx.plans[2], want_db=want_db)
+        else:
+            dX = _native.spmm_bf16(g, Wp.transpose(1, 2).contiguous(), None, ctx.plans[2]) if ctx.needs_input_grad[0] else None
+            dW = _native.wgrad_bf16(Xp, g, ctx.graph.wgt_plan(), Wp.shape[0]) if ctx.needs_input_grad[1] else None
+            db = _native.colsum_bf16(g) if want_db else None
+        if dX is not None and dX.shape[1] != d_in:
+            dX = dX[:, :d_in].contiguous()
+        dW = dW[:, :d_in, :d_out].to(ctx.w_dtype) if (ctx.needs_input_grad[1] and dW is not None) else None
+        db = db[:d_out].to(ctx.b_dtype) if db is not None else None
+        return (dX if ctx.needs_input_grad[0] else None), dW, db, None, None, None
+
+
+def relational_mp_bf16(features, weights, bias, graph, relu=False, group=None, n_slabs=0, comm="allreduce"):
+    """relational_mp for bf16 features: weights [R, d_in, d_out] and bias in fp32 (the layer widened bf16 parameters) -> bf16 [N, d_out].
+    Native HIP route where it applies (_bf16_native_plans); the rest -- widths above 64, relation-sharded layers (group),
+    RGCN_DETERMINISTIC=1 -- runs the fp32 route on the widened features and rounds its output: CORRECTNESS ONLY, no speed-up (autograd
+    carries the casts)."""
+    if features.dtype != torch.bfloat16:
+        raise TypeError(f"relational_mp_bf16: features must be torch.bfloat16, got {features.dtype}")
+    if weights.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise TypeError("relational_mp_bf16: weights and bias are widened to torch.float32 by the caller")
+    d16 = lambda n: n + (-n % 16)
+    plans = None if group is not None else _bf16_native_plans(graph, d16(weights.shape[1]), d16(weights.shape[2]), relu)
+    if plans is not None:
+        return _RelationalMPBF16.apply(features, weights, bias, graph, relu, plans)
+    if group is not None:
+        out = sharded_relational_mp(features.float(), weights, bias, graph, group, n_slabs, comm)
+        return (torch.relu(out) if relu else out).to(torch.bfloat16)
+    return relational_mp(features.float(), weights, bias, graph, relu=relu).to(torch.bfloat16)
+
+
 def _join_shards(partial, group, mode="allreduce"):
     """Sum the ranks' partial N x d matrices (in place; returns the tensor to use).  mode (an argument -- the sharded
     layer's transport, torch_rgcn.dist.set_transport -- not process-global state):

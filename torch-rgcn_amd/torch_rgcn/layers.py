@@ -120,6 +120,19 @@ class _RGCBase(Module):
         else:
             raise NotImplementedError(f'{kind} decomposition has not been implemented')
 
+    def _dense_weights_f32(self):
+        """the dense fp32 weights of the bf16 route: bf16 parameters widened once per call (autograd carries the casts back)"""
+        if getattr(self, "diag_weight_matrix", False):
+            return torch.diag_embed(self.weights.float())
+        kind = self.weight_decomp
+        if kind is None:
+            return self.weights.float()
+        if kind == 'basis':
+            B = self.bases.size(0)
+            W = F_.matmul_mfma(self.comps.float(), self.bases.float().reshape(B, -1))
+            return W.view(self.comps.size(0), *self.bases.shape[1:])
+        return block_diag(self.blocks.float())
+
     def _dense_weights(self):
         """(R, in_dim, out_dim) view of the (possibly decomposed) relation weights."""
         kind = self.weight_decomp
@@ -135,6 +148,26 @@ class _RGCBase(Module):
         if kind == 'block':
             return block_diag(self.blocks)
         raise NotImplementedError(f'{kind} decomposition has not been implemented')
+
+
+def _check_dtypes(layer, features):
+    """fp32 (the default) or bf16 features (bf16 out, fp32 arithmetic); the parameters fp32, or bf16 with bf16 features only"""
+    pdt = {p.dtype for p in layer.parameters()}
+    if features is None:
+        if pdt - {torch.float32}:
+            raise TypeError(f"featureless layers support torch.float32 parameters only, got {sorted(map(str, pdt))}")
+        return False
+    if features.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"features must be torch.float32 or torch.bfloat16 (opt-in, fp32 arithmetic), got {features.dtype}")
+    if pdt - {torch.float32, torch.bfloat16}:
+        raise TypeError(f"parameters must be torch.float32 or torch.bfloat16, got {sorted(map(str, pdt))}")
+    if features.dtype == torch.float32 and torch.bfloat16 in pdt:
+        raise TypeError("torch.bfloat16 parameters need torch.bfloat16 features (fp32 features take torch.float32 parameters)")
+    return features.dtype == torch.bfloat16
+
+
+def _f32(t):
+    return None if t is None else t.float()
 
 
 class RelationalGraphConvolutionNC(_RGCBase):
@@ -231,6 +264,8 @@ class RelationalGraphConvolutionNC(_RGCBase):
     def _forward_impl(self, features, activation, private=False):
         assert (features is None) == (self.in_features is None), "in_features not provided!"
         assert activation in (None, "relu"), f"unknown activation {activation!r}"
+        if _check_dtypes(self, features):
+            return self._forward_bf16(features, activation, private)
         any_param = self.weights if (self.diag_weight_matrix or self.weight_decomp is None) else \
             (self.bases if self.weight_decomp == 'basis' else self.blocks)
         _require_gpu(any_param, "RelationalGraphConvolutionNC parameters")
@@ -316,6 +351,25 @@ class RelationalGraphConvolutionNC(_RGCBase):
             output = output.index_select(0, graph.perm)
         return torch.relu(output) if activation == "relu" else output
 
+    def _forward_bf16(self, features, activation, private):
+        """bf16 features: every decomposition on its dense fp32 W, bf16 output rounded once"""
+        _require_gpu(features, "features")
+        N, out_dim = self.num_nodes, self.out_features
+        assert features.size() == (N, self.in_features), f"features {tuple(features.size())} vs ({N}, {self.in_features})"
+        any_param = next(self.parameters())
+        _require_gpu(any_param, "RelationalGraphConvolutionNC parameters")
+        graph = self._graph_on(any_param.device)
+        if graph.perm is not None:
+            features = features.index_select(0, graph.inv)
+        weights = self._dense_weights_f32()
+        assert weights.size() == (self.num_relations, self.in_features, out_dim)
+        relu = activation == "relu" and ("private" if private else True)
+        group = getattr(self, "_shard_group", None)
+        comm, slabs = getattr(self, "_shard_transport", ("allreduce", 0))
+        output = F_.relational_mp_bf16(features, weights, _f32(self.bias), graph, relu=relu, group=group, n_slabs=slabs, comm=comm)
+        assert output.size() == (N, out_dim)
+        return output.index_select(0, graph.perm) if graph.perm is not None else output
+
 
 class RelationalGraphConvolutionLP(_RGCBase):
     """R-GCN layer for link prediction; the message graph is supplied on every call."""
@@ -390,12 +444,16 @@ class RelationalGraphConvolutionLP(_RGCBase):
             graph = graph_from_lp_triples(triples, N, R, self.vertical_stacking, mask, device)
 
         assert features.size() == (N, in_dim)
+        bf16 = _check_dtypes(self, features)
         self_drop = None
         block_path = self.weight_decomp == 'block' and F_.use_block_path(graph, self.blocks)
         if self.weight_decomp == 'block':
             if training_dropout and self.edge_dropout["self_loop"] > 0:
                 # dense dropout on the self-loop messages X @ blocks_self before aggregation (added below)
                 self_drop = self.edge_dropout["self_loop"]
+        if bf16:
+            return self._forward_bf16(features, graph, self_drop)
+        if self.weight_decomp == 'block':
             if block_path:      # blocks applied as they are; the dense self-loop relation is added below
                 weights = None
             else:
@@ -425,3 +483,20 @@ class RelationalGraphConvolutionLP(_RGCBase):
             output = output + nn.functional.dropout(F_.matmul_mfma(features, self.blocks_self), p=self_drop, training=True)
         assert output.size() == (N, out_dim)
         return output
+
+    def _forward_bf16(self, features, graph, self_drop):
+        """bf16 features: the dense fp32 W of every decomposition (block: block_diag(blocks) with the dense self-loop relation),
+        bf16 output rounded once"""
+        if self.weight_decomp == 'block':
+            own = torch.zeros_like(self.blocks_self, dtype=torch.float32) if self_drop is not None else self.blocks_self.float()
+            weights = torch.cat([block_diag(self.blocks.float()), own[None]], dim=0)
+        else:
+            weights = self._dense_weights_f32()
+        assert weights.size() == (self.num_relations, self.in_features, self.out_features)
+        if self_drop is None:
+            return F_.relational_mp_bf16(features, weights, _f32(self.bias), graph)
+        # schlichtkrull-dropout: the self-loop messages are added before the one rounding (upcast route)
+        X = features.float()
+        output = F_.relational_mp(X, weights, _f32(self.bias), graph)
+        output = output + nn.functional.dropout(F_.matmul_mfma(X, self.blocks_self.float()), p=self_drop, training=True)
+        return output.to(torch.bfloat16)
