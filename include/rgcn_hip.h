@@ -599,6 +599,28 @@ RGCN_API int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, co
                                       int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream);
 RGCN_API int rgcn_fbasis_tile_bwd_fused_gn(int32_t R, int32_t B, int32_t d, int64_t n_nodes);
 
+/* The same three on a bf16 table (reference layers.py:241-242 + :286-288 for a featureless basis layer whose bases are
+ * bf16).  bf16 tensors are uint16_t bit patterns.  Shapes, modes, LDS budgets and rgcn_fbasis_tile_supported / _fused_gn are those of the
+ * fp32 entry points; a staged piece is 4 bf16 (8 bytes, aligned when N d % 4 == 0 and the pointers are 8-byte aligned), widened into the
+ * fp32 LDS tile.  Every product and sum is fp32, or fp64 where the kernels sum in LDS doubles; round to nearest even, a NaN stays NaN.
+ *   rgcn_fbasis_tile_fwd_bf16:    bases bf16; comps, e_val and the per-message scratch Y fp32 (Y holds partial sums: never rounded).
+ *   rgcn_gather_rows_sum4_bf16:   Y and bias fp32, out bf16, rounded once after the bias and the ReLU; columns w .. out_stride written as
+ *                                 zeros.  With rows cut into shared units (n_split > 0) the rows are summed in `scratch` (fp32, n_rows x
+ *                                 out_stride, 16-byte aligned) by rgcn_gather_rows_sum4_f32 and rounded (and ReLU'd) in a second launch --
+ *                                 never bf16 atomics; relu is allowed there too.
+ *   rgcn_fbasis_tile_bwd_bf16:    bases and G bf16 (G rows g_stride ELEMENTS apart), comps fp32; dbases bf16 in the parameter's [B, N, d]
+ *                                 layout, the fp32 / fp64 sum rounded once as it leaves the LDS; dcomps fp32.  No messages: dbases
+ *                                 zero-filled by a kernel. */
+RGCN_API int rgcn_fbasis_tile_fwd_bf16(const uint16_t *bases, const float *comps, float *Y, const int32_t *rowptr, const int32_t *e_rel,
+                                       const float *e_val, int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d,
+                                       int32_t mode, void *stream);
+RGCN_API int rgcn_gather_rows_sum4_bf16(const float *Y, int32_t ys, const int32_t *perm, const int32_t *units, int64_t n_units,
+                                        int64_t n_split, const float *bias, uint16_t *out, float *scratch, int64_t n_rows, int32_t w,
+                                        int32_t out_stride, int32_t relu, void *stream);
+RGCN_API int rgcn_fbasis_tile_bwd_bf16(const uint16_t *bases, const float *comps, const uint16_t *G, int32_t g_stride, uint16_t *dbases,
+                                       float *dcomps, const int32_t *rowptr, const int32_t *e_dst, const int32_t *e_rel, const float *e_val,
+                                       int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream);
+
 /* Classifier head of the node-classification experiments, one launch: loss = mean cross-entropy of the logits' LABELLED rows and
  * dlogits [N, C] = d loss / d logits (zero rows for unlabelled nodes).  Replaces `criterion(model()[train_idx, :], train_lbl)` with
  * nn.CrossEntropyLoss() and its autograd graph (reference experiments/classify_nodes.py:107-110, :129): row_label [N] = class of the

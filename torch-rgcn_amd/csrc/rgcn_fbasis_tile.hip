@@ -82,6 +82,48 @@ __device__ __forceinline__ int node_of(int rp, int lane, int p) {
   return __popcll(__ballot(lane >= 1 && lane <= TN && rp <= p));
 }
 
+// Storage T of the table, its gradient and the gathered gradient rows: float, or bf16 as uint16_t bit patterns.  Every
+// product and sum stays fp32 / fp64: a staged piece (4 consecutive elements, 16 or 8 bytes) flies through the pipeline in its packed form
+// (Piece<T>) and is widened as it goes into the fp32 LDS tile; a gathered element is held in a 32-bit register (Reg<T>) and widened where
+// it is used; a gradient piece is rounded once, on its way out (v_cvt_pk_bf16_f32).  For T = float every helper is the identity.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+template <typename T> struct Stor { typedef f32x4 piece; typedef float reg; };
+template <> struct Stor<uint16_t> { typedef u32x2 piece; typedef unsigned reg; };
+template <typename T> using Piece = typename Stor<T>::piece;
+template <typename T> using Reg = typename Stor<T>::reg;
+__device__ __forceinline__ f32x4 widen4(const f32x4 &v) { return v; }
+__device__ __forceinline__ f32x4 widen4(const u32x2 &u) {
+  const float4 f = bf16x4_widen(uint2{u[0], u[1]});
+  return f32x4{f.x, f.y, f.z, f.w};
+}
+__device__ __forceinline__ float widen1(float v) { return v; }
+__device__ __forceinline__ float widen1(unsigned v) { return __uint_as_float(v << 16); }
+template <typename T> __device__ __forceinline__ Piece<T> round4(const f32x4 &v);
+template <> __device__ __forceinline__ f32x4 round4<float>(const f32x4 &v) { return v; }
+template <> __device__ __forceinline__ u32x2 round4<uint16_t>(const f32x4 &v) {
+  const uint2 u = bf16x4_round(make_float4(v[0], v[1], v[2], v[3]));
+  return u32x2{u.x, u.y};
+}
+// (The fp32 code paths keep their own text behind `if constexpr`, statement order included: with equivalent shared helpers the compiler
+// scheduled the kernels near the register limit differently -- fbn_bwd_kernel, fbn_dbases_kernel, the four-piece staging.  tools/isa_compare.py
+// finds every fp32 instantiation identical to its form before bf16 storage.)
+// a bf16 piece of a table at `p`: one 8-byte load when aligned (VEC), else element by element
+template <bool VEC>
+__device__ __forceinline__ u32x2 piece_load_bf16(const uint16_t *p) {
+  if (VEC) return *reinterpret_cast<const u32x2 *>(p);
+  return u32x2{(unsigned)p[0] | ((unsigned)p[1] << 16), (unsigned)p[2] | ((unsigned)p[3] << 16)};
+}
+// a rounded bf16 piece out to `o`: elements pos + c >= lo only (the last tile's overlap); one store when VEC and whole
+template <bool VEC>
+__device__ __forceinline__ void piece_store_bf16(uint16_t *o, const u32x2 &v, int pos, int lo) {
+  if (VEC && pos >= lo) *reinterpret_cast<u32x2 *>(o) = v;
+  else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (pos + c >= lo) o[c] = (uint16_t)(v[c >> 1] >> (16 * (c & 1)));
+  }
+}
+
 // staging geometry of one thread: its 16-byte pieces of a tile (piece = 4 consecutive floats of one basis' run)
 template <int KLD>
 struct Geo { long long goff[KLD]; int loff[KLD], pos[KLD]; bool act[KLD]; };
@@ -98,21 +140,26 @@ __device__ __forceinline__ void geo_init(Geo<KLD> &g, int tid, int B, int d, lon
     g.pos[k] = 4 * q;
   }
 }
-template <int KLD, bool VEC>
-__device__ __forceinline__ void stage_load(f32x4 (&st)[KLD], const Geo<KLD> &g, const float *__restrict__ bases, long long base) {
+template <int KLD, bool VEC, typename T>
+__device__ __forceinline__ void stage_load(Piece<T> (&st)[KLD], const Geo<KLD> &g, const T *__restrict__ bases, long long base) {
 #pragma unroll
   for (int k = 0; k < KLD; ++k) {                            // no branches: a conditional load costs a phi, and the phi's temporary a wait
-    const float *p = bases + g.goff[k] + base;
-    if (VEC) st[k] = *reinterpret_cast<const f32x4 *>(p);
+    const T *p = bases + g.goff[k] + base;
+    if constexpr (sizeof(T) == 2) st[k] = piece_load_bf16<VEC>(p);     // (packed in flight: widened by stage_store)
+    else if (VEC) st[k] = *reinterpret_cast<const f32x4 *>(p);
     else st[k] = f32x4{p[0], p[1], p[2], p[3]};
   }
 }
-template <int KLD, bool V4>
-__device__ __forceinline__ void stage_store(float *buf, const f32x4 (&st)[KLD], const Geo<KLD> &g) {
+template <int KLD, bool V4, typename P>
+__device__ __forceinline__ void stage_store(float *buf, const P (&st)[KLD], const Geo<KLD> &g) {
 #pragma unroll
   for (int k = 0; k < KLD; ++k)
     if (g.act[k]) {
-      if (V4) *reinterpret_cast<f32x4 *>(buf + g.loff[k]) = st[k];
+      if constexpr (sizeof(P) == 8) {
+        const f32x4 v = widen4(st[k]);
+        if (V4) *reinterpret_cast<f32x4 *>(buf + g.loff[k]) = v;
+        else { buf[g.loff[k]] = v[0]; buf[g.loff[k] + 1] = v[1]; buf[g.loff[k] + 2] = v[2]; buf[g.loff[k] + 3] = v[3]; }
+      } else if (V4) *reinterpret_cast<f32x4 *>(buf + g.loff[k]) = st[k];
       else { buf[g.loff[k]] = st[k][0]; buf[g.loff[k] + 1] = st[k][1]; buf[g.loff[k] + 2] = st[k][2]; buf[g.loff[k] + 3] = st[k][3]; }
     }
 }
@@ -122,9 +169,9 @@ __device__ __forceinline__ void stage_store(float *buf, const f32x4 (&st)[KLD], 
 // node; coefficient table in LDS as [R][BP = NREG * (64 / DP)], zero padded.  Y rows are DP floats wide (zero padded: rgcn_gather_rows_sum4_f32
 // reads them 16 bytes per lane), written by the wave one iteration later from a wave-private LDS strip (coalesced, and issued before the
 // iteration's loads so no wait ever includes them).
-template <int DP, int NREG, int KLD, bool VEC>
+template <int DP, int NREG, int KLD, bool VEC, typename T>
 __global__ __launch_bounds__(TW) void fbt_fwd_kernel(
-    const float *__restrict__ bases, const float *__restrict__ comps, float *__restrict__ Y, const int *__restrict__ rowptr,
+    const T *__restrict__ bases, const float *__restrict__ comps, float *__restrict__ Y, const int *__restrict__ rowptr,
     const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B, int d, int ts, int last, int abl) {
   constexpr int NGRP = 64 / DP, BP = NREG * NGRP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -147,7 +194,7 @@ __global__ __launch_bounds__(TW) void fbt_fwd_kernel(
   };
   auto base_of = [&](int tt) { return (long long)min(min(tt, n_tiles - 1) * TN, N - TN) * d; };     // the last tile is staged from node N - 16
 
-  f32x4 st[KLD];
+  Piece<T> st[KLD];
   int rp = rp_of(t), rp1 = rp_of(t + G);
   stage_load<KLD, VEC>(st, g, bases, base_of(t));
   Share s = share_of(rp, wave, true);
@@ -266,10 +313,12 @@ __global__ __launch_bounds__(TW) void fbt_fwd_kernel(
 
 // out[row, 0..w) = (bias) + sum_j Y[perm[j], :] over the units of a row; Y rows are 4 LPR floats (16-byte pieces, one per lane), LPR lanes
 // per unit, two row reads in flight per lane (the layout of segment_gather_sum_units_d16_kernel for any width <= 16).
-template <int LPR>
+// TO = uint16_t: bf16 rows, rounded once after the bias and the ReLU; only launched on units that are not shared (hub rows go through
+// the fp32 form into a scratch and are rounded afterwards: no bf16 atomics)
+template <int LPR, typename TO = float>
 __global__ __launch_bounds__(256) void gather_rows_sum4_kernel(const float *__restrict__ Y, const int *__restrict__ perm,
                                                                const int4 *__restrict__ units, const float *__restrict__ bias,
-                                                               float *__restrict__ out, long long n_units, int w, int ow, int relu_out, int vec_out) {
+                                                               TO *__restrict__ out, long long n_units, int w, int ow, int relu_out, int vec_out) {
   const int q = threadIdx.x % LPR;
   for (long long u = ((long long)blockIdx.x * 256 + threadIdx.x) / LPR; u < n_units; u += ((long long)gridDim.x * 256) / LPR) {
     const int4 unit = units[u];
@@ -299,9 +348,22 @@ __global__ __launch_bounds__(256) void gather_rows_sum4_kernel(const float *__re
       }
     }
     a += b;
-    float *o = out + (size_t)unit.x * ow + 4 * q;           // rows of ow >= w floats: columns w .. ow are written as zeros (a zero-padded
+    TO *o = out + (size_t)unit.x * ow + 4 * q;              // rows of ow >= w floats: columns w .. ow are written as zeros (a zero-padded
                                                             // [N, 16] row is what the width-16 kernels of the next layer read in place)
-    if (!shared && vec_out) {                               // whole 16-byte pieces: one store per lane (four scalar ones: 0.34 -> 0.30 ms at AM size)
+    if constexpr (sizeof(TO) == 2) {
+      if (4 * q < ow) {
+        f32x4 v;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = 4 * q + c < w ? (relu_out ? fmaxf(a[c], 0.f) : a[c]) : 0.f;
+        const u32x2 r = round4<uint16_t>(v);
+        if (vec_out) *reinterpret_cast<u32x2 *>(o) = r;     // (ow % 4 == 0: the piece lies inside the row)
+        else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (4 * q + c < ow) o[c] = (uint16_t)(r[c >> 1] >> (16 * (c & 1)));
+        }
+      }
+    } else if (!shared && vec_out) {                             // whole 16-byte pieces: one store per lane (four scalar ones: 0.34 -> 0.30 ms at AM size)
       if (4 * q < ow) {
         f32x4 v;
 #pragma unroll
@@ -338,7 +400,9 @@ __device__ __forceinline__ Idx idx_load(const int *__restrict__ e_dst, const int
   return x;
 }
 // lanes (m, c >= d) re-read column d - 1 and messages past n the wave's last one: finite duplicates that no sum ever uses
-__device__ __forceinline__ void gather_rows(float (&gp)[GQ], const float *__restrict__ G, int es, int n, int d, int lane, int gstride) {
+// (T = bf16: the element is loaded into the low half of a 32-bit register and widened when it is laid down or used)
+template <typename T>
+__device__ __forceinline__ void gather_rows(Reg<T> (&gp)[GQ], const T *__restrict__ G, int es, int n, int d, int lane, int gstride) {
   const int m = lane >> 4, c = min(lane & 15, d - 1);
 #pragma unroll
   for (int q = 0; q < GQ; ++q)
@@ -347,18 +411,18 @@ __device__ __forceinline__ void gather_rows(float (&gp)[GQ], const float *__rest
       gp[q] = G[(size_t)s * gstride + c];
     }
 }
-template <int GS, int NQ>
-__device__ __forceinline__ void strip_store(float *gs, const float (&gp)[NQ], int n, int lane) {
+template <int GS, int NQ, typename R>
+__device__ __forceinline__ void strip_store(float *gs, const R (&gp)[NQ], int n, int lane) {
   const int m = lane >> 4, c = lane & 15;
 #pragma unroll
   for (int q = 0; q < NQ; ++q)
-    if (4 * q < n && c < GS) gs[(4 * q + m) * GS + c] = gp[q];          // (rows n .. 4 ceil(n / 4) hold duplicates of row n - 1)
+    if (4 * q < n && c < GS) gs[(4 * q + m) * GS + c] = widen1(gp[q]);  // (rows n .. 4 ceil(n / 4) hold duplicates of row n - 1)
 }
 
 // ---- dcomps[r,b] += val_e <bases[b,o_e,:], G[s_e,:]>: tiles staged like the forward's; dcomps summed per workgroup in an LDS table of doubles
-template <int DPB, int KLD, bool VEC>
+template <int DPB, int KLD, bool VEC, typename T>
 __global__ __launch_bounds__(TW) void fbt_dcomps_kernel(
-    const float *__restrict__ bases, const float *__restrict__ G, float *__restrict__ dC, const int *__restrict__ rowptr,
+    const T *__restrict__ bases, const T *__restrict__ G, float *__restrict__ dC, const int *__restrict__ rowptr,
     const int *__restrict__ e_dst, const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B,
     int d, int ts, int last, int gstride, int abl) {
   constexpr int GS = DPB;
@@ -381,14 +445,14 @@ __global__ __launch_bounds__(TW) void fbt_dcomps_kernel(
   const int bl = min(lane, B - 1);
   const bool has_b = lane < B;
 
-  f32x4 st[KLD];
+  Piece<T> st[KLD];
   int rp = rp_of(t), rp1 = rp_of(t + Gd), rp2 = rp_of(t + 2 * Gd);
   stage_load<KLD, VEC>(st, g, bases, base_of(t));
   Share s = share_of<PERB>(rp, wave, true);
   Idx x = idx_load(e_dst, e_rel, e_val, s.a, last, lane);
   Share s1 = share_of<PERB>(rp1, wave, t + Gd < n_tiles);
   Idx x1 = idx_load(e_dst, e_rel, e_val, s1.a, last, lane);
-  float gp1[GQ] = {};
+  Reg<T> gp1[GQ] = {};
   gather_rows(gp1, G, x.es, s.n, d, lane, gstride);
   strip_store<GS>(gs, gp1, s.n, lane);
   stage_store<KLD, false>(tb, st, g);
@@ -466,7 +530,7 @@ __global__ __launch_bounds__(TW) void fbt_dcomps_kernel(
       c_a = c0 + wave * s.per;                              // tiles with more than 16 x PERB messages: further chunks, loaded on demand
       c_n = max(0, min(s.per, min(c0 + TWV * s.per, s.me) - c_a));
       c_x = idx_load(e_dst, e_rel, e_val, c_a, last, lane);
-      float gq[GQ] = {};
+      Reg<T> gq[GQ] = {};
       gather_rows(gq, G, c_x.es, c_n, d, lane, gstride);
       FBT_ARRIVED(c_x.er); FBT_ARRIVED(c_x.ev);
       strip_store<GS>(gs, gq, c_n, lane);
@@ -486,9 +550,9 @@ __global__ __launch_bounds__(TW) void fbt_dcomps_kernel(
 // ---- dbases[b,o,:] = sum_e val_e comps[r_e,b] G[s_e,:]: per run of a node's messages D[b][i] += sum_m A[b][m] B[m][i] on the matrix cores
 // (v_mfma_f32_16x16x4_f32, four messages per step: A = val_m comps[r_m, 16 t + row] out of the LDS coefficient table, B = the strip's rows);
 // the tile's gradient is summed in LDS doubles (two tiles: one being written out while the next is summed) and written once, in place
-template <int DPB, int KLD, bool VEC>
+template <int DPB, int KLD, bool VEC, typename T>
 __global__ __launch_bounds__(TW) void fbt_dbases_kernel(
-    const float *__restrict__ comps, const float *__restrict__ G, float *__restrict__ dbases, const int *__restrict__ rowptr,
+    const float *__restrict__ comps, const T *__restrict__ G, T *__restrict__ dbases, const int *__restrict__ rowptr,
     const int *__restrict__ e_dst, const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B,
     int d, int ts, int last, int gstride, int abl) {
   constexpr int GS = DPB, NT = 4;                           // NT 16-row tiles of bases (B <= 64)
@@ -515,7 +579,7 @@ __global__ __launch_bounds__(TW) void fbt_dbases_kernel(
   Idx x = idx_load(e_dst, e_rel, e_val, s.a, last, lane);
   Share s1 = share_of<PERB>(rp1, wave, t + Gd < n_tiles);
   Idx x1 = idx_load(e_dst, e_rel, e_val, s1.a, last, lane);
-  float gp1[GQ] = {};
+  Reg<T> gp1[GQ] = {};
   gather_rows(gp1, G, x.es, s.n, d, lane, gstride);
   strip_store<GS>(gs, gp1, s.n, lane);
   int t_out = -1;                                           // the tile whose gradient waits in dt[(k - 1) & 1]
@@ -529,9 +593,10 @@ __global__ __launch_bounds__(TW) void fbt_dbases_kernel(
         double *p = src + g.loff[k2];
         const f32x4 v = {(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
         p[0] = 0.0; p[1] = 0.0; p[2] = 0.0; p[3] = 0.0;
-        float *o = dbases + g.goff[k2] + base;
+        T *o = dbases + g.goff[k2] + base;
         const int pos = g.pos[k2];
-        if (VEC && pos >= lo) *reinterpret_cast<f32x4 *>(o) = v;
+        if constexpr (sizeof(T) == 2) piece_store_bf16<VEC>(o, round4<T>(v), pos, lo);
+        else if (VEC && pos >= lo) *reinterpret_cast<f32x4 *>(o) = v;
         else {
 #pragma unroll
           for (int c = 0; c < 4; ++c)
@@ -593,7 +658,7 @@ __global__ __launch_bounds__(TW) void fbt_dbases_kernel(
       c_a = c0 + wave * s.per;
       c_n = max(0, min(s.per, min(c0 + TWV * s.per, s.me) - c_a));
       c_x = idx_load(e_dst, e_rel, e_val, c_a, last, lane);
-      float gq[GQ] = {};
+      Reg<T> gq[GQ] = {};
       gather_rows(gq, G, c_x.es, c_n, d, lane, gstride);
       FBT_ARRIVED(c_x.er); FBT_ARRIVED(c_x.ev);
       strip_store<GS>(gs, gq, c_n, lane);
@@ -631,8 +696,8 @@ __device__ __forceinline__ NodeRange node_range(int rp, int wave, bool valid) {
   return r;
 }
 // rows of up to 16 messages starting at entry `off` of the wave's 64 prefetched indices -> packed registers (see gather_rows)
-template <int NQ>
-__device__ __forceinline__ void gather_rows_at(float (&gp)[NQ], const float *__restrict__ G, int es, int off, int n, int d, int lane, int gstride) {
+template <int NQ, typename T>
+__device__ __forceinline__ void gather_rows_at(Reg<T> (&gp)[NQ], const T *__restrict__ G, int es, int off, int n, int d, int lane, int gstride) {
   const int m = lane >> 4, c = min(lane & 15, d - 1);
 #pragma unroll
   for (int q = 0; q < NQ; ++q)
@@ -644,8 +709,8 @@ __device__ __forceinline__ void gather_rows_at(float (&gp)[NQ], const float *__r
 
 // the first rows of the wave's run, ALWAYS four loads (a run shorter than 16 re-reads its last row, an empty one entry 0 of the indices):
 // a fixed number of loads per iteration lets the compiler count them (s_waitcnt vmcnt(n)) instead of draining everything
-template <int NQ>
-__device__ __forceinline__ void gather_rows_all(float (&gp)[NQ], const float *__restrict__ G, int es, int n, int d, int lane, int gstride) {
+template <int NQ, typename T>
+__device__ __forceinline__ void gather_rows_all(Reg<T> (&gp)[NQ], const T *__restrict__ G, int es, int n, int d, int lane, int gstride) {
   const int m = lane >> 4, c = min(lane & 15, d - 1);
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -654,9 +719,9 @@ __device__ __forceinline__ void gather_rows_all(float (&gp)[NQ], const float *__
   }
 }
 
-template <int NKSM, int KLD, bool VEC>
+template <int NKSM, int KLD, bool VEC, typename T>
 __global__ __launch_bounds__(TW) void fbn_fwd_kernel(
-    const float *__restrict__ bases, const float *__restrict__ comps, float *__restrict__ Y, const int *__restrict__ rowptr,
+    const T *__restrict__ bases, const float *__restrict__ comps, float *__restrict__ Y, const int *__restrict__ rowptr,
     const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B, int d, int ts, int last, int ys,
     int abl) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -683,7 +748,7 @@ __global__ __launch_bounds__(TW) void fbn_fwd_kernel(
   };
   auto base_of = [&](int tt) { return (long long)min(min(tt, n_tiles - 1) * TN, N - TN) * d; };
 
-  f32x4 st[KLD];
+  Piece<T> st[KLD];
   int rp = rp_of(t), rp1 = rp_of(t + G);
   stage_load<KLD, VEC>(st, g, bases, base_of(t));
   NodeRange s = node_range(rp, wave, true);
@@ -771,9 +836,9 @@ __global__ __launch_bounds__(TW) void fbn_fwd_kernel(
   flush();
 }
 
-template <int NKD, int KLD, bool VEC>
+template <int NKD, int KLD, bool VEC, typename T>
 __global__ __launch_bounds__(TW) void fbn_dcomps_kernel(
-    const float *__restrict__ bases, const float *__restrict__ G, float *__restrict__ dC, const int *__restrict__ rowptr,
+    const T *__restrict__ bases, const T *__restrict__ G, float *__restrict__ dC, const int *__restrict__ rowptr,
     const int *__restrict__ e_dst, const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B,
     int d, int ts, int last, int gstride, int abl) {
   constexpr int GS = 4 * NKD, NBTM = 4;
@@ -796,14 +861,14 @@ __global__ __launch_bounds__(TW) void fbn_dcomps_kernel(
   };
   auto base_of = [&](int tt) { return (long long)min(min(tt, n_tiles - 1) * TN, N - TN) * d; };
 
-  f32x4 st[KLD];
+  Piece<T> st[KLD];
   int rp = rp_of(t), rp1 = rp_of(t + Gd), rp2 = rp_of(t + 2 * Gd);
   stage_load<KLD, VEC>(st, g, bases, base_of(t));
   NodeRange s = node_range(rp, wave, true);
   Idx x = idx_load(e_dst, e_rel, e_val, s.a, last, lane);
   NodeRange s1 = node_range(rp1, wave, t + Gd < n_tiles);
   Idx x1 = idx_load(e_dst, e_rel, e_val, s1.a, last, lane);
-  float gp1[GQ] = {};
+  Reg<T> gp1[GQ] = {};
   gather_rows_at(gp1, G, x.es, 0, min(16, s.n), d, lane, gstride);
   strip_store<GS>(gs, gp1, min(16, s.n), lane);
   stage_store<KLD, false>(tb, st, g);
@@ -845,7 +910,7 @@ __global__ __launch_bounds__(TW) void fbn_dcomps_kernel(
             c_x = idx_load(e_dst, e_rel, e_val, s.a + g0, last, lane);
             FBT_ARRIVED(c_x.es); FBT_ARRIVED(c_x.er); FBT_ARRIVED(c_x.ev);
           }
-          float gq[GQ] = {};
+          Reg<T> gq[GQ] = {};
           gather_rows_at(gq, G, c_x.es, g0 & 63, n16, d, lane, gstride);
           strip_store<GS>(gs, gq, n16, lane);
         }
@@ -895,9 +960,9 @@ __global__ __launch_bounds__(TW) void fbn_dcomps_kernel(
 // half as often and a tile's message loops are as long as the memory latency they have to cover
 // NW waves per workgroup: 16 (one workgroup per CU, the tile gradient double-buffered) or 8 (512 threads, ONE tile buffer, 75 KB of LDS: two
 // workgroups per CU -- one's stores and loads fly under the other's message loops; a single workgroup's waves are all in the same phase)
-template <int NKD, int KLD, bool VEC, int NPW, int NW>
+template <int NKD, int KLD, bool VEC, int NPW, int NW, typename T>
 __global__ __launch_bounds__(64 * NW) void fbn_dbases_kernel(
-    const float *__restrict__ comps, const float *__restrict__ G, float *__restrict__ dbases, const int *__restrict__ rowptr,
+    const float *__restrict__ comps, const T *__restrict__ G, T *__restrict__ dbases, const int *__restrict__ rowptr,
     const int *__restrict__ e_dst, const int *__restrict__ e_rel, const float *__restrict__ e_val, int n_tiles, int N, int R, int B,
     int d, int ts, int last, int gstride, int abl) {
   constexpr int GS = 4 * NKD, NBTM = 4, TNV = NW * NPW, NTH = 64 * NW;
@@ -932,23 +997,28 @@ __global__ __launch_bounds__(64 * NW) void fbn_dbases_kernel(
   Idx x = idx_load(e_dst, e_rel, e_val, s.a, last, lane);
   NodeRange s1 = range_of(rp1, t + Gd < n_tiles);
   Idx x1 = idx_load(e_dst, e_rel, e_val, s1.a, last, lane);
-  float gp1[NQ] = {};
+  Reg<T> gp1[NQ] = {};
   gather_rows_at(gp1, G, x.es, 0, min(SR, s.n), d, lane, gstride);
   strip_store<GS>(gs, gp1, min(SR, s.n), lane);
   // the tile whose gradient waits in the other buffer.  Before the first tile: the workgroup's own first tile -- whatever the LDS holds goes out
   // and is overwritten one iteration later by the same threads: every iteration then issues the same number of stores, which lets the
   // compiler wait for the iteration's LOADS with an exact count and leave the stores in flight
   int t_out = t;
-  f32x4 kept[KLD];                                          // the stored pieces, kept alive over the message loops (see fbn_fwd_kernel's flush)
+  Piece<T> kept[KLD];                                       // the stored pieces, kept alive over the message loops (see fbn_fwd_kernel's flush)
   auto write_out = [&](const float *src, int part) {        // part < NPW: that share of the thread's pieces; part < 0: all of them
     const long long base = (long long)first_of(t_out) * d;
 #pragma unroll
     for (int k2 = 0; k2 < KLD; ++k2)
       if (!FBT_ABL(32) && (part < 0 || k2 * NPW / KLD == part)) {      // (a thread without a k2-th piece stores piece 0 again: same bytes, no predicate)
-        kept[k2] = *reinterpret_cast<const f32x4 *>(src + g.loff[k2]);
-        float *o = dbases + g.goff[k2] + base;
-        if (VEC) *reinterpret_cast<f32x4 *>(o) = kept[k2];  // (non-temporal stores measured the same)
-        else { o[0] = kept[k2][0]; o[1] = kept[k2][1]; o[2] = kept[k2][2]; o[3] = kept[k2][3]; }
+        if constexpr (sizeof(T) == 2) {
+          kept[k2] = round4<T>(*reinterpret_cast<const f32x4 *>(src + g.loff[k2]));
+          piece_store_bf16<VEC>(dbases + g.goff[k2] + base, kept[k2], 0, 0);
+        } else {
+          kept[k2] = *reinterpret_cast<const f32x4 *>(src + g.loff[k2]);
+          float *o = dbases + g.goff[k2] + base;
+          if (VEC) *reinterpret_cast<f32x4 *>(o) = kept[k2];  // (non-temporal stores measured the same)
+          else { o[0] = kept[k2][0]; o[1] = kept[k2][1]; o[2] = kept[k2][2]; o[3] = kept[k2][3]; }
+        }
       }
   };
   FBT_DBG(long long dbg[6] = {0, 0, 0, 0, 0, 0};)
@@ -988,7 +1058,7 @@ __global__ __launch_bounds__(64 * NW) void fbn_dbases_kernel(
         if (g0 + n16 > sb0 + SR) {                          // past the prefetched rows
           sb0 = g0;
           const int nrow = min(SR, min(s.n, cb0 + 64) - g0);  // a whole window (the next node's group may start inside it)
-          float gq[NQ] = {};
+          Reg<T> gq[NQ] = {};
           gather_rows_at(gq, G, c_x.es, g0 - cb0, nrow, d, lane, gstride);
           strip_store<GS>(gs, gq, nrow, lane);
         }
@@ -1057,9 +1127,9 @@ template <int NK>
 struct __attribute__((packed, aligned(4))) FK { float f[NK]; };
 struct __attribute__((packed, aligned(4))) F2U { float f[2]; };
 
-template <int NKD, int KLD, bool VEC, int NBTM>
+template <int NKD, int KLD, bool VEC, int NBTM, typename T>
 __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
-    const float *__restrict__ bases, const float *__restrict__ comps, const float *__restrict__ G, float *__restrict__ dbases,
+    const T *__restrict__ bases, const float *__restrict__ comps, const T *__restrict__ G, T *__restrict__ dbases,
     float *__restrict__ dC, const int *__restrict__ rowptr, const int *__restrict__ e_dst, const int *__restrict__ e_rel,
     const float *__restrict__ e_val, int n_tiles, int N, int R, int B, int d, int ts, int last, int gstride, int gn, int abl) {
   // (NBTM = ceil(B / 16): the 16-row tiles of bases, a template parameter -- registers)
@@ -1084,11 +1154,12 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
   }
   const long long Nd = (long long)N * d;
   auto piece_act = [&](int k2) { return tid + k2 * TW < B * q4; };
-  auto tile_load = [&](f32x4 (&st)[KLD], long long base) {
+  auto tile_load = [&](Piece<T> (&st)[KLD], long long base) {
 #pragma unroll
     for (int k2 = 0; k2 < KLD; ++k2) {
-      const float *p = bases + (bq[k2] >> 16) * Nd + 4 * (bq[k2] & 0xffff) + base;
-      if (VEC) st[k2] = *reinterpret_cast<const f32x4 *>(p);
+      const T *p = bases + (bq[k2] >> 16) * Nd + 4 * (bq[k2] & 0xffff) + base;
+      if constexpr (sizeof(T) == 2) st[k2] = piece_load_bf16<VEC>(p);
+      else if (VEC) st[k2] = *reinterpret_cast<const f32x4 *>(p);
       else st[k2] = f32x4{p[0], p[1], p[2], p[3]};
     }
   };
@@ -1099,7 +1170,7 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
     return rowptr[min((long long)tt * TN + min(lane, TN), (long long)N)];
   };
   auto base_of = [&](int tt) { return (long long)min(min(tt, n_tiles - 1) * TN, N - TN) * d; };
-  auto rows_first = [&](float (&gp)[GQ], int es, int n) {    // the first rows of the wave's run: always GQ loads (see gather_rows_all)
+  auto rows_first = [&](Reg<T> (&gp)[GQ], int es, int n) {   // the first rows of the wave's run: always GQ loads (see gather_rows_all)
     const int m = lane >> 4, cc = min(lane & 15, d - 1);
 #pragma unroll
     for (int q = 0; q < GQ; ++q) {
@@ -1107,7 +1178,7 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
       gp[q] = G[(size_t)sidx * gstride + cc];
     }
   };
-  auto rows_at = [&](float (&gp)[GQ], int es, int off, int n) {
+  auto rows_at = [&](Reg<T> (&gp)[GQ], int es, int off, int n) {
     const int m = lane >> 4, cc = min(lane & 15, d - 1);
 #pragma unroll
     for (int q = 0; q < GQ; ++q)
@@ -1117,21 +1188,27 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
       }
   };
 
-  f32x4 st[KLD], kept[KLD];
+  Piece<T> st[KLD], kept[KLD];
   int rp = rp_of(t), rp1 = rp_of(t + Gd), rp2 = rp_of(t + 2 * Gd);
   tile_load(st, base_of(t));
   NodeRange s = node_range(rp, wave, true);
   Idx x = idx_load(e_dst, e_rel, e_val, s.a, last, lane);
   NodeRange s1 = node_range(rp1, wave, t + Gd < n_tiles);
   Idx x1 = idx_load(e_dst, e_rel, e_val, s1.a, last, lane);
-  float gp[GQ], gp1[GQ];                                    // rows of the current tile's messages, of the next tile's
+  Reg<T> gp[GQ], gp1[GQ];                                   // rows of the current tile's messages, of the next tile's
   rows_first(gp, x.es, min(gn, s.n));
 #pragma unroll
   for (int k2 = 0; k2 < KLD; ++k2)
-    if (piece_act(k2)) *reinterpret_cast<f32x4 *>(xt + (bq[k2] >> 16) * ts + 4 * (bq[k2] & 0xffff)) = st[k2];
+    if (piece_act(k2)) {
+      if constexpr (sizeof(T) == 2) *reinterpret_cast<f32x4 *>(xt + (bq[k2] >> 16) * ts + 4 * (bq[k2] & 0xffff)) = widen4(st[k2]);
+      else *reinterpret_cast<f32x4 *>(xt + (bq[k2] >> 16) * ts + 4 * (bq[k2] & 0xffff)) = st[k2];
+    }
   tile_load(st, base_of(t + Gd));
 #pragma unroll
-  for (int k2 = 0; k2 < KLD; ++k2) kept[k2] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k2 = 0; k2 < KLD; ++k2) {
+    if constexpr (sizeof(T) == 2) kept[k2] = u32x2{0u, 0u};
+    else kept[k2] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   lds_barrier();
 
   // one tile per iteration; st = tile t + Gd, requested one hand-over ago and laid down at this iteration's hand-over
@@ -1183,7 +1260,7 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
         // operations in order: no barrier)
 #pragma unroll
         for (int q = 0; q < GQ; ++q)
-          if (4 * q < n16 && c < d) xt[(4 * q + k) * ts + nl * d + c] = gp[q];
+          if (4 * q < n16 && c < d) xt[(4 * q + k) * ts + nl * d + c] = widen1(gp[q]);
         float av[NKD];
         {
           // A row c holds message pm = 4 (c & 3) + (c >> 2) -- the 4 x 4 transpose of the row index -- so that D's row 4 k + e is message 4 e + k:
@@ -1225,7 +1302,7 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
             const float v = (4 * q + k < n16) ? vs : 0.f;
 #pragma unroll
             for (int tb2 = 0; tb2 < NBTM; ++tb2)
-              if (tb2 < nbt) accD[tb2] = __builtin_amdgcn_mfma_f32_16x16x4f32(gp[q], ctab[r * B + min(16 * tb2 + c, B - 1)] * v, accD[tb2], 0, 0, 0);
+              if (tb2 < nbt) accD[tb2] = __builtin_amdgcn_mfma_f32_16x16x4f32(widen1(gp[q]), ctab[r * B + min(16 * tb2 + c, B - 1)] * v, accD[tb2], 0, 0, 0);
           }
       }
     }
@@ -1269,17 +1346,23 @@ __global__ __launch_bounds__(TW) void fbn_bwd_kernel(
         if (piece_act(k2)) {
           const int pos = 4 * (bq[k2] & 0xffff);
           float *p = xt + (bq[k2] >> 16) * ts + pos;
-          kept[k2] = *reinterpret_cast<const f32x4 *>(p);
-          float *o = dbases + (bq[k2] >> 16) * Nd + pos + base;
-          if (!FBT_ABL(32)) {
-            if (VEC && pos >= lo) *reinterpret_cast<f32x4 *>(o) = kept[k2];
-            else {
+          if constexpr (sizeof(T) == 2) {
+            kept[k2] = round4<T>(*reinterpret_cast<const f32x4 *>(p));
+            if (!FBT_ABL(32)) piece_store_bf16<VEC>(dbases + (bq[k2] >> 16) * Nd + pos + base, kept[k2], pos, lo);
+            if (has1) *reinterpret_cast<f32x4 *>(p) = widen4(st[k2]);
+          } else {
+            kept[k2] = *reinterpret_cast<const f32x4 *>(p);
+            float *o = dbases + (bq[k2] >> 16) * Nd + pos + base;
+            if (!FBT_ABL(32)) {
+              if (VEC && pos >= lo) *reinterpret_cast<f32x4 *>(o) = kept[k2];
+              else {
 #pragma unroll
-              for (int cc = 0; cc < 4; ++cc)
-                if (pos + cc >= lo) o[cc] = kept[k2][cc];
+                for (int cc = 0; cc < 4; ++cc)
+                  if (pos + cc >= lo) o[cc] = kept[k2][cc];
+              }
             }
+            if (has1) *reinterpret_cast<f32x4 *>(p) = st[k2];
           }
-          if (has1) *reinterpret_cast<f32x4 *>(p) = st[k2];
         }
       if (!FBT_ABL(2)) tile_load(st, base_of(t + 2 * Gd));     // (past the end: the last tile again, never laid down)
     }
@@ -1353,7 +1436,9 @@ hipError_t raise_lds(K kernel, size_t bytes) {
 
 }  // namespace
 
-#ifdef RGCN_ABLATIONS
+// Entry points.  The bf16 ones are compiled in a translation unit of their own (rgcn_fbasis_tile_bf16.hip defines RGCN_FBT_BF16 and
+// includes this file): both storages in one unit took 62 s to compile against 35 s for fp32 alone; split, the halves build side by side.
+#if defined(RGCN_ABLATIONS) && !defined(RGCN_FBT_BF16)
 /* ablation library only: 100 MHz ticks summed over the waves of all forward tile launches since the last reset:
  * {arrival + tile store + Y flush, issue of the next loads, message loops, barrier, rotation, waves} */
 extern "C" __attribute__((visibility("default"))) int rgcn_fbt_debug_read(unsigned long long *out8, int reset) {
@@ -1368,6 +1453,7 @@ extern "C" __attribute__((visibility("default"))) int rgcn_fbt_debug_read(unsign
 }
 #endif
 
+#ifndef RGCN_FBT_BF16
 extern "C" int rgcn_fbasis_tile_supported(int32_t R, int32_t B, int32_t d, int64_t n_nodes) {
   TileShape s;
   if (!tile_shape(R, B, d, n_nodes, s)) return 0;
@@ -1376,10 +1462,13 @@ extern "C" int rgcn_fbasis_tile_supported(int32_t R, int32_t B, int32_t d, int64
 }
 
 extern "C" int rgcn_fbasis_tile_ystride(int32_t d) { return d >= 1 && d <= 16 ? pow2_at_least(d, 4) : 0; }
+#endif
 
-extern "C" int rgcn_fbasis_tile_fwd_f32(const float *bases, const float *comps, float *Y, const int32_t *rowptr, const int32_t *e_rel,
-                                        const float *e_val, int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode,
-                                        void *stream) {
+namespace {
+// the entry points for storage T (float / bf16 bit patterns); fp32 and bf16 launch the same kernels with the same shapes
+template <typename T>
+int fbasis_tile_fwd(const T *bases, const float *comps, float *Y, const int32_t *rowptr, const int32_t *e_rel, const float *e_val,
+                    int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream) {
   TileShape s;
   if (n_messages == 0) return RGCN_OK;
   if (!bases || !comps || !Y || !rowptr || !e_rel || !e_val || n_messages < 0 || n_messages > INT32_MAX) { rgcn_set_error("fbasis_tile_fwd: bad argument"); return RGCN_EINVAL; }
@@ -1387,15 +1476,15 @@ extern "C" int rgcn_fbasis_tile_fwd_f32(const float *bases, const float *comps, 
   const int abl = rgcn_option_value(RGCN_OPT_BWD_ABL);      // 0 in the shipped library (rgcn_set_option refuses it)
   if (!tile_shape(R, B, d, n_nodes, s) || (mode ? s.lds_fwd_n : s.lds_fwd) > (size_t)LDS_MAX || (mode != 0 && mode != 1)) { rgcn_set_error("fbasis_tile_fwd: shape outside the tile kernel (rgcn_fbasis_tile_supported)"); return RGCN_EUNSUPPORTED; }
   const int n_tiles = (int)((n_nodes + TN - 1) / TN);
-  const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % 16 == 0);
+  const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % (4 * sizeof(T)) == 0);
   const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cus()));
   hipStream_t st = (hipStream_t)stream;
   if (mode == 1) {                                          // one wave per node, MFMA
     const int ys = pow2_at_least(d, 4);
 #define FBN_FWD3(NK_, KL_, VE_)                                                                                                 \
   {                                                                                                                             \
-    HIP_TRY(raise_lds(fbn_fwd_kernel<NK_, KL_, VE_>, s.lds_fwd_n));                                                             \
-    hipLaunchKernelGGL((fbn_fwd_kernel<NK_, KL_, VE_>), grid, dim3(TW), s.lds_fwd_n, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
+    HIP_TRY(raise_lds(fbn_fwd_kernel<NK_, KL_, VE_, T>, s.lds_fwd_n));                                                          \
+    hipLaunchKernelGGL((fbn_fwd_kernel<NK_, KL_, VE_, T>), grid, dim3(TW), s.lds_fwd_n, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                        (int)n_nodes, R, B, d, s.ts_f, last, ys, abl);                                                            \
   }
 #define FBN_FWD2(NK_, KL_) { if (vec) FBN_FWD3(NK_, KL_, true) else FBN_FWD3(NK_, KL_, false) }
@@ -1410,12 +1499,12 @@ extern "C" int rgcn_fbasis_tile_fwd_f32(const float *bases, const float *comps, 
 #define FBT_FWD3(DP_, NR_, KL_)                                                                                                   \
   {                                                                                                                               \
     if (vec) {                                                                                                                    \
-      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, true>, s.lds_fwd));                                                         \
-      hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, true>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
+      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, true, T>, s.lds_fwd));                                                      \
+      hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, true, T>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                          (int)n_nodes, R, B, d, s.ts_f, last, abl);                                                                          \
     } else {                                                                                                                      \
-      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, false>, s.lds_fwd));                                                        \
-      hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, false>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
+      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, false, T>, s.lds_fwd));                                                     \
+      hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, false, T>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                          (int)n_nodes, R, B, d, s.ts_f, last, abl);                                                                          \
     }                                                                                                                             \
   }
@@ -1428,7 +1517,23 @@ extern "C" int rgcn_fbasis_tile_fwd_f32(const float *bases, const float *comps, 
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
+}  // namespace
 
+#ifndef RGCN_FBT_BF16
+extern "C" int rgcn_fbasis_tile_fwd_f32(const float *bases, const float *comps, float *Y, const int32_t *rowptr, const int32_t *e_rel,
+                                        const float *e_val, int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode,
+                                        void *stream) {
+  return fbasis_tile_fwd(bases, comps, Y, rowptr, e_rel, e_val, n_messages, n_nodes, R, B, d, mode, stream);
+}
+#else
+extern "C" int rgcn_fbasis_tile_fwd_bf16(const uint16_t *bases, const float *comps, float *Y, const int32_t *rowptr, const int32_t *e_rel,
+                                         const float *e_val, int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode,
+                                         void *stream) {
+  return fbasis_tile_fwd(bases, comps, Y, rowptr, e_rel, e_val, n_messages, n_nodes, R, B, d, mode, stream);
+}
+#endif
+
+#ifndef RGCN_FBT_BF16
 namespace {
 __global__ __launch_bounds__(1024) void poison_lds_kernel(int n_words) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1473,7 +1578,59 @@ extern "C" int rgcn_gather_rows_sum4_f32(const float *Y, int32_t ys, const int32
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
+#endif
 
+#ifdef RGCN_FBT_BF16
+namespace {
+// dst[i] = bf16(max(src[i], 0) or src[i]), n any count (rows of [N, 10] do not come in multiples of 4 elements: round4_bf16_kernel's form
+// with a scalar tail)
+__global__ __launch_bounds__(256) void round_bf16_kernel(const float *__restrict__ src, uint16_t *__restrict__ dst, long long n, int relu) {
+  const long long n4 = n / 4, stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 v = reinterpret_cast<const f32x4 *>(src)[i];
+    if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+    reinterpret_cast<u32x2 *>(dst)[i] = round4<uint16_t>(v);
+  }
+  for (long long i = 4 * n4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float v = relu ? fmaxf(src[i], 0.f) : src[i];
+    dst[i] = (uint16_t)(bf16x2_round(v, 0.f) & 0xFFFFu);
+  }
+}
+}  // namespace
+
+extern "C" int rgcn_gather_rows_sum4_bf16(const float *Y, int32_t ys, const int32_t *perm, const int32_t *units, int64_t n_units,
+                                          int64_t n_split, const float *bias, uint16_t *out, float *scratch, int64_t n_rows, int32_t w,
+                                          int32_t out_stride, int32_t relu, void *stream) {
+  const int ow = out_stride;
+  if (n_units < 0 || n_rows < 0 || w <= 0 || w > ys || ow < w || ow > ys || (ys != 4 && ys != 8 && ys != 16) || (n_units && (!Y || !perm || !units || !out)) ||
+      (n_split && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || (reinterpret_cast<uintptr_t>(out) & 7)))) {
+    rgcn_set_error("gather_rows_sum4_bf16: bad argument (rows cut into shared units need a 16-byte aligned fp32 scratch of n_rows x out_stride "
+                   "and an 8-byte aligned out)");
+    return RGCN_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (n_split) {
+    // hub rows: summed in fp32 (the f32 form's atomics into the scratch), then rounded once -- the ReLU with the rounding
+    const int rc = rgcn_gather_rows_sum4_f32(Y, ys, perm, units, n_units, n_split, bias, scratch, n_rows, w, ow, 0, stream);
+    if (rc != RGCN_OK) return rc;
+    const long long n = (long long)n_rows * ow;
+    if (n) hipLaunchKernelGGL(round_bf16_kernel, dim3((unsigned)std::min<long long>((n / 4 + 255) / 256 + 1, 4096)), dim3(256), 0, st, scratch, out, n,
+                              relu ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return RGCN_OK;
+  }
+  if (n_units == 0) return RGCN_OK;
+  const int lpr = ys / 4;
+  const dim3 grid((unsigned)std::min<int64_t>((n_units * lpr + 255) / 256, (int64_t)n_cus() * 64));
+  const int4 *un = reinterpret_cast<const int4 *>(units);
+  const int vec_out = (ow & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
+  if (lpr == 1) hipLaunchKernelGGL((gather_rows_sum4_kernel<1, uint16_t>), grid, dim3(256), 0, st, Y, perm, un, bias, out, (long long)n_units, w, ow, relu ? 1 : 0, vec_out);
+  else if (lpr == 2) hipLaunchKernelGGL((gather_rows_sum4_kernel<2, uint16_t>), grid, dim3(256), 0, st, Y, perm, un, bias, out, (long long)n_units, w, ow, relu ? 1 : 0, vec_out);
+  else hipLaunchKernelGGL((gather_rows_sum4_kernel<4, uint16_t>), grid, dim3(256), 0, st, Y, perm, un, bias, out, (long long)n_units, w, ow, relu ? 1 : 0, vec_out);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+#else
 extern "C" int rgcn_fbasis_tile_bwd_fused_gn(int32_t R, int32_t B, int32_t d, int64_t n_nodes) {
   TileShape s;
   if (!tile_shape(R, B, d, n_nodes, s)) return 0;
@@ -1483,16 +1640,19 @@ extern "C" int rgcn_fbasis_tile_bwd_fused_gn(int32_t R, int32_t B, int32_t d, in
   if (s.kld != 2 || nbt * nkd > 9 || (nbt == 4 && nkd >= 2) || B < 16) return 0;     // (B >= 16: the slot doubles as a 16-row strip)
   return fused_lds(s, R, B, 16) <= (size_t)LDS_MAX ? 16 : 0;      // messages of a node per pass
 }
+#endif
 
-extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, const float *G, int32_t g_stride, float *dbases, float *dcomps,
-                                        const int32_t *rowptr, const int32_t *e_dst, const int32_t *e_rel, const float *e_val,
-                                        int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream) {
+namespace {
+template <typename T>
+int fbasis_tile_bwd(const T *bases, const float *comps, const T *G, int32_t g_stride, T *dbases, float *dcomps, const int32_t *rowptr,
+                    const int32_t *e_dst, const int32_t *e_rel, const float *e_val, int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B,
+                    int32_t d, int32_t mode, void *stream) {
   TileShape s;
   const int gstride = g_stride;
   if (g_stride < d) { rgcn_set_error("fbasis_tile_bwd: row stride of the upstream gradient below its width"); return RGCN_EINVAL; }
   if (!bases || !comps || !G || !rowptr || !e_dst || !e_rel || !e_val || (!dbases && !dcomps) || n_messages < 0 || n_messages > INT32_MAX) { rgcn_set_error("fbasis_tile_bwd: bad argument"); return RGCN_EINVAL; }
   if (n_messages == 0) {                                    // no messages: both gradients are zero
-    if (dbases) HIP_TRY(zero_async(dbases, (size_t)B * n_nodes * d * sizeof(float), (hipStream_t)stream));
+    if (dbases) HIP_TRY(zero_async(dbases, (size_t)B * n_nodes * d * sizeof(T), (hipStream_t)stream));
     if (dcomps) HIP_TRY(zero_async(dcomps, (size_t)R * B * sizeof(float), (hipStream_t)stream));
     return RGCN_OK;
   }
@@ -1500,17 +1660,18 @@ extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, 
   const int abl = rgcn_option_value(RGCN_OPT_BWD_ABL);      // 0 in the shipped library (rgcn_set_option refuses it)
   if (!tile_shape(R, B, d, n_nodes, s) || s.lds_dc > (size_t)LDS_MAX || (mode ? s.lds_db_n : s.lds_db) > (size_t)LDS_MAX || (mode != 0 && mode != 1 && mode != 3)) { rgcn_set_error("fbasis_tile_bwd: shape outside the tile kernels (rgcn_fbasis_tile_supported)"); return RGCN_EUNSUPPORTED; }
   const int n_tiles = (int)((n_nodes + TN - 1) / TN);
-  const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % 16 == 0) && (!dbases || reinterpret_cast<uintptr_t>(dbases) % 16 == 0);
+  const size_t al = 4 * sizeof(T);                          // a piece: 16 (fp32) or 8 (bf16) bytes
+  const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % al == 0) && (!dbases || reinterpret_cast<uintptr_t>(dbases) % al == 0);
   const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cus()));
   hipStream_t st = (hipStream_t)stream;
 #define FBT_BWD3(KERNEL, LDSB, DPB_, KL_, ...)                                                                            \
   {                                                                                                                       \
     if (vec) {                                                                                                            \
-      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, true>, LDSB));                                                                  \
-      hipLaunchKernelGGL((KERNEL<DPB_, KL_, true>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                               \
+      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, true, T>, LDSB));                                                               \
+      hipLaunchKernelGGL((KERNEL<DPB_, KL_, true, T>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                            \
     } else {                                                                                                              \
-      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, false>, LDSB));                                                                 \
-      hipLaunchKernelGGL((KERNEL<DPB_, KL_, false>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                              \
+      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, false, T>, LDSB));                                                              \
+      hipLaunchKernelGGL((KERNEL<DPB_, KL_, false, T>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                           \
     }                                                                                                                     \
   }
 #define FBT_BWD2(KERNEL, LDSB, DPB_, ...) { if (s.kld == 2) FBT_BWD3(KERNEL, LDSB, DPB_, 2, __VA_ARGS__) else FBT_BWD3(KERNEL, LDSB, DPB_, 4, __VA_ARGS__) }
@@ -1524,8 +1685,8 @@ extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, 
     const size_t lds_f = fused_lds(s, R, B, gn_fused);
 #define FBN_F4(NK_, KL_, VE_, NB_)                                                                                                  \
   {                                                                                                                                 \
-    HIP_TRY(raise_lds(fbn_bwd_kernel<NK_, KL_, VE_, NB_>, lds_f));                                                                  \
-    hipLaunchKernelGGL((fbn_bwd_kernel<NK_, KL_, VE_, NB_>), grid, dim3(TW), lds_f, st, bases, comps, G, dbases, dcomps, rowptr, e_dst, e_rel, e_val, \
+    HIP_TRY(raise_lds(fbn_bwd_kernel<NK_, KL_, VE_, NB_, T>, lds_f));                                                               \
+    hipLaunchKernelGGL((fbn_bwd_kernel<NK_, KL_, VE_, NB_, T>), grid, dim3(TW), lds_f, st, bases, comps, G, dbases, dcomps, rowptr, e_dst, e_rel, e_val, \
                        n_tiles, (int)n_nodes, R, B, d, s.ts_f, last, gstride, gn_fused, abl);                                        \
   }
 #define FBN_F3(NK_, KL_, VE_) { if (B <= 16) FBN_F4(NK_, KL_, VE_, 1) else if (B <= 32) FBN_F4(NK_, KL_, VE_, 2) else if (B <= 48) FBN_F4(NK_, KL_, VE_, 3) else FBN_F4(NK_, KL_, VE_, 4) }
@@ -1556,8 +1717,8 @@ extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, 
       const dim3 grid_db((unsigned)std::min<int64_t>(tiles_db, (int64_t)n_cus() * (pair ? 2 : 1)));
 #define FBN_DB3(NK_, KL_, VE_, NP_, NW_)                                                                                          \
   {                                                                                                                               \
-    HIP_TRY(raise_lds(fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_>, lds_db));                                                        \
-    hipLaunchKernelGGL((fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_>), grid_db, dim3(64 * NW_), lds_db, st, comps, G, dbases, rowptr, e_dst, e_rel, \
+    HIP_TRY(raise_lds(fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_, T>, lds_db));                                                     \
+    hipLaunchKernelGGL((fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_, T>), grid_db, dim3(64 * NW_), lds_db, st, comps, G, dbases, rowptr, e_dst, e_rel, \
                        e_val, tiles_db, (int)n_nodes, R, B, d, ts_db, last, gstride, abl);                                                  \
   }
 #define FBN_DB2(NK_, KL_, VE_) { if (pair) FBN_DB3(NK_, KL_, VE_, 2, 8) else if (two) FBN_DB3(NK_, KL_, VE_, 2, 16) else FBN_DB3(NK_, KL_, VE_, 1, 16) }
@@ -1589,3 +1750,18 @@ extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, 
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
+}  // namespace
+
+#ifndef RGCN_FBT_BF16
+extern "C" int rgcn_fbasis_tile_bwd_f32(const float *bases, const float *comps, const float *G, int32_t g_stride, float *dbases, float *dcomps,
+                                        const int32_t *rowptr, const int32_t *e_dst, const int32_t *e_rel, const float *e_val,
+                                        int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream) {
+  return fbasis_tile_bwd(bases, comps, G, g_stride, dbases, dcomps, rowptr, e_dst, e_rel, e_val, n_messages, n_nodes, R, B, d, mode, stream);
+}
+#else
+extern "C" int rgcn_fbasis_tile_bwd_bf16(const uint16_t *bases, const float *comps, const uint16_t *G, int32_t g_stride, uint16_t *dbases,
+                                         float *dcomps, const int32_t *rowptr, const int32_t *e_dst, const int32_t *e_rel, const float *e_val,
+                                         int64_t n_messages, int64_t n_nodes, int32_t R, int32_t B, int32_t d, int32_t mode, void *stream) {
+  return fbasis_tile_bwd(bases, comps, G, g_stride, dbases, dcomps, rowptr, e_dst, e_rel, e_val, n_messages, n_nodes, R, B, d, mode, stream);
+}
+#endif

@@ -935,6 +935,53 @@ def fbasis_tile_bwd(bases, comps, g, plan, need_bases=True, need_comps=True, mod
     return dB, dC
 
 
+def fbasis_tile_fwd_bf16(bases, comps, bias, plan, relu=False, mode=0):
+    """fbasis_tile_fwd for bf16 bases: comps and bias fp32, the per-message scratch Y fp32 -> out [N, d] bf16, the fp32 sum
+    rounded once after the bias and the ReLU.  Rows cut into shared units are summed in an fp32 scratch and rounded in a second launch (the
+    ReLU with them).  relu: (out, True) -- the activation is always applied."""
+    _req(bases, "bases", torch.bfloat16); _req(comps, "comps"); _req(bias, "bias")
+    B, N, d = bases.shape
+    dev = bases.device
+    ys = int(lib().rgcn_fbasis_tile_ystride(c_i32(d)))
+    Y = torch.empty(max(plan.n_messages, 1), ys, device=dev, dtype=torch.float32)
+    out = torch.empty(N, d, device=dev, dtype=torch.bfloat16)
+    units, n_units, n_split = plan.units_dst
+    scratch = torch.empty(N, d, device=dev, dtype=torch.float32) if n_split else None
+    with _on(dev), _timed("fbasis_tile_fwd_bf16"):
+        _check(lib().rgcn_fbasis_tile_fwd_bf16(_dp(bases), _dp(comps), _dp(Y), _dp(plan.rowptr_src), _dp(plan.e_rel), _dp(plan.e_val),
+                                               c_i64(plan.n_messages), c_i64(N), c_i32(comps.shape[0]), c_i32(B), c_i32(d), c_i32(1 if mode else 0),
+                                               _stream(dev)), "fbasis_tile_fwd_bf16")
+    with _on(dev), _timed("gather_rows_sum4_bf16"):
+        _check(lib().rgcn_gather_rows_sum4_bf16(_dp(Y), c_i32(ys), _dp(plan.perm_dst), _dp(units), c_i64(n_units), c_i64(n_split), _dp(bias),
+                                                _dp(out), _dp(scratch), c_i64(N), c_i32(d), c_i32(d), c_i32(1 if relu else 0), _stream(dev)),
+               "gather_rows_sum4_bf16")
+    return (out, True) if relu else out
+
+
+def fbasis_tile_bwd_bf16(bases, comps, g, plan, need_bases=True, need_comps=True, mode=0):
+    """fbasis_tile_bwd for bf16 bases and upstream gradient g [N, d] (rows contiguous, or at a larger row stride: the first columns of
+    zero-padded rows) -> (dbases [B, N, d] bf16, rounded once; dcomps [R, B] fp32)"""
+    _req(bases, "bases", torch.bfloat16); _req(comps, "comps")
+    B, N, d = bases.shape
+    if g.dim() == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1] and g.data_ptr() % 16 == 0 and not g.is_contiguous():
+        g_stride = int(g.stride(0))
+    else:
+        _req(g, "grad", torch.bfloat16)
+        g_stride = d
+    assert g.dtype == torch.bfloat16 and g.shape == (N, d), (g.dtype, g.shape)
+    R = comps.shape[0]
+    dev = bases.device
+    dB = torch.empty_like(bases) if need_bases else None
+    dC = torch.empty(R, B, device=dev, dtype=torch.float32) if need_comps else None
+    if dB is None and dC is None:
+        return None, None
+    with _on(dev), _timed("fbasis_tile_bwd_bf16"):
+        _check(lib().rgcn_fbasis_tile_bwd_bf16(_dp(bases), _dp(comps), _dp(g), c_i32(g_stride), _dp(dB), _dp(dC), _dp(plan.rowptr_src),
+                                               _dp(plan.e_dst), _dp(plan.e_rel), _dp(plan.e_val), c_i64(plan.n_messages), c_i64(N), c_i32(R),
+                                               c_i32(B), c_i32(d), c_i32(mode), _stream(dev)), "fbasis_tile_bwd_bf16")
+    return dB, dC
+
+
 def basis_aggregate(X, comps, csr, B, d, n_b_in):
     _req(X, "features"); _req(comps, "comps")
     out = torch.empty((csr.n_rows, B * d) if n_b_in == 1 else (csr.n_rows, d), device=X.device, dtype=torch.float32)

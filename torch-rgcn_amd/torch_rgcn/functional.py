@@ -928,6 +928,60 @@ def featureless_basis_mp(bases, comps, bias, graph, relu=False):
     return _FeaturelessBasisMP.apply(bases, comps, bias, graph, relu)
 
 
+class _FeaturelessBasisMPBF16(torch.autograd.Function):
+    """featureless_basis_mp on a bf16 bases table, on the tile kernels: the table is staged as bf16 and widened, comps and the
+    bias are fp32 (widened here, once per call, never rounded), out is the fp32 sum rounded to bf16 once (after the bias and the ReLU).
+    Backward: the upstream gradient is gathered as bf16 rows; dbases is bf16 in the parameter's layout (the fp32 / fp64 sum rounded once),
+    dcomps and db are fp32 sums returned in each parameter's dtype."""
+
+    @staticmethod
+    def forward(ctx, bases, comps, bias, graph, relu, mode):
+        ctx.graph, ctx.mode, ctx.relu, ctx.has_bias = graph, mode, bool(relu), bias is not None
+        ctx.c_dtype, ctx.b_dtype = comps.dtype, None if bias is None else bias.dtype
+        bases, c32 = dense(bases), dense(comps.detach().float())
+        b32 = None if bias is None else dense(bias.detach().float())
+        out = _native.fbasis_tile_fwd_bf16(bases, c32, b32, graph.fbasis_plan(), relu=bool(relu), mode=mode)
+        out = out[0] if relu else out
+        ctx.save_for_backward(bases, c32, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        bases, c32, out = ctx.saved_tensors
+        d = bases.shape[2]
+        g = g.to(torch.bfloat16)
+        if ctx.relu:
+            g = torch.ops.aten.threshold_backward(g, out, 0.0)        # a mask: exact in bf16
+        # zero-padded [N, 16 k] rows: 32-byte aligned gathers in the tile kernels (20-byte rows at d = 10 straddle lines), and the width
+        # rgcn_colsum_bf16 wants (a multiple of 4) for the bias
+        g16 = dense(_pad16(g, (d,)))
+        gv = g16[:, :d] if g16.shape[1] != d else g16
+        dB, dC = _native.fbasis_tile_bwd_bf16(bases, c32, gv, ctx.graph.fbasis_plan(), ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                              mode=ctx.mode)
+        db = _native.colsum_bf16(g16)[:d].to(ctx.b_dtype) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        dC = dC.to(ctx.c_dtype) if dC is not None else None
+        return dB, dC, db, None, None, None
+
+
+def featureless_basis_mp_bf16(bases, comps, bias, graph, relu=False):
+    """featureless_basis_mp for a bf16 bases table (comps and bias fp32 or bf16) -> bf16 [N, d].  The tile kernels whenever
+    fbasis_tile_ok offers them, whatever the table's size (rgcn_basis.hip has no bf16 form); otherwise -- shapes the tile kernels refuse,
+    RGCN_DETERMINISTIC=1, fbasis_tile=0, fbasis=csr -- the fp32 route on the widened parameters with its output rounded: CORRECTNESS ONLY,
+    no speed-up (autograd carries the casts)."""
+    if bases.dtype != torch.bfloat16:
+        raise TypeError(f"featureless_basis_mp_bf16: bases must be torch.bfloat16, got {bases.dtype}")
+    if any(t is not None and t.dtype not in (torch.float32, torch.bfloat16) for t in (comps, bias)):
+        raise TypeError("featureless_basis_mp_bf16: comps and bias must be torch.float32 or torch.bfloat16")
+    B, N, d = bases.shape
+    ok, mode = False, 0
+    if _native.fbasis_supported(B, d) and routes.get("fbasis", "src") == "src":
+        ok, mode = _native.fbasis_tile_ok(comps.shape[0], B, d, N, graph.fbasis_plan().max_src_degree)
+    if ok:
+        return _FeaturelessBasisMPBF16.apply(bases, comps, bias, graph, bool(relu), mode)
+    out = featureless_basis_mp(bases.float(), comps.float(), None if bias is None else bias.float(), graph, relu=bool(relu))
+    return out.to(torch.bfloat16)
+
+
 def basis_mp(features, bases, comps, bias, graph):
     return _BasisMP.apply(features, bases, comps, bias, graph)
 

@@ -151,12 +151,21 @@ class _RGCBase(Module):
 
 
 def _check_dtypes(layer, features):
-    """fp32 (the default) or bf16 features (bf16 out, fp32 arithmetic); the parameters fp32, or bf16 with bf16 features only"""
+    """fp32 (the default) or bf16 features (bf16 out, fp32 arithmetic); the parameters fp32, or bf16 with bf16 features only.
+    Featureless: fp32 parameters, or -- basis decomposition only -- bf16 bases (the table decides the storage) with fp32 or bf16 comps / bias"""
     pdt = {p.dtype for p in layer.parameters()}
     if features is None:
-        if pdt - {torch.float32}:
-            raise TypeError(f"featureless layers support torch.float32 parameters only, got {sorted(map(str, pdt))}")
-        return False
+        if not pdt - {torch.float32}:
+            return False
+        if layer.weight_decomp != 'basis' or getattr(layer, "diag_weight_matrix", False) or layer.in_features is not None:
+            raise TypeError(f"featureless layers support torch.float32 parameters only (torch.bfloat16 needs basis decomposition), "
+                            f"got {sorted(map(str, pdt))}")
+        if pdt - {torch.float32, torch.bfloat16}:
+            raise TypeError(f"featureless basis layers take torch.float32 or torch.bfloat16 parameters, got {sorted(map(str, pdt))}")
+        if layer.bases.dtype != torch.bfloat16:
+            raise TypeError("torch.bfloat16 comps / bias need torch.bfloat16 bases (the bases table decides the storage; "
+                            f"got bases {layer.bases.dtype})")
+        return True
     if features.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"features must be torch.float32 or torch.bfloat16 (opt-in, fp32 arithmetic), got {features.dtype}")
     if pdt - {torch.float32, torch.bfloat16}:
@@ -265,6 +274,8 @@ class RelationalGraphConvolutionNC(_RGCBase):
         assert (features is None) == (self.in_features is None), "in_features not provided!"
         assert activation in (None, "relu"), f"unknown activation {activation!r}"
         if _check_dtypes(self, features):
+            if features is None:
+                return self._forward_featureless_bf16(activation, private)
             return self._forward_bf16(features, activation, private)
         any_param = self.weights if (self.diag_weight_matrix or self.weight_decomp is None) else \
             (self.bases if self.weight_decomp == 'basis' else self.blocks)
@@ -369,6 +380,42 @@ class RelationalGraphConvolutionNC(_RGCBase):
         output = F_.relational_mp_bf16(features, weights, _f32(self.bias), graph, relu=relu, group=group, n_slabs=slabs, comm=comm)
         assert output.size() == (N, out_dim)
         return output.index_select(0, graph.perm) if graph.perm is not None else output
+
+    def _forward_featureless_bf16(self, activation, private):
+        """featureless layer with basis decomposition and bf16 bases: the tile kernels on the bf16 table
+        (F_.featureless_basis_mp_bf16); relation-sharded layers, host-built graphs and basis_path=0 run the fp32 route on the widened
+        parameters and round the output once"""
+        N, R, out_dim = self.num_nodes, self.num_relations, self.out_features
+        _require_gpu(self.bases, "RelationalGraphConvolutionNC parameters")
+        assert self.bases.size() == (self.num_bases, N, out_dim) and self.comps.size() == (R, self.num_bases)
+        graph = self._graph_on(self.bases.device)
+        if graph.perm is not None:
+            raise NotImplementedError("RGCN_RELABEL with a featureless layer (the R x N x d weight table is indexed by node id)")
+        if self.vertical_stacking:
+            raise RuntimeError("featureless message passing needs horizontal stacking "
+                               f"(mat1 and mat2 shapes cannot be multiplied: {R * N}x{N} and {R * N}x{out_dim})")
+        relu = activation == "relu"
+        group = getattr(self, "_shard_group", None)
+        fl_basis = getattr(graph, "_dev", None) is not None and routes.get("basis_path") != "0"
+        if group is None and fl_basis:
+            return F_.featureless_basis_mp_bf16(self.bases, self.comps, self.bias, graph, relu=relu)
+        # upcast: the fp32 routes of _forward_impl on the widened parameters, one rounding at the end
+        bases, comps, bias = self.bases.float(), self.comps.float(), _f32(self.bias)
+        if fl_basis:
+            local = lambda: F_.featureless_basis_mp(bases, comps, None, graph)
+        else:
+            W = F_.matmul_mfma(comps, bases.reshape(self.num_bases, -1)).view(R, N, out_dim)
+            local = lambda: F_.featureless_mp(W, None, graph)
+        if group is None:
+            output = local()
+        else:
+            from .dist import sharded_apply
+            output = sharded_apply(lambda _x: local(), None, group)
+        if bias is not None:
+            output = output + bias
+        output = torch.relu(output) if relu else output
+        assert output.size() == (N, out_dim)
+        return output.to(torch.bfloat16)
 
 
 class RelationalGraphConvolutionLP(_RGCBase):
