@@ -428,7 +428,8 @@ RGCN_API int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, const 
  *                     second launch -- never bf16 atomics.  flags: RGCN_F_RELU (not with hub pieces).  The feature gradient is the same call
  *                     on the transposed plan with the transposed weights.
  *   rgcn_wgrad_bf16   dW [R][d_in][d_out] (fp32, zeroed first) += val X[src]^T G[dst] on the relation-major plan, as rgcn_wgrad_f32.
- *   rgcn_colsum_bf16  db [d] = column sums of G [n][d] (fp32; d a multiple of 4, at most 256); scratch as rgcn_colsum_f32. */
+ *   rgcn_colsum_bf16  db [d] = column sums of G [n][d] (fp32; any width: 8-byte loads when d is a multiple of 4, else 2-byte elements;
+ *                     wide rows loop over column blocks); scratch as rgcn_colsum_f32. */
 RGCN_API int rgcn_spmm_bf16(const uint16_t *X, const float *W_packed, const float *bias, uint16_t *out, float *scratch,
                             const int32_t *p_pack, const int32_t *chunk_rel, const int32_t *units, int64_t n_units, int64_t n_split,
                             int32_t tile_rows, int64_t n_dst, int64_t n_src, int32_t d_in, int32_t d_out, int32_t flags, void *stream);
@@ -436,6 +437,33 @@ RGCN_API int rgcn_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dW, co
                              const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items, int32_t R,
                              int32_t d_in, int32_t d_out, void *stream);
 RGCN_API int rgcn_colsum_bf16(const uint16_t *G, float *db, float *scratch, int64_t n, int32_t d, void *stream);
+/* bf16 storage for the two structured decompositions (layers.py:243-244 / :289-292 for a layer called with bf16 features):
+ * the storage twins of rgcn_block_spmm_f32 / rgcn_block_wgrad_f32 / rgcn_diag_spmm_f32 / rgcn_diag_wgrad_f32 -- same arguments, checks and
+ * error codes (blocks above 8 x 8: RGCN_EUNSUPPORTED), same arithmetic in the same order.  X / G, out are bf16 (uint16_t bit patterns);
+ * blocks, w, bias, dblocks and dw fp32; every product and sum fp32.  Nothing of size R x d x d exists.
+ *   rgcn_block_spmm_bf16 / rgcn_diag_spmm_bf16
+ *       out != NULL: the rows of units that are not shared are rounded once (nearest even, NaN stays NaN) and written to out; the pieces of
+ *                    hub rows (n_split > 0) add fp32 values into `scratch` ([n_rows][width] floats, zeroed here; may be NULL when
+ *                    n_split = 0) and a second launch rounds those rows into out -- never bf16 atomics.  RGCN_F_RELU not with hub pieces.
+ *       out == NULL: the fp32 output mode -- bf16 gathers, the unrounded fp32 sums are left in `scratch` (required), for a caller that adds
+ *                    a further term before the one rounding (the LP layer's dense self-loop relation).
+ *       out == NULL and scratch == NULL: RGCN_EINVAL.
+ *   rgcn_block_wgrad_bf16 / rgcn_diag_wgrad_bf16: X and G gathered as bf16, the gradient summed in fp32 (zeroed first) as in the twins.
+ * A segment of a row is loaded 8 bytes (four features) at a time where it is 8-byte aligned (4 x 4 and 8 x 8 blocks; diagonal widths that
+ * are multiples of 4), else as 2-byte elements. */
+RGCN_API int rgcn_block_spmm_bf16(const uint16_t *X, const float *blocks, const float *bias, uint16_t *out, float *scratch,
+                                  const int32_t *units, const int32_t *rowptr, int64_t n_units, int64_t n_split, const int32_t *e_src,
+                                  const int32_t *e_rel, const float *e_val, int64_t n_rows, int32_t n_rel_blocks, int32_t nb, int32_t bi,
+                                  int32_t bo, int32_t flags, void *stream);
+RGCN_API int rgcn_block_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dblocks, const int32_t *p_src, const int32_t *p_dst,
+                                   const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items,
+                                   int32_t n_rel_blocks, int32_t nb, int32_t bi, int32_t bo, void *stream);
+RGCN_API int rgcn_diag_spmm_bf16(const uint16_t *X, const float *w, const float *bias, uint16_t *out, float *scratch,
+                                 const int32_t *rowptr_units, int64_t n_units, int64_t n_split, const int32_t *e_src, const int32_t *e_rel,
+                                 const float *e_val, int64_t n_rows, int32_t R, int32_t d, void *stream);
+RGCN_API int rgcn_diag_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dw, const int32_t *p_src, const int32_t *p_dst,
+                                  const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items, int32_t R, int32_t d,
+                                  void *stream);
 /* The same for graphs whose (tile, relation) buckets are sparse (AM: 267 relations), on the RELATION-major plan of the
  * two-pass path: one wave per work item gathers G[p_src] and X[p_dst] once per message and produces
  *   Y[slot, :] = val G[p_src] W_r^T   (slot order; pass 2 = rgcn_segment_gather_sum_f32 sums them per destination -> dX)

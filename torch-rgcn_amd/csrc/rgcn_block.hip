@@ -29,12 +29,16 @@ constexpr int MAXB = 8;      // runtime-sized blocks up to 8 x 8 (larger blocks:
 // BI_ x BO_ = the block as stored ([bi][bo] row-major); TR: multiply by the transposed block (input width bo, output bi).
 // BI_ = 0: sizes at run time (bi, bo <= MAXB).
 // one work unit (a row, or a piece of a hub row) on `lr` lanes; W = the block table in global memory or in LDS
-template <int BI_, int BO_, bool TR>
+// BF (rgcn_block_spmm_bf16): X holds bf16 rows -- a segment is one 8-byte load per four features where it is 8-byte aligned
+// (the fixed 4 x 4 and 8 x 8 forms), 2-byte elements otherwise (a 5-wide segment starts on a 10-byte boundary) -- widened to fp32; rows
+// of units that are not shared are rounded once and written to out16 when it is given, the pieces of hub rows always add fp32 values to
+// `out` (the launcher's fp32 scratch).  BF = false: the fp32 kernel as it was.
+template <int BI_, int BO_, bool TR, bool BF = false>
 __device__ __forceinline__ void block_unit(
     const float *__restrict__ X, const float *W, const float *__restrict__ bias, float *__restrict__ out,
     const int4 *__restrict__ units, const int *__restrict__ rowptr, long long u, long long n_units,
     const int *__restrict__ e_src, const int *__restrict__ e_rel, const float *__restrict__ e_val, int nb, int bi_rt, int bo_rt,
-    int n_rel_blocks, int lpm, int lr, int relu, int rel_stride) {
+    int n_rel_blocks, int lpm, int lr, int relu, int rel_stride, uint16_t *__restrict__ out16 = nullptr) {
   constexpr bool FIXED = BI_ > 0;
   constexpr int CAP_IN = FIXED ? (TR ? BO_ : BI_) : MAXB, CAP_OUT = FIXED ? (TR ? BI_ : BO_) : MAXB;
   const int bi = FIXED ? BI_ : bi_rt, bo = FIXED ? BO_ : bo_rt;
@@ -67,7 +71,19 @@ __device__ __forceinline__ void block_unit(
         const float *xr = X + (size_t)e_src[ee] * d_in + (size_t)b * n_in;
         const float *wr = W + (size_t)(rel < n_rel_blocks ? rel : 0) * rel_stride + (size_t)b * (bi * bo);
         float x[CAP_IN], w[FIXED ? BI_ * BO_ : MAXB * MAXB];
-        if (vec_in) {
+        if constexpr (BF) {
+          const uint16_t *xh = reinterpret_cast<const uint16_t *>(X) + (size_t)e_src[ee] * d_in + (size_t)b * n_in;
+          if (vec_in) {
+#pragma unroll
+            for (int i = 0; i < CAP_IN / 4; ++i) {
+              const float4 t = bf16x4_widen(reinterpret_cast<const uint2 *>(xh)[i]);
+              x[4 * i] = t.x * v; x[4 * i + 1] = t.y * v; x[4 * i + 2] = t.z * v; x[4 * i + 3] = t.w * v;
+            }
+          } else {
+#pragma unroll
+            for (int i = 0; i < CAP_IN; ++i) x[i] = (FIXED || i < n_in) ? bf16_widen(xh[i]) * v : 0.f;
+          }
+        } else if (vec_in) {
 #pragma unroll
           for (int i = 0; i < CAP_IN / 4; ++i) {
             const f32x4 t = reinterpret_cast<const f32x4 *>(xr)[i];
@@ -111,7 +127,24 @@ __device__ __forceinline__ void block_unit(
 #pragma unroll
       for (int o = 0; o < CAP_OUT; ++o) acc[o] += __shfl_xor(acc[o], s, 64);
     }
-    if (on && g == 0 && b < nb) {
+    if (BF && on && g == 0 && b < nb && !shared && out16) {      // bf16 row of a unit that owns it: one rounding
+      uint16_t *orow = out16 + (size_t)unit.x * d_out + (size_t)b * n_out;
+      float r[CAP_OUT];
+#pragma unroll
+      for (int o = 0; o < CAP_OUT; ++o) {
+        r[o] = (FIXED || o < n_out) ? acc[o] + (add_bias ? bias[(size_t)b * n_out + o] : 0.f) : 0.f;
+        if (relu) r[o] = fmaxf(r[o], 0.f);
+      }
+      if (FIXED && CAP_OUT % 4 == 0) {
+#pragma unroll
+        for (int o = 0; o < CAP_OUT / 4; ++o)
+          reinterpret_cast<uint2 *>(orow)[o] = bf16x4_round(make_float4(r[4 * o], r[4 * o + 1], r[4 * o + 2], r[4 * o + 3]));
+      } else {
+#pragma unroll
+        for (int o = 0; o < CAP_OUT; ++o)
+          if (FIXED || o < n_out) orow[o] = bf16_round(r[o]);
+      }
+    } else if (on && g == 0 && b < nb) {
       float *orow = out + (size_t)unit.x * d_out + (size_t)b * n_out;
 #pragma unroll
       for (int o = 0; o < CAP_OUT; ++o)
@@ -128,14 +161,23 @@ __device__ __forceinline__ void block_unit(
   }
 }
 
-template <int BI_, int BO_, bool TR>
+// O16: empty -- the fp32 kernel, its arguments as they were -- or one `uint16_t *` (the bf16 kernel: X holds bf16 rows; the pointer is the
+// bf16 output, NULL = every row stays fp32 in `out`)
+template <typename... O16>
+__device__ __forceinline__ uint16_t *first_or_null(O16... p) {
+  if constexpr (sizeof...(O16) == 0) return nullptr;
+  else return (p, ...);
+}
+
+template <int BI_, int BO_, bool TR, typename... O16>
 __global__ __launch_bounds__(WG) void block_csr_kernel(
     const float *__restrict__ X, const float *__restrict__ W, const float *__restrict__ bias, float *__restrict__ out,
     const int4 *__restrict__ units, const int *__restrict__ rowptr, long long n_units, const int *__restrict__ e_src,
     const int *__restrict__ e_rel, const float *__restrict__ e_val, int nb, int bi_rt, int bo_rt, int n_rel_blocks, int lpm,
-    int lr, int relu) {
-  block_unit<BI_, BO_, TR>(X, W, bias, out, units, rowptr, ((long long)blockIdx.x * WG + threadIdx.x) / lr, n_units, e_src, e_rel,
-                           e_val, nb, bi_rt, bo_rt, n_rel_blocks, lpm, lr, relu, nb * (BI_ > 0 ? BI_ * BO_ : bi_rt * bo_rt));
+    int lr, int relu, O16... out16) {
+  block_unit<BI_, BO_, TR, sizeof...(O16) != 0>(X, W, bias, out, units, rowptr, ((long long)blockIdx.x * WG + threadIdx.x) / lr, n_units,
+                                                e_src, e_rel, e_val, nb, bi_rt, bo_rt, n_rel_blocks, lpm, lr, relu,
+                                                nb * (BI_ > 0 ? BI_ * BO_ : bi_rt * bo_rt), first_or_null(out16...));
 }
 
 // The same with the WHOLE block table resident in LDS (tables up to LDS_TABLE_BYTES: AM at width 16 is 267 x 4 x 16 floats =
@@ -144,12 +186,12 @@ __global__ __launch_bounds__(WG) void block_csr_kernel(
 constexpr int BIG_WG = 1024;
 constexpr size_t LDS_TABLE_BYTES = 76 * 1024;
 
-template <int BI_, int BO_, bool TR>
+template <int BI_, int BO_, bool TR, typename... O16>
 __global__ __launch_bounds__(BIG_WG) void block_csr_lds_kernel(
     const float *__restrict__ X, const float *__restrict__ W, const float *__restrict__ bias, float *__restrict__ out,
     const int4 *__restrict__ units, const int *__restrict__ rowptr, long long n_units, const int *__restrict__ e_src,
     const int *__restrict__ e_rel, const float *__restrict__ e_val, int nb, int bi_rt, int bo_rt, int n_rel_blocks, int lpm,
-    int lr, int relu, int table_floats) {
+    int lr, int relu, int table_floats, O16... out16) {
   extern __shared__ __attribute__((aligned(16))) float wt[];
   // a relation's blocks are padded by 4 floats: unpadded, every relation starts on bank 0 (nb x 16 floats = a multiple of the
   // 64 banks at nb = 4) and the 16 messages of a ds_read_b128 collide 16 ways
@@ -158,8 +200,8 @@ __global__ __launch_bounds__(BIG_WG) void block_csr_lds_kernel(
   __syncthreads();
   const int upw = BIG_WG / lr;
   for (long long base = (long long)blockIdx.x * upw; base < n_units; base += (long long)gridDim.x * upw)
-    block_unit<BI_, BO_, TR>(X, wt, bias, out, units, rowptr, base + threadIdx.x / lr, n_units, e_src, e_rel, e_val, nb, bi_rt,
-                             bo_rt, n_rel_blocks, lpm, lr, relu, rel_stride);
+    block_unit<BI_, BO_, TR, sizeof...(O16) != 0>(X, wt, bias, out, units, rowptr, base + threadIdx.x / lr, n_units, e_src, e_rel, e_val,
+                                                  nb, bi_rt, bo_rt, n_rel_blocks, lpm, lr, relu, rel_stride, first_or_null(out16...));
 }
 
 // The common case by hand: 4 blocks of 4 x 4 (width 16), block table in LDS, work units given.  Same arithmetic as
@@ -327,7 +369,9 @@ __global__ __launch_bounds__(BIG_WG) void spmm_csr_d16_kernel(
 }
 
 // One wave per work item (a chunk range of ONE relation in the relation-major plan; pads carry val = 0).
-template <int BI_, int BO_>
+// BF (rgcn_block_wgrad_bf16): X and G hold bf16 rows (8-byte loads where a segment is 8-byte aligned, else 2-byte elements; widened);
+// dW stays fp32.  BF = false: the fp32 kernel as it was.
+template <int BI_, int BO_, bool BF = false>
 __global__ __launch_bounds__(WG) void block_wgrad_kernel(
     const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ dW, const int *__restrict__ p_src,
     const int *__restrict__ p_dst, const float *__restrict__ p_val, const int *__restrict__ chunk_rel,
@@ -360,6 +404,31 @@ __global__ __launch_bounds__(WG) void block_wgrad_kernel(
         const float v = have ? p_val[ss] : 0.f;
         const float *xr = X + (size_t)p_src[ss] * d_in + (size_t)b * bi;
         const float *gr = G + (size_t)max(p_dst[ss], 0) * d_out + (size_t)b * bo;
+        if constexpr (BF) {
+          const uint16_t *xh = reinterpret_cast<const uint16_t *>(X) + (size_t)p_src[ss] * d_in + (size_t)b * bi;
+          const uint16_t *gh = reinterpret_cast<const uint16_t *>(G) + (size_t)max(p_dst[ss], 0) * d_out + (size_t)b * bo;
+          if (vec_i) {
+#pragma unroll
+            for (int i = 0; i < CAP_I / 4; ++i) {
+              const float4 t = bf16x4_widen(reinterpret_cast<const uint2 *>(xh)[i]);
+              x[4 * i] = t.x * v; x[4 * i + 1] = t.y * v; x[4 * i + 2] = t.z * v; x[4 * i + 3] = t.w * v;
+            }
+          } else {
+#pragma unroll
+            for (int i = 0; i < CAP_I; ++i) x[i] = (FIXED || i < bi) ? bf16_widen(xh[i]) * v : 0.f;
+          }
+          if (vec_o) {
+#pragma unroll
+            for (int o = 0; o < CAP_O / 4; ++o) {
+              const float4 t = bf16x4_widen(reinterpret_cast<const uint2 *>(gh)[o]);
+              gg[4 * o] = t.x; gg[4 * o + 1] = t.y; gg[4 * o + 2] = t.z; gg[4 * o + 3] = t.w;
+            }
+          } else {
+#pragma unroll
+            for (int o = 0; o < CAP_O; ++o) gg[o] = (FIXED || o < bo) ? bf16_widen(gh[o]) : 0.f;
+          }
+          return;
+        }
         if (vec_i) {
 #pragma unroll
           for (int i = 0; i < CAP_I / 4; ++i) {
@@ -418,6 +487,89 @@ int lanes_per_message(int nb) {
 
 extern "C" int rgcn_block_supported(int32_t bi, int32_t bo) { return bi >= 1 && bo >= 1 && bi <= MAXB && bo <= MAXB; }
 
+namespace {
+
+// the launches behind rgcn_block_spmm_f32 (BF = false: out16 unused) and rgcn_block_spmm_bf16 (BF: X holds bf16 rows; `out` = the fp32
+// destination -- the scratch of the hub pieces, or every row in the fp32 output mode -- and out16 the bf16 rows, or NULL)
+template <bool BF>
+int block_spmm_launch(const float *X, const float *blocks, const float *bias, float *out, uint16_t *out16, const int32_t *units,
+                      const int32_t *rowptr, int64_t n_units, int64_t n_split, const int32_t *e_src, const int32_t *e_rel,
+                      const float *e_val, int64_t n_rows, int32_t n_rel_blocks, int32_t nb, int32_t bi, int32_t bo, bool tr, bool relu,
+                      hipStream_t st) {
+  const int n_out = tr ? bi : bo;
+  if (n_split) HIP_TRY(zero_async(out, (size_t)n_rows * nb * n_out * sizeof(float), st));
+  const int lpm = lanes_per_message(nb);
+  const int lr = std::min(64, std::max(16, 2 * lpm));
+  const int upw = WG / lr;
+  const dim3 grid((unsigned)((n_units + upw - 1) / upw)), block(WG);
+  const int4 *un = reinterpret_cast<const int4 *>(units);
+  // table in LDS: worth it when the graph is large enough to amortise 512 table loads (and the table fits)
+  const size_t table_bytes = (size_t)n_rel_blocks * nb * bi * bo * sizeof(float);
+  const size_t lds_bytes = table_bytes + (size_t)n_rel_blocks * 4 * sizeof(float);          // + the per-relation pad
+  if (bi == 4 && bo == 4 && lds_bytes <= LDS_TABLE_BYTES && n_units >= 64 * 1024) {
+    const dim3 pgrid((unsigned)std::min<int64_t>(512, (n_units * lr + BIG_WG - 1) / BIG_WG));
+    auto launch = [&](auto kern, bool &raised, auto... o16) -> hipError_t {
+      if (lds_bytes > 64 * 1024 && !raised) {     // once per process and kernel (not a stream operation: keep it out of captures)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)LDS_TABLE_BYTES);
+        if (e != hipSuccess) return e;
+        raised = true;
+      }
+      hipLaunchKernelGGL(kern, pgrid, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, rowptr, (long long)n_units, e_src,
+                         e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu, (int)(table_bytes / sizeof(float)), o16...);
+      return hipGetLastError();
+    };
+    static bool raised_t = false, raised_n = false, raised_pt = false, raised_pn = false;
+    if constexpr (BF) {           // (width 16 too: block44_csr_kernel has no bf16 form)
+      (void)raised_pt; (void)raised_pn;
+      if (tr) HIP_TRY(launch(block_csr_lds_kernel<4, 4, true, uint16_t *>, raised_t, out16));
+      else HIP_TRY(launch(block_csr_lds_kernel<4, 4, false, uint16_t *>, raised_n, out16));
+    } else {
+      if (nb == 4 && un) {          // width 16: the software-pipelined form
+        const dim3 pg((unsigned)std::min<int64_t>(512, (n_units + BIG_WG / 16 - 1) / (BIG_WG / 16)));
+        auto launch_p = [&](auto kern, bool &raised) -> hipError_t {
+          if (lds_bytes > 64 * 1024 && !raised) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TABLE_BYTES);
+            if (e != hipSuccess) return e;
+            raised = true;
+          }
+          hipLaunchKernelGGL(kern, pg, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, (long long)n_units, e_src, e_rel, e_val,
+                             n_rel_blocks, (int)relu, (int)(table_bytes / sizeof(float)));
+          return hipGetLastError();
+        };
+        if (tr) HIP_TRY(launch_p(block44_csr_kernel<true>, raised_pt));
+        else HIP_TRY(launch_p(block44_csr_kernel<false>, raised_pn));
+        return RGCN_OK;
+      }
+      if (tr) HIP_TRY(launch(block_csr_lds_kernel<4, 4, true>, raised_t));
+      else HIP_TRY(launch(block_csr_lds_kernel<4, 4, false>, raised_n));
+    }
+    return RGCN_OK;
+  }
+#define RGCN_BLOCK_ARGS X, blocks, bias, out, un, rowptr, (long long)n_units, e_src, e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu
+#define RGCN_BLOCK_LAUNCH(BI, BO)                                                                                              \
+  do {                                                                                                                         \
+    if constexpr (BF) {                                                                                                        \
+      if (tr) hipLaunchKernelGGL((block_csr_kernel<BI, BO, true, uint16_t *>), grid, block, 0, st, RGCN_BLOCK_ARGS, out16);    \
+      else hipLaunchKernelGGL((block_csr_kernel<BI, BO, false, uint16_t *>), grid, block, 0, st, RGCN_BLOCK_ARGS, out16);      \
+    } else {                                                                                                                   \
+      if (tr) hipLaunchKernelGGL((block_csr_kernel<BI, BO, true>), grid, block, 0, st, RGCN_BLOCK_ARGS);                       \
+      else hipLaunchKernelGGL((block_csr_kernel<BI, BO, false>), grid, block, 0, st, RGCN_BLOCK_ARGS);                         \
+    }                                                                                                                          \
+  } while (0)
+  if (bi == 4 && bo == 4) RGCN_BLOCK_LAUNCH(4, 4);
+  else if (bi == 5 && bo == 5) RGCN_BLOCK_LAUNCH(5, 5);
+  else if (bi == 8 && bo == 8) RGCN_BLOCK_LAUNCH(8, 8);
+  else if (bi == 2 && bo == 2) RGCN_BLOCK_LAUNCH(2, 2);
+  else RGCN_BLOCK_LAUNCH(0, 0);
+#undef RGCN_BLOCK_LAUNCH
+#undef RGCN_BLOCK_ARGS
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
+
 extern "C" int rgcn_block_spmm_f32(const float *X, const float *blocks, const float *bias, float *out, const int32_t *units,
                                    const int32_t *rowptr, int64_t n_units, int64_t n_split, const int32_t *e_src,
                                    const int32_t *e_rel, const float *e_val, int64_t n_rows, int32_t n_rel_blocks, int32_t nb,
@@ -435,65 +587,36 @@ extern "C" int rgcn_block_spmm_f32(const float *X, const float *blocks, const fl
   const bool tr = flags & RGCN_F_TRANSPOSE_W, relu = flags & RGCN_F_RELU;
   if (relu && n_split) { rgcn_set_error("block_spmm: RGCN_F_RELU with shared units"); return RGCN_EINVAL; }
   if (n_rows == 0 || n_units == 0) return RGCN_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int n_out = tr ? bi : bo;
-  if (n_split) HIP_TRY(zero_async(out, (size_t)n_rows * nb * n_out * sizeof(float), st));
-  const int lpm = lanes_per_message(nb);
-  const int lr = std::min(64, std::max(16, 2 * lpm));
-  const int upw = WG / lr;
-  const dim3 grid((unsigned)((n_units + upw - 1) / upw)), block(WG);
-  const int4 *un = reinterpret_cast<const int4 *>(units);
-  // table in LDS: worth it when the graph is large enough to amortise 512 table loads (and the table fits)
-  const size_t table_bytes = (size_t)n_rel_blocks * nb * bi * bo * sizeof(float);
-  const size_t lds_bytes = table_bytes + (size_t)n_rel_blocks * 4 * sizeof(float);          // + the per-relation pad
-  if (bi == 4 && bo == 4 && lds_bytes <= LDS_TABLE_BYTES && n_units >= 64 * 1024) {
-    const dim3 pgrid((unsigned)std::min<int64_t>(512, (n_units * lr + BIG_WG - 1) / BIG_WG));
-    auto launch = [&](auto kern, bool &raised) -> hipError_t {
-      if (lds_bytes > 64 * 1024 && !raised) {     // once per process and kernel (not a stream operation: keep it out of captures)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)LDS_TABLE_BYTES);
-        if (e != hipSuccess) return e;
-        raised = true;
-      }
-      hipLaunchKernelGGL(kern, pgrid, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, rowptr, (long long)n_units, e_src,
-                         e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu, (int)(table_bytes / sizeof(float)));
-      return hipGetLastError();
-    };
-    static bool raised_t = false, raised_n = false, raised_pt = false, raised_pn = false;
-    if (nb == 4 && un) {          // width 16: the software-pipelined form
-      const dim3 pg((unsigned)std::min<int64_t>(512, (n_units + BIG_WG / 16 - 1) / (BIG_WG / 16)));
-      auto launch_p = [&](auto kern, bool &raised) -> hipError_t {
-        if (lds_bytes > 64 * 1024 && !raised) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TABLE_BYTES);
-          if (e != hipSuccess) return e;
-          raised = true;
-        }
-        hipLaunchKernelGGL(kern, pg, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, (long long)n_units, e_src, e_rel, e_val,
-                           n_rel_blocks, (int)relu, (int)(table_bytes / sizeof(float)));
-        return hipGetLastError();
-      };
-      if (tr) HIP_TRY(launch_p(block44_csr_kernel<true>, raised_pt));
-      else HIP_TRY(launch_p(block44_csr_kernel<false>, raised_pn));
-      return RGCN_OK;
-    }
-    if (tr) HIP_TRY(launch(block_csr_lds_kernel<4, 4, true>, raised_t));
-    else HIP_TRY(launch(block_csr_lds_kernel<4, 4, false>, raised_n));
-    return RGCN_OK;
+  return block_spmm_launch<false>(X, blocks, bias, out, nullptr, units, rowptr, n_units, n_split, e_src, e_rel, e_val, n_rows,
+                                  n_rel_blocks, nb, bi, bo, tr, relu, (hipStream_t)stream);
+}
+
+extern "C" int rgcn_block_spmm_bf16(const uint16_t *X, const float *blocks, const float *bias, uint16_t *out, float *scratch,
+                                    const int32_t *units, const int32_t *rowptr, int64_t n_units, int64_t n_split,
+                                    const int32_t *e_src, const int32_t *e_rel, const float *e_val, int64_t n_rows,
+                                    int32_t n_rel_blocks, int32_t nb, int32_t bi, int32_t bo, int32_t flags, void *stream) {
+  if (!X || !blocks || (!out && !scratch) || (n_split && !scratch) || n_rows < 0 || n_units < 0 || n_split < 0 || nb <= 0 ||
+      n_rel_blocks < 0 || (!units && !rowptr) || (n_split && !units) || (n_units && (!e_src || !e_rel || !e_val))) {
+    rgcn_set_error("block_spmm_bf16: bad argument (out or the fp32 scratch; hub pieces need the scratch)");
+    return RGCN_EINVAL;
   }
-#define RGCN_BLOCK_LAUNCH(BI, BO)                                                                                              \
-  do {                                                                                                                         \
-    if (tr) hipLaunchKernelGGL((block_csr_kernel<BI, BO, true>), grid, block, 0, st, X, blocks, bias, out, un, rowptr,         \
-                               (long long)n_units, e_src, e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu);         \
-    else hipLaunchKernelGGL((block_csr_kernel<BI, BO, false>), grid, block, 0, st, X, blocks, bias, out, un, rowptr,           \
-                            (long long)n_units, e_src, e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu);            \
-  } while (0)
-  if (bi == 4 && bo == 4) RGCN_BLOCK_LAUNCH(4, 4);
-  else if (bi == 5 && bo == 5) RGCN_BLOCK_LAUNCH(5, 5);
-  else if (bi == 8 && bo == 8) RGCN_BLOCK_LAUNCH(8, 8);
-  else if (bi == 2 && bo == 2) RGCN_BLOCK_LAUNCH(2, 2);
-  else RGCN_BLOCK_LAUNCH(0, 0);
-#undef RGCN_BLOCK_LAUNCH
-  HIP_TRY(hipGetLastError());
+  if (!rgcn_block_supported(bi, bo)) {
+    rgcn_set_error("block_spmm_bf16: blocks of %d x %d (limit %d x %d)", bi, bo, MAXB, MAXB);
+    return RGCN_EUNSUPPORTED;
+  }
+  if (!units && n_units != n_rows) { rgcn_set_error("block_spmm_bf16: without units, one unit per row"); return RGCN_EINVAL; }
+  const bool tr = flags & RGCN_F_TRANSPOSE_W, relu = flags & RGCN_F_RELU;
+  if (relu && n_split) { rgcn_set_error("block_spmm_bf16: RGCN_F_RELU with shared units"); return RGCN_EINVAL; }
+  if (n_rows == 0 || n_units == 0) return RGCN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = block_spmm_launch<true>(reinterpret_cast<const float *>(X), blocks, bias, scratch, out, units, rowptr, n_units, n_split,
+                                         e_src, e_rel, e_val, n_rows, n_rel_blocks, nb, bi, bo, tr, relu, st);
+  if (rc != RGCN_OK) return rc;
+  if (n_split && out) {           // the hub rows: fp32 sums of their pieces in the scratch -> bf16, one rounding
+    hipLaunchKernelGGL(round_shared_rows_bf16_kernel<16>, dim3((unsigned)((n_units * 16 + WG - 1) / WG)), dim3(WG), 0, st, scratch, out,
+                       reinterpret_cast<const int4 *>(units), (long long)n_units, nb * (tr ? bi : bo));
+    HIP_TRY(hipGetLastError());
+  }
   return RGCN_OK;
 }
 
@@ -525,6 +648,32 @@ extern "C" int rgcn_spmm_csr_d16_f32(const float *X, const float *W, const float
   return RGCN_OK;
 }
 
+namespace {
+
+template <bool BF>
+int block_wgrad_launch(const float *X, const float *G, float *dblocks, const int32_t *p_src, const int32_t *p_dst, const float *p_val,
+                       const int32_t *chunk_rel, const int32_t *items, int64_t n_items, int32_t n_rel_blocks, int32_t nb, int32_t bi,
+                       int32_t bo, hipStream_t st) {
+  if (n_rel_blocks) HIP_TRY(zero_async(dblocks, (size_t)n_rel_blocks * nb * bi * bo * sizeof(float), st));
+  if (n_items == 0 || n_rel_blocks == 0) return RGCN_OK;
+  const int lpm = lanes_per_message(nb);
+  const dim3 grid((unsigned)((n_items + WG / 64 - 1) / (WG / 64))), block(WG);
+  const int2 *its = reinterpret_cast<const int2 *>(items);
+#define RGCN_BLOCK_LAUNCH(BI, BO)                                                                                              \
+  hipLaunchKernelGGL((block_wgrad_kernel<BI, BO, BF>), grid, block, 0, st, X, G, dblocks, p_src, p_dst, p_val, chunk_rel, its, \
+                     (long long)n_items, nb, bi, bo, n_rel_blocks, lpm)
+  if (bi == 4 && bo == 4) RGCN_BLOCK_LAUNCH(4, 4);
+  else if (bi == 5 && bo == 5) RGCN_BLOCK_LAUNCH(5, 5);
+  else if (bi == 8 && bo == 8) RGCN_BLOCK_LAUNCH(8, 8);
+  else if (bi == 2 && bo == 2) RGCN_BLOCK_LAUNCH(2, 2);
+  else RGCN_BLOCK_LAUNCH(0, 0);
+#undef RGCN_BLOCK_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
+
 extern "C" int rgcn_block_wgrad_f32(const float *X, const float *G, float *dblocks, const int32_t *p_src, const int32_t *p_dst,
                                     const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items,
                                     int32_t n_rel_blocks, int32_t nb, int32_t bi, int32_t bo, void *stream) {
@@ -537,21 +686,22 @@ extern "C" int rgcn_block_wgrad_f32(const float *X, const float *G, float *dbloc
     rgcn_set_error("block_wgrad: blocks of %d x %d (limit %d x %d)", bi, bo, MAXB, MAXB);
     return RGCN_EUNSUPPORTED;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (n_rel_blocks) HIP_TRY(zero_async(dblocks, (size_t)n_rel_blocks * nb * bi * bo * sizeof(float), st));
-  if (n_items == 0 || n_rel_blocks == 0) return RGCN_OK;
-  const int lpm = lanes_per_message(nb);
-  const dim3 grid((unsigned)((n_items + WG / 64 - 1) / (WG / 64))), block(WG);
-  const int2 *its = reinterpret_cast<const int2 *>(items);
-#define RGCN_BLOCK_LAUNCH(BI, BO)                                                                                              \
-  hipLaunchKernelGGL((block_wgrad_kernel<BI, BO>), grid, block, 0, st, X, G, dblocks, p_src, p_dst, p_val, chunk_rel, its,     \
-                     (long long)n_items, nb, bi, bo, n_rel_blocks, lpm)
-  if (bi == 4 && bo == 4) RGCN_BLOCK_LAUNCH(4, 4);
-  else if (bi == 5 && bo == 5) RGCN_BLOCK_LAUNCH(5, 5);
-  else if (bi == 8 && bo == 8) RGCN_BLOCK_LAUNCH(8, 8);
-  else if (bi == 2 && bo == 2) RGCN_BLOCK_LAUNCH(2, 2);
-  else RGCN_BLOCK_LAUNCH(0, 0);
-#undef RGCN_BLOCK_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
+  return block_wgrad_launch<false>(X, G, dblocks, p_src, p_dst, p_val, chunk_rel, items, n_items, n_rel_blocks, nb, bi, bo,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int rgcn_block_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dblocks, const int32_t *p_src, const int32_t *p_dst,
+                                     const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items,
+                                     int32_t n_rel_blocks, int32_t nb, int32_t bi, int32_t bo, void *stream) {
+  if (!X || !G || !dblocks || n_items < 0 || nb <= 0 || n_rel_blocks < 0 ||
+      (n_items && (!items || !p_src || !p_dst || !p_val || !chunk_rel))) {
+    rgcn_set_error("block_wgrad_bf16: bad argument");
+    return RGCN_EINVAL;
+  }
+  if (!rgcn_block_supported(bi, bo)) {
+    rgcn_set_error("block_wgrad_bf16: blocks of %d x %d (limit %d x %d)", bi, bo, MAXB, MAXB);
+    return RGCN_EUNSUPPORTED;
+  }
+  return block_wgrad_launch<true>(reinterpret_cast<const float *>(X), reinterpret_cast<const float *>(G), dblocks, p_src, p_dst, p_val,
+                                  chunk_rel, items, n_items, n_rel_blocks, nb, bi, bo, (hipStream_t)stream);
 }

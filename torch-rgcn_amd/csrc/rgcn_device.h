@@ -71,6 +71,23 @@ __device__ __forceinline__ unsigned bf16x2_round(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t{lo, hi}), bf16x2_t));
 }
 __device__ __forceinline__ uint2 bf16x4_round(float4 a) { return uint2{bf16x2_round(a.x, a.y), bf16x2_round(a.z, a.w)}; }
+// single elements (rows whose segments are not 8-byte aligned: 5-wide blocks, widths that are no multiple of 4)
+__device__ __forceinline__ float bf16_widen(uint16_t u) { return __uint_as_float((unsigned)u << 16); }
+__device__ __forceinline__ uint16_t bf16_round(float a) { return (uint16_t)(bf16x2_round(a, 0.f) & 0xFFFFu); }
+
+// The CSR kernels with bf16 output (rgcn_block_spmm_bf16, rgcn_diag_spmm_bf16) and hub rows: the rows' pieces (RGCN_U_SHARED) add fp32
+// values into a zeroed fp32 scratch [n_rows][d]; this second launch rounds those rows -- once -- into the bf16 output.  LANES lanes per
+// unit; the unit with RGCN_U_FIRST stands for its row.
+template <int LANES>
+__global__ __launch_bounds__(256) void round_shared_rows_bf16_kernel(const float *__restrict__ scratch, uint16_t *__restrict__ out,
+                                                                     const int4 *__restrict__ units, long long n_units, int d) {
+  const long long u = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;
+  if (u >= n_units) return;
+  const int4 unit = units[u];
+  if ((unit.w & (RGCN_U_SHARED | RGCN_U_FIRST)) != (RGCN_U_SHARED | RGCN_U_FIRST)) return;
+  const size_t base = (size_t)unit.x * d;
+  for (int f = threadIdx.x % LANES; f < d; f += LANES) out[base + f] = bf16_round(scratch[base + f]);
+}
 
 constexpr int ROW_SHR = 0x110;  // + n : lane m reads lane m-n of its 16-lane row
 constexpr int ROW_SHL = 0x100;  // + n : lane m reads lane m+n

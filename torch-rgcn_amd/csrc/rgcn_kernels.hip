@@ -880,11 +880,16 @@ __global__ __launch_bounds__(WG) void featureless_wgrad_kernel(
 // the zeroed output).  `lr` lanes per unit = lr / lpm messages in flight x lpm lanes x float4; unrolled by two.
 // TABLE (featureless layer on a graph with sparse (tile, relation) buckets): X is the weight table [R][n_src][d] itself, the message's
 // row is table[rel][src] and there is no w -- out[row, :] = bias + the sum of val * table[rel, src, :].
-template <bool TABLE>
+// O16 (rgcn_diag_spmm_bf16; not with TABLE): empty -- the fp32 kernel, its arguments as they were -- or one `uint16_t *`:
+// X holds bf16 rows (8 bytes per 4 features when d % 4 == 0, else 2-byte elements; widened), w and bias stay fp32; rows of units that are
+// not shared are rounded once and written through that pointer (NULL: they stay fp32 in `out`), hub pieces add fp32 values to `out`.
+template <bool TABLE, typename... O16>
 __global__ __launch_bounds__(WG) void diag_csr_kernel(
     const float *__restrict__ X, const float *__restrict__ w, const float *__restrict__ bias, float *__restrict__ out,
     const int4 *__restrict__ units, long long n_units, const int *__restrict__ e_src, const int *__restrict__ e_rel,
-    const float *__restrict__ e_val, int d, int lpm, int lr, long long n_src, int relu_out) {
+    const float *__restrict__ e_val, int d, int lpm, int lr, long long n_src, int relu_out, O16... out16) {
+  constexpr bool BF = sizeof...(O16) != 0;
+  static_assert(!(BF && TABLE), "the featureless table stays fp32");
   const long long u = ((long long)blockIdx.x * WG + threadIdx.x) / lr;
   const int sub = threadIdx.x % lr, g = sub / lpm, j = sub % lpm, gpr = lr / lpm;
   const bool on = u < n_units;
@@ -905,7 +910,21 @@ __global__ __launch_bounds__(WG) void diag_csr_kernel(
         const float *xa = X + ((TABLE ? ra * n_src : 0) + e_src[e]) * (size_t)d + f;
         const float *xb = X + ((TABLE ? rb * n_src : 0) + e_src[hb ? eb : e]) * (size_t)d + f;
         const float *wa = TABLE ? xa : w + (size_t)ra * d + f, *wb = TABLE ? xb : w + (size_t)rb * d + f;
-        if (vec) {
+        if constexpr (BF) {
+          const uint16_t *ha = reinterpret_cast<const uint16_t *>(X) + (size_t)e_src[e] * d + f;
+          const uint16_t *hb2 = reinterpret_cast<const uint16_t *>(X) + (size_t)e_src[hb ? eb : e] * d + f;
+          if (vec) {
+            const float4 t0 = bf16x4_widen(*reinterpret_cast<const uint2 *>(ha)), t1 = bf16x4_widen(*reinterpret_cast<const uint2 *>(hb2));
+            const f32x4 x0 = {t0.x, t0.y, t0.z, t0.w}, x1 = {t1.x, t1.y, t1.z, t1.w};
+            const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wa), w1 = *reinterpret_cast<const f32x4 *>(wb);
+            a += x0 * w0 * va;
+            b += x1 * w1 * vb;
+          } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (f + q < d) { a[q] += bf16_widen(ha[q]) * wa[q] * va; b[q] += bf16_widen(hb2[q]) * wb[q] * vb; }
+          }
+        } else if (vec) {
           const f32x4 x0 = *reinterpret_cast<const f32x4 *>(xa), x1 = *reinterpret_cast<const f32x4 *>(xb);
           if (TABLE) {
             a += x0 * va;
@@ -935,7 +954,18 @@ __global__ __launch_bounds__(WG) void diag_csr_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) a[q] = fmaxf(a[q], 0.f);
       }
-      if (vec && !shared) {
+      uint16_t *o16 = nullptr;
+      if constexpr (BF) o16 = (out16, ...);
+      if (BF && !shared && o16) {                 // bf16 row of a unit that owns it: one rounding
+        uint16_t *oh = o16 + (size_t)unit.x * d + f;
+        if (vec) {
+          *reinterpret_cast<uint2 *>(oh) = bf16x4_round(make_float4(a[0], a[1], a[2], a[3]));
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (f + q < d) oh[q] = bf16_round(a[q]);
+        }
+      } else if (vec && !shared) {
         *reinterpret_cast<f32x4 *>(o) = a;
       } else {
 #pragma unroll
@@ -989,7 +1019,8 @@ __global__ __launch_bounds__(WG) void featureless_csr_wgrad_kernel(
 // twice: 57 M fabric requests per launch on the AM-shaped graph instead of 27 M, profiles/r02_pmc_csr_kernels.json),
 // 64 / lpm slots in flight, two per lane; the slot groups are summed with wave shuffles, one float4 of atomics per
 // (item, 4 columns).  Rows wider than 256 floats loop over column blocks.
-template <bool VEC>
+// BF (rgcn_diag_wgrad_bf16): X and G hold bf16 rows (widened); BF = false: the fp32 kernel as it was
+template <bool VEC, bool BF = false>
 __global__ __launch_bounds__(WG) void diag_wgrad_kernel(
     const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ dw, const int *__restrict__ p_src,
     const int *__restrict__ p_dst, const float *__restrict__ p_val, const int *__restrict__ chunk_rel,
@@ -1013,7 +1044,18 @@ __global__ __launch_bounds__(WG) void diag_wgrad_kernel(
         const float v = have ? p_val[ss] : 0.f;
         const float *x = X + (size_t)p_src[ss] * d + col, *gr = G + (size_t)max(p_dst[ss], 0) * d + col;
         f32x4 r = {0.f, 0.f, 0.f, 0.f};
-        if (vec4) {
+        if constexpr (BF) {
+          const uint16_t *xh = reinterpret_cast<const uint16_t *>(X) + (size_t)p_src[ss] * d + col;
+          const uint16_t *gh = reinterpret_cast<const uint16_t *>(G) + (size_t)max(p_dst[ss], 0) * d + col;
+          if (vec4) {
+            const float4 t0 = bf16x4_widen(*reinterpret_cast<const uint2 *>(xh)), t1 = bf16x4_widen(*reinterpret_cast<const uint2 *>(gh));
+            r = f32x4{t0.x, t0.y, t0.z, t0.w} * f32x4{t1.x, t1.y, t1.z, t1.w} * v;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (col + i < d) r[i] = v * bf16_widen(xh[i]) * bf16_widen(gh[i]);
+          }
+        } else if (vec4) {
           r = *reinterpret_cast<const f32x4 *>(x) * *reinterpret_cast<const f32x4 *>(gr) * v;
         } else {
 #pragma unroll
@@ -1043,7 +1085,7 @@ __global__ __launch_bounds__(WG) void diag_wgrad_kernel(
 // ------------------------------------------------------------------ column sum (bias gradient)
 // Two stages, no atomics, fixed summation order (bit-reproducible): stage A -- every workgroup streams its rows (float4 per
 // thread when d % 4 == 0) and leaves one partial row in `partial[block][d]`; stage B -- one workgroup sums the partial rows.
-// BF (rgcn_colsum_bf16, VEC4 only): G holds bf16 rows (8 bytes per 4 columns, widened); BF = false: the fp32 kernel as it was
+// BF (rgcn_colsum_bf16): G holds bf16 rows (VEC4: 8 bytes per 4 columns; else 2-byte elements; widened); BF = false: the fp32 kernel as it was
 template <bool VEC4, bool BF = false>
 __global__ __launch_bounds__(WG) void colsum_a_kernel(const float *__restrict__ G, float *__restrict__ partial, long long n, int d) {
   __shared__ float part[WG * 4];
@@ -1061,6 +1103,8 @@ __global__ __launch_bounds__(WG) void colsum_a_kernel(const float *__restrict__ 
           if constexpr (BF) x = bf16x4_widen(*reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(G) + (size_t)row * d + 4 * cc));
           else x = *reinterpret_cast<const float4 *>(G + (size_t)row * d + 4 * cc);
           a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
+        } else if constexpr (BF) {
+          a.x += bf16_widen(reinterpret_cast<const uint16_t *>(G)[(size_t)row * d + cc]);
         } else {
           a.x += G[(size_t)row * d + cc];
         }
@@ -1873,15 +1917,72 @@ extern "C" int rgcn_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dW, 
 }
 
 extern "C" int rgcn_colsum_bf16(const uint16_t *G, float *db, float *scratch, int64_t n, int32_t d, void *stream) {
-  if (!G || !db || !scratch || n < 0 || d <= 0 || d % 4 || d > 256) { rgcn_set_error("colsum_bf16: bad argument (d a multiple of 4, at most 256)"); return RGCN_EINVAL; }
+  if (!G || !db || !scratch || n < 0 || d <= 0) { rgcn_set_error("colsum_bf16: bad argument"); return RGCN_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) { HIP_TRY(zero_async(db, (size_t)d * sizeof(float), st)); return RGCN_OK; }
-  const int lanes = d / 4;
+  // any width (the block and diagonal layers: 500, 30): rows wider than 256 threads' worth loop over column blocks in both stages, widths
+  // that are no multiple of 4 read 2-byte elements
+  const bool vec4 = d % 4 == 0;
+  const int lanes = vec4 ? d / 4 : d;
   const int groups = std::max(1, WG / lanes);
   const int64_t max_part = d <= 32 ? 512 : (d <= 128 ? 128 : 64);
   const unsigned gx = (unsigned)std::min<int64_t>((n + groups - 1) / groups, max_part);
-  hipLaunchKernelGGL((colsum_a_kernel<true, true>), dim3(gx), dim3(WG), 0, st, reinterpret_cast<const float *>(G), scratch, (long long)n, d);
+  if (vec4) hipLaunchKernelGGL((colsum_a_kernel<true, true>), dim3(gx), dim3(WG), 0, st, reinterpret_cast<const float *>(G), scratch, (long long)n, d);
+  else hipLaunchKernelGGL((colsum_a_kernel<false, true>), dim3(gx), dim3(WG), 0, st, reinterpret_cast<const float *>(G), scratch, (long long)n, d);
   hipLaunchKernelGGL(colsum_b_kernel, dim3(1), dim3(WG), 0, st, scratch, db, (int)gx, d);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_diag_spmm_bf16(const uint16_t *X, const float *w, const float *bias, uint16_t *out, float *scratch,
+                                   const int32_t *rowptr_units, int64_t n_units, int64_t n_split, const int32_t *e_src,
+                                   const int32_t *e_rel, const float *e_val, int64_t n_rows, int32_t R, int32_t d, void *stream) {
+  (void)R;
+  if (!X || !w || (!out && !scratch) || (n_split && !scratch) || d <= 0 || n_rows < 0 || n_units < 0 || n_split < 0 ||
+      (n_units && (!rowptr_units || !e_src || !e_rel || !e_val))) {
+    rgcn_set_error("diag_spmm_bf16: bad argument (out or the fp32 scratch; hub pieces need the scratch)");
+    return RGCN_EINVAL;
+  }
+  if (n_rows == 0 || n_units == 0) return RGCN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // hub pieces add fp32 values into the zeroed scratch; their rows are rounded to bf16 once afterwards: never bf16 atomics
+  if (n_split) HIP_TRY(zero_async(scratch, (size_t)n_rows * d * sizeof(float), st));
+  int lpm = 1;                                  // lanes per message: four features each, a power of two
+  while (lpm < 64 && 4 * lpm < d) lpm *= 2;
+  const int lr = std::min(64, std::max(16, 2 * lpm));
+  const int upw = WG / lr;
+  const unsigned gx = (unsigned)((n_units + upw - 1) / upw);
+  const int4 *un = reinterpret_cast<const int4 *>(rowptr_units);
+  hipLaunchKernelGGL((diag_csr_kernel<false, uint16_t *>), dim3(gx), dim3(WG), 0, st, reinterpret_cast<const float *>(X), w, bias, scratch,
+                     un, (long long)n_units, e_src, e_rel, e_val, d, lpm, lr, 0LL, 0, out);
+  HIP_TRY(hipGetLastError());
+  if (n_split && out) {
+    hipLaunchKernelGGL(round_shared_rows_bf16_kernel<16>, dim3((unsigned)((n_units * 16 + WG - 1) / WG)), dim3(WG), 0, st, scratch, out, un,
+                       (long long)n_units, d);
+    HIP_TRY(hipGetLastError());
+  }
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_diag_wgrad_bf16(const uint16_t *X, const uint16_t *G, float *dw, const int32_t *p_src, const int32_t *p_dst,
+                                    const float *p_val, const int32_t *chunk_rel, const int32_t *items, int64_t n_items,
+                                    int32_t R, int32_t d, void *stream) {
+  if (!X || !G || !dw || R <= 0 || d <= 0 || n_items < 0 || (n_items && (!items || !p_src || !p_dst || !p_val || !chunk_rel))) {
+    rgcn_set_error("diag_wgrad_bf16: bad argument");
+    return RGCN_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(zero_async(dw, (size_t)R * d * sizeof(float), st));
+  if (n_items == 0) return RGCN_OK;
+  int lpm = 1;                                  // lanes per slot: four features each, a power of two
+  while (lpm < 64 && 4 * lpm < d) lpm *= 2;
+  const dim3 grid((unsigned)((n_items + WG / 64 - 1) / (WG / 64)));
+  const float *Xf = reinterpret_cast<const float *>(X), *Gf = reinterpret_cast<const float *>(G);
+  const int2 *its = reinterpret_cast<const int2 *>(items);
+  if ((d & 3) == 0)
+    hipLaunchKernelGGL((diag_wgrad_kernel<true, true>), grid, dim3(WG), 0, st, Xf, Gf, dw, p_src, p_dst, p_val, chunk_rel, its, (long long)n_items, d, lpm);
+  else
+    hipLaunchKernelGGL((diag_wgrad_kernel<false, true>), grid, dim3(WG), 0, st, Xf, Gf, dw, p_src, p_dst, p_val, chunk_rel, its, (long long)n_items, d, lpm);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

@@ -1476,7 +1476,7 @@ def wgrad_bf16(X, G, plan, num_rels):
 
 
 def colsum_bf16(G):
-    """db [d] fp32 = column sums of bf16 G (rgcn_colsum_bf16)"""
+    """db [d] fp32 = column sums of bf16 G (rgcn_colsum_bf16; any width)"""
     _req(G, "grad_output", torch.bfloat16)
     db = torch.empty(G.shape[1], device=G.device, dtype=torch.float32)
     scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(c_i64(G.shape[0]), c_i32(G.shape[1]))), device=G.device, dtype=torch.float32)
@@ -1901,6 +1901,71 @@ def colsum(G):
         _check(lib().rgcn_colsum_f32(_dp(G), _dp(db), _dp(scratch), c_i64(G.shape[0]), c_i32(G.shape[1]),
                                      _stream(G.device)), "colsum")
     return db
+
+
+def block_spmm_bf16(X, blocks, bias, csr, transposed=False, relu=False, out_f32=False):
+    """block_spmm for bf16 rows X (rgcn_block_spmm_bf16; blocks and bias fp32): rows gathered as bf16, fp32 products and sums, -> bf16 rounded
+    once (hub pieces summed in an fp32 scratch and rounded by a second launch; relu on a CSR with hub pieces is applied after the rounding,
+    which is exact).  out_f32: the unrounded fp32 sums instead (the caller adds a further term before its one rounding)."""
+    _req(X, "features", torch.bfloat16); _req(blocks, "blocks"); _req(bias, "bias")
+    Rb, nb, bi, bo = blocks.shape
+    assert X.shape[1] == nb * (bo if transposed else bi)
+    width = nb * (bi if transposed else bo)
+    if csr.src.numel() == 0:
+        out = _empty_csr_out(csr, width, bias, relu, X.device)
+        return out if out_f32 else out.to(torch.bfloat16)
+    units, n_units, n_split = _csr_units(csr)
+    fuse_relu = relu and n_split == 0
+    out = None if out_f32 else torch.empty((csr.n_rows, width), device=X.device, dtype=torch.bfloat16)
+    scratch = torch.empty((csr.n_rows, width), device=X.device, dtype=torch.float32) if (out_f32 or n_split) else None
+    flags = (F_TRANSPOSE_W if transposed else 0) | (F_RELU if fuse_relu else 0)
+    with _on(X.device), _timed("block_spmm_bf16"):
+        _check(lib().rgcn_block_spmm_bf16(_dp(X), _dp(blocks), _dp(bias), _dp(out), _dp(scratch), _dp(units), _dp(csr.rowptr),
+                                          c_i64(n_units), c_i64(n_split), _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows),
+                                          c_i32(Rb), c_i32(nb), c_i32(bi), c_i32(bo), c_i32(flags), _stream(X.device)), "block_spmm_bf16")
+    res = scratch if out_f32 else out
+    return res.relu_() if (relu and not fuse_relu) else res
+
+
+def block_wgrad_bf16(X, G, scatter_plan, shape):
+    """block_wgrad for bf16 X and G (rgcn_block_wgrad_bf16) -> dblocks fp32"""
+    _req(X, "features", torch.bfloat16); _req(G, "grad_output", torch.bfloat16)
+    p = scatter_plan
+    Rb, nb, bi, bo = shape
+    dB = torch.empty(shape, device=X.device, dtype=torch.float32)
+    with _on(X.device), _timed("block_wgrad_bf16"):
+        _check(lib().rgcn_block_wgrad_bf16(_dp(X), _dp(G), _dp(dB), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
+                                           _dp(p.items), c_i64(p.n_items), c_i32(Rb), c_i32(nb), c_i32(bi), c_i32(bo),
+                                           _stream(X.device)), "block_wgrad_bf16")
+    return dB
+
+
+def diag_spmm_bf16(X, w, bias, csr):
+    """diag_spmm for bf16 rows X (rgcn_diag_spmm_bf16; w and bias fp32) -> bf16, rounded once; hub pieces as in block_spmm_bf16"""
+    _req(X, "features", torch.bfloat16); _req(w, "weights"); _req(bias, "bias")
+    R, d = w.shape
+    assert X.shape[1] == d
+    units, n_units, n_split = _csr_units(csr)
+    assert units is not None, "the diagonal layer is not part of the sync-free LP step"
+    out = torch.empty((csr.n_rows, d), device=X.device, dtype=torch.bfloat16)
+    scratch = torch.empty((csr.n_rows, d), device=X.device, dtype=torch.float32) if n_split else None
+    with _on(X.device), _timed("diag_spmm_bf16"):
+        _check(lib().rgcn_diag_spmm_bf16(_dp(X), _dp(w), _dp(bias), _dp(out), _dp(scratch), _dp(units), c_i64(n_units), c_i64(n_split),
+                                         _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i32(R), c_i32(d),
+                                         _stream(X.device)), "diag_spmm_bf16")
+    return out
+
+
+def diag_wgrad_bf16(X, G, scatter_plan, num_rels):
+    """diag_wgrad for bf16 X and G (rgcn_diag_wgrad_bf16) -> dw fp32"""
+    _req(X, "features", torch.bfloat16); _req(G, "grad_output", torch.bfloat16)
+    p, d = scatter_plan, X.shape[1]
+    dw = torch.empty((num_rels, d), device=X.device, dtype=torch.float32)
+    with _on(X.device), _timed("diag_wgrad_bf16"):
+        _check(lib().rgcn_diag_wgrad_bf16(_dp(X), _dp(G), _dp(dw), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
+                                          _dp(p.items), c_i64(p.n_items), c_i32(num_rels), c_i32(d), _stream(X.device)),
+               "diag_wgrad_bf16")
+    return dw
 
 
 def resize3(src, shape, src1=None, n1d=None):

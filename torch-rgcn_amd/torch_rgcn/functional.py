@@ -734,6 +734,135 @@ def use_diag_path(graph, d):
     return getattr(graph, "_dev", None) is not None and routes.get("diag_path") != "0"
 
 
+# bf16 storage of the two structured decompositions: storage twins of _BlockMP / _DiagMP.  X and the upstream gradient
+# are gathered as bf16 rows, the parameters arrive widened to fp32 by the layer (autograd carries the cast back: a bf16 parameter gets a bf16
+# gradient), out and dX are fp32 sums rounded once, the parameter gradients fp32.  Nothing of size R x d x d is built.
+
+
+class _BlockMPBF16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, blocks, bias, graph, relu):
+        X, blocks = dense(X), dense(blocks)
+        b = None if bias is None else dense(bias)
+        out = _native.block_spmm_bf16(X, blocks, b, graph.csr("fwd"), relu=relu)
+        ctx.save_for_backward(X, blocks, out if relu else None)
+        ctx.graph, ctx.has_bias, ctx.relu = graph, bias is not None, relu
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, blocks, out = ctx.saved_tensors
+        g = dense(g.to(torch.bfloat16))              # (exact when it comes from a bf16 consumer)
+        if ctx.relu:
+            g = torch.ops.aten.threshold_backward(g, out, 0.0)        # a mask: exact in bf16
+        graph = ctx.graph
+        dX = dB = db = None
+        if ctx.needs_input_grad[0]:
+            dX = _native.block_spmm_bf16(g, blocks, None, graph.csr("bwd"), transposed=True)
+        if ctx.needs_input_grad[1]:
+            dB = _native.block_wgrad_bf16(X, g, graph.wgt_plan(), tuple(blocks.shape))
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = _native.colsum_bf16(g)
+        return dX, dB, db, None, None
+
+
+def _check_bf16_args(name, features, *params):
+    if features.dtype != torch.bfloat16:
+        raise TypeError(f"{name}: features must be torch.bfloat16, got {features.dtype}")
+    if any(p is not None and p.dtype != torch.float32 for p in params):
+        raise TypeError(f"{name}: the parameters are widened to torch.float32 by the caller")
+
+
+def block_mp_bf16(features, blocks, bias, graph, relu=False):
+    """block_mp for bf16 features [N, nb * bi]: blocks [R', nb, bi, bo] and bias fp32 -> bf16 [N, nb * bo] (csrc/rgcn_block.hip, bf16 forms)"""
+    _check_bf16_args("block_mp_bf16", features, blocks, bias)
+    return _BlockMPBF16.apply(features, blocks, bias, graph, bool(relu))
+
+
+class _BlockSelfMPBF16(torch.autograd.Function):
+    """The LP layer with block decomposition on bf16 features: out = round(block part + self-loop part), ONE rounding.  The block part
+    (relations 0 .. R-2) is gathered as bf16 and left as unrounded fp32 sums (the fp32 output mode of rgcn_block_spmm_bf16); the self-loop
+    relation has a dense weight and one message per node, X.float() @ blocks_self on rgcn_gemm_f32, masked by the node keep-mask or by
+    the schlichtkrull dropout exactly as the fp32 route does (torch.native_dropout: what nn.functional.dropout dispatches to on the GPU, so
+    a seeded run draws the same mask in both dtypes).  dX likewise: transposed block spmm (fp32 output mode) + g @ blocks_self^T, rounded once."""
+
+    @staticmethod
+    def forward(ctx, X, blocks, blocks_self, bias, graph, node_mask, self_drop):
+        X, blocks, blocks_self = dense(X), dense(blocks), dense(blocks_self)
+        b = None if bias is None else dense(bias)
+        acc = _native.block_spmm_bf16(X, blocks, b, graph.csr("fwd"), out_f32=True)
+        own = _native.gemm(X.float(), blocks_self)
+        drop_mask = None
+        if self_drop is not None:
+            own, drop_mask = torch.native_dropout(own, self_drop, True)
+        elif node_mask is not None:
+            own = own * node_mask[:, None].to(own.dtype)
+        ctx.save_for_backward(X, blocks, blocks_self, drop_mask, node_mask)
+        ctx.graph, ctx.has_bias, ctx.self_drop = graph, bias is not None, self_drop
+        return acc.add_(own).to(torch.bfloat16)
+
+    @staticmethod
+    def backward(ctx, g):
+        X, blocks, blocks_self, drop_mask, node_mask = ctx.saved_tensors
+        g = dense(g.to(torch.bfloat16))
+        graph = ctx.graph
+        g_own = g.float()                            # the gradient of the self-loop messages
+        if drop_mask is not None:
+            g_own = torch.ops.aten.native_dropout_backward(g_own, drop_mask, 1.0 / (1.0 - ctx.self_drop))
+        elif node_mask is not None:
+            g_own = g_own * node_mask[:, None].to(g_own.dtype)
+        dX = dB = dS = db = None
+        if ctx.needs_input_grad[0]:
+            acc = _native.block_spmm_bf16(g, blocks, None, graph.csr("bwd"), transposed=True, out_f32=True)
+            dX = acc.add_(_native.gemm(g_own, blocks_self, trans_b=True)).to(torch.bfloat16)
+        if ctx.needs_input_grad[1]:
+            dB = _native.block_wgrad_bf16(X, g, graph.wgt_plan(), tuple(blocks.shape))
+        if ctx.needs_input_grad[2]:
+            X32 = X.float()
+            dS = _native.gemm(X32, g_own, trans_a=True, split_k=_split_k(X32.shape[0], X32.shape[1], g_own.shape[1]))
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = _native.colsum_bf16(g)
+        return dX, dB, dS, db, None, None, None
+
+
+def block_self_mp_bf16(features, blocks, blocks_self, bias, graph, node_mask=None, self_drop=None):
+    """the LP layer's block decomposition for bf16 features: block_mp over `blocks` plus the dense self-loop relation features @ blocks_self
+    (rows masked by node_mask [N] where given, or dropped out with probability self_drop), rounded to bf16 once.  Parameters fp32."""
+    _check_bf16_args("block_self_mp_bf16", features, blocks, blocks_self, bias)
+    return _BlockSelfMPBF16.apply(features, blocks, blocks_self, bias, graph, node_mask, self_drop)
+
+
+class _DiagMPBF16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, w, bias, graph):
+        X, w = dense(X), dense(w)
+        b = None if bias is None else dense(bias)
+        out = _native.diag_spmm_bf16(X, w, b, graph.csr("fwd"))
+        ctx.save_for_backward(X, w)
+        ctx.graph, ctx.has_bias = graph, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, w = ctx.saved_tensors
+        g = dense(g.to(torch.bfloat16))
+        graph = ctx.graph
+        dX = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dX = _native.diag_spmm_bf16(g, w, None, graph.csr("bwd"))
+        if ctx.needs_input_grad[1]:
+            dw = _native.diag_wgrad_bf16(X, g, graph.wgt_plan(), w.shape[0])
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = _native.colsum_bf16(g)
+        return dX, dw, db, None
+
+
+def diag_mp_bf16(features, w, bias, graph):
+    """diag_mp for bf16 features [N, d]: w [R, d] and bias fp32 -> bf16 [N, d] (diag_csr_kernel / diag_wgrad_kernel, bf16 forms)"""
+    _check_bf16_args("diag_mp_bf16", features, w, bias)
+    return _DiagMPBF16.apply(features, w, bias, graph)
+
+
 def _split_k(K, M, N):
     """slices of the K dimension so that a skinny product (K = number of nodes, M x N = a weight matrix) still fills the chip"""
     tiles = -(-M // 128) * -(-N // 128)

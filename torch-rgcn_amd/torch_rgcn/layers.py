@@ -363,7 +363,9 @@ class RelationalGraphConvolutionNC(_RGCBase):
         return torch.relu(output) if activation == "relu" else output
 
     def _forward_bf16(self, features, activation, private):
-        """bf16 features: every decomposition on its dense fp32 W, bf16 output rounded once"""
+        """bf16 features, bf16 output rounded once.  Block-diagonal and diagonal weights are applied as they are on the bf16
+        forms of the block / diagonal kernels where the fp32 layer takes those kernels (above padded width 16; block_path / diag_path = 2:
+        at any width); every other layer -- width 16, relation-sharded, RGCN_DETERMINISTIC=1, host-built graphs -- on its dense fp32 W"""
         _require_gpu(features, "features")
         N, out_dim = self.num_nodes, self.out_features
         assert features.size() == (N, self.in_features), f"features {tuple(features.size())} vs ({N}, {self.in_features})"
@@ -372,6 +374,20 @@ class RelationalGraphConvolutionNC(_RGCBase):
         graph = self._graph_on(any_param.device)
         if graph.perm is not None:
             features = features.index_select(0, graph.inv)
+        structured = getattr(self, "_shard_group", None) is None and not F_.deterministic()
+        output = None
+        if structured and self.diag_weight_matrix:
+            wide = self.in_features + (-self.in_features % 16) > 16 or routes.get("diag_path") == "2"
+            if wide and not self.vertical_stacking and F_.use_diag_path(graph, self.in_features):
+                assert self.weights.size() == (self.num_relations, self.in_features)
+                output = F_.diag_mp_bf16(features, self.weights.float(), _f32(self.bias), graph)
+                if activation == "relu":
+                    output = torch.relu(output)
+        elif structured and self.weight_decomp == 'block' and F_.use_block_path(graph, self.blocks):
+            output = F_.block_mp_bf16(features, self.blocks.float(), _f32(self.bias), graph, relu=activation == "relu")
+        if output is not None:
+            assert output.size() == (N, out_dim)
+            return output.index_select(0, graph.perm) if graph.perm is not None else output
         weights = self._dense_weights_f32()
         assert weights.size() == (self.num_relations, self.in_features, out_dim)
         relu = activation == "relu" and ("private" if private else True)
@@ -499,7 +515,7 @@ class RelationalGraphConvolutionLP(_RGCBase):
                 # dense dropout on the self-loop messages X @ blocks_self before aggregation (added below)
                 self_drop = self.edge_dropout["self_loop"]
         if bf16:
-            return self._forward_bf16(features, graph, self_drop)
+            return self._forward_bf16(features, graph, self_drop, block_path, None if keep == 1 else mask)
         if self.weight_decomp == 'block':
             if block_path:      # blocks applied as they are; the dense self-loop relation is added below
                 weights = None
@@ -531,9 +547,13 @@ class RelationalGraphConvolutionLP(_RGCBase):
         assert output.size() == (N, out_dim)
         return output
 
-    def _forward_bf16(self, features, graph, self_drop):
-        """bf16 features: the dense fp32 W of every decomposition (block: block_diag(blocks) with the dense self-loop relation),
-        bf16 output rounded once"""
+    def _forward_bf16(self, features, graph, self_drop, block_path=False, node_mask=None):
+        """bf16 features, bf16 output rounded once.  Block decomposition on the block path: the blocks as they are on the bf16
+        block kernels plus the dense self-loop relation, summed in fp32 and rounded once (F_.block_self_mp_bf16); everything else on the dense
+        fp32 W of its decomposition (block: block_diag(blocks) with the dense self-loop relation)"""
+        if block_path and not F_.deterministic():
+            return F_.block_self_mp_bf16(features, self.blocks.float(), self.blocks_self.float(), _f32(self.bias), graph,
+                                         node_mask=node_mask, self_drop=self_drop)
         if self.weight_decomp == 'block':
             own = torch.zeros_like(self.blocks_self, dtype=torch.float32) if self_drop is not None else self.blocks_self.float()
             weights = torch.cat([block_diag(self.blocks.float()), own[None]], dim=0)
