@@ -87,13 +87,14 @@ def test_shipped_library_has_no_wrong_result_switch():
     lib_path = os.path.join(PKG, "torch_rgcn", "lib", "librgcn_hip.so")
     if not os.path.isfile(lib_path):
         pytest.skip("library not built")
+    from torch_rgcn import _native
     L = ctypes.CDLL(lib_path)
-    L.rgcn_last_error.restype = ctypes.c_char_p
+    _native._bind(L, _native._HEADER_PATH)
     for name in (b"bwd_abl",):
-        assert L.rgcn_set_option(name, ctypes.c_int32(2)) != 0, name
-        assert L.rgcn_set_option(name, ctypes.c_int32(0)) == 0, name
-    assert L.rgcn_set_option(b"gemm_bm", ctypes.c_int32(64)) == 0 and L.rgcn_set_option(b"gemm_bm", ctypes.c_int32(0)) == 0
-    assert L.rgcn_set_option(b"no_such_option", ctypes.c_int32(1)) != 0
+        assert L.rgcn_set_option(name, 2) != 0, name
+        assert L.rgcn_set_option(name, 0) == 0, name
+    assert L.rgcn_set_option(b"gemm_bm", 64) == 0 and L.rgcn_set_option(b"gemm_bm", 0) == 0
+    assert L.rgcn_set_option(b"no_such_option", 1) != 0
     syms = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True).stdout
     assert "rgcn_blk_debug_read" not in syms and "abl" not in syms.lower().replace("available", ""), "ablation entry points in the shipped library"
 

@@ -7,7 +7,6 @@ elements and at most one bf16 ulp off elsewhere; the cancellation allowance appl
 the LP layer's self-loop sum change the order.  fp32 parameter gradients within 1e-4 relative, bf16 ones within 2^-7 and in the parameter's
 dtype.  Every route test asserts the new profile tags and the absence of the fp32 / dense-weight ones."""
 import copy
-import ctypes
 
 import numpy as np
 import pytest
@@ -365,21 +364,16 @@ def test_cabi_argument_checks():
     from torch_rgcn import _native
     L = _native.lib()
     EINVAL, EUNSUPPORTED = 1, 5
-    i32, i64 = ctypes.c_int32, ctypes.c_int64
     n, nb = 8, 2
     z16 = torch.zeros(n * nb * 9, dtype=BF, device=DEV)
     z32 = torch.zeros(3 * nb * 81, device=DEV)
     idx = torch.zeros(64, dtype=torch.int32, device=DEV)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    null = ctypes.c_void_p(None)
+    p, null = _native._dp, None
 
     def spmm(out, scratch, b):
-        return L.rgcn_block_spmm_bf16(p(z16), p(z32), null, out, scratch, null, p(idx), i64(n), i64(0), p(idx), p(idx), p(z32), i64(n), i32(3),
-                                      i32(nb), i32(b), i32(b), i32(0), null)
+        return L.rgcn_block_spmm_bf16(p(z16), p(z32), null, out, scratch, null, p(idx), n, 0, p(idx), p(idx), p(z32), n, 3, nb, b, b, 0, null)
     assert spmm(p(z16), p(z32), 9) == EUNSUPPORTED
     assert spmm(null, null, 4) == EINVAL
-    assert L.rgcn_block_wgrad_bf16(p(z16), p(z16), p(z32), p(idx), p(idx), p(z32), p(idx), p(idx), i64(0), i32(3), i32(nb), i32(9), i32(9),
-                                   null) == EUNSUPPORTED
-    assert L.rgcn_diag_spmm_bf16(p(z16), p(z32), null, null, null, p(idx), i64(n), i64(0), p(idx), p(idx), p(z32), i64(n), i32(3), i32(8),
-                                 null) == EINVAL
+    assert L.rgcn_block_wgrad_bf16(p(z16), p(z16), p(z32), p(idx), p(idx), p(z32), p(idx), p(idx), 0, 3, nb, 9, 9, null) == EUNSUPPORTED
+    assert L.rgcn_diag_spmm_bf16(p(z16), p(z32), null, null, null, p(idx), n, 0, p(idx), p(idx), p(z32), n, 3, 8, null) == EINVAL
     torch.cuda.synchronize()

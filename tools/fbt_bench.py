@@ -61,6 +61,7 @@ res = {"mode": mode, "max_degree": plan.max_src_degree,
 L = _native.lib()
 if hasattr(L, "rgcn_fbt_debug_read"):
     import ctypes
+    L.rgcn_fbt_debug_read.argtypes = [ctypes.c_void_p, ctypes.c_int]      # ablation build only: not in include/rgcn_hip.h
     buf = (ctypes.c_ulonglong * 8)()
     L.rgcn_fbt_debug_read(buf, 1)
     _native.fbasis_tile_fwd(bases, comps, bias, plan, mode=0)

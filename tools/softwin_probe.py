@@ -17,7 +17,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from torch_rgcn import _native  # noqa: E402
-from torch_rgcn._native import F_RELU, _check, _dp, _on, _stream, c_i32, c_i64, lib  # noqa: E402
+from torch_rgcn._native import F_RELU, _check, _dp, _on, _stream, lib  # noqa: E402
 from torch_rgcn.graph import graph_from_nc_triples  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -92,9 +92,9 @@ def make_plan(dst, src, rel, val, rows, order):
 
 
 def records(S, D, V, crel, rows, n_chunks):
-    rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(c_i64(n_chunks))) + 16, device=dev, dtype=torch.uint8)
+    rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(n_chunks)) + 16, device=dev, dtype=torch.uint8)
     with _on(dev):
-        _check(lib().rgcn_bwd_blk_prepare_f32(None, _dp(S), _dp(D), _dp(V), c_i32(rows), _dp(crel), c_i64(n_chunks), _dp(rec), _stream(dev)), "prep")
+        _check(lib().rgcn_bwd_blk_prepare_f32(None, _dp(S), _dp(D), _dp(V), rows, _dp(crel), n_chunks, _dp(rec), _stream(dev)), "prep")
     return rec
 
 
@@ -112,8 +112,8 @@ for rows in [int(v) for v in a.fwd_rows.split(",") if v]:
 
         def run():
             with _on(dev):
-                _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(b), _dp(out), _dp(rec), _dp(run_ptr), c_i64(n_tiles), c_i32(rows), c_i64(N),
-                                               c_i32(R), c_i32(0), None, c_i64(0), c_i64(0), _stream(dev)), "spmm_blk")
+                _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(b), _dp(out), _dp(rec), _dp(run_ptr), n_tiles, rows, N,
+                                               R, 0, None, 0, 0, _stream(dev)), "spmm_blk")
         med, mn = timeit(run, a.iters)
         err = float((out - ref).abs().max() / ref.abs().max())
         print(f"forward spmm_blk rows={rows} order={order}: pad {m_pad / M:.3f} chunks {n_chunks} med {med:.3f} min {mn:.3f} ms err {err:.1e}", flush=True)
@@ -134,8 +134,8 @@ for rows in [int(v) for v in a.bwd_rows.split(",") if v]:
 
         def run():
             with _on(dev):
-                _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(run_ptr), c_i64(n_tiles), c_i32(rows), c_i64(N),
-                                              c_i32(R), c_i32(0), None, c_i64(N), None, c_i64(0), c_i64(0), _stream(dev)), "bwd_blk")
+                _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(run_ptr), n_tiles, rows, N,
+                                              R, 0, None, N, None, 0, 0, _stream(dev)), "bwd_blk")
         med, mn = timeit(run, a.iters)
         e1 = float((dX - dX0).abs().max() / dX0.abs().max())
         e2 = float((dW - dW0).abs().max() / dW0.abs().max())

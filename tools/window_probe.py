@@ -14,7 +14,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from torch_rgcn import _native  # noqa: E402
-from torch_rgcn._native import _check, _dp, _on, _stream, c_i32, c_i64, lib  # noqa: E402
+from torch_rgcn._native import _check, _dp, _on, _stream, lib  # noqa: E402
 from torch_rgcn.graph import graph_from_nc_triples  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -67,8 +67,8 @@ for rows in [int(v) for v in a.rows.split(",")]:
 
         def run():
             with _on(dev):
-                _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(b), _dp(out), _dp(rec), _dp(plan.run_ptr), c_i64(plan.n_tiles),
-                                               c_i32(plan.tile_rows), c_i64(N), c_i32(R * nw), c_i32(0), None, c_i64(0), c_i64(0), _stream(dev)), "spmm_blk")
+                _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(b), _dp(out), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
+                                               plan.tile_rows, N, R * nw, 0, None, 0, 0, _stream(dev)), "spmm_blk")
         med, mn = timeit(run, a.iters)
         err = float((out - ref).abs().max() / ref.abs().max())
         print(f"spmm_blk rows={rows} tiles={plan.n_tiles} windows={nw} ({wrows * 64 / 1e6:.1f} MB): pad {plan.m_pad / M:.3f} chunks {plan.n_chunks} "

@@ -1,10 +1,16 @@
 """ctypes binding of librgcn_hip.so (C ABI in include/rgcn_hip.h).
 
-There is deliberately NO fallback: if the shared library is missing or a kernel
-launch fails, the caller gets an exception.  The library is built in-tree by
+The header is the one description of the ABI: lib() parses its prototypes and declares every entry point's `argtypes`
+and `restype` from them, so the wrappers below pass plain Python ints and addresses (None = NULL) and a wrong type or a
+missing argument raises in ctypes instead of reaching a kernel.  Surplus arguments are not caught by ctypes;
+tests/test_cabi_symbols.py compares every call site's arity with the header.
+
+There is deliberately NO fallback: if the shared library or the header is missing, a prototype cannot be bound or a
+kernel launch fails, the caller gets an exception.  The library is built in-tree by
 `__graft_entry__.build()` / `make -C torch-rgcn_amd/csrc`.
 """
 import ctypes
+import re
 import threading
 import os
 
@@ -15,16 +21,45 @@ from . import routes
 
 # RGCN_HIP_LIB: tools/ only -- the ablation build (make -C csrc abl -> lib/librgcn_hip_abl.so), whose kernels can be told to skip work
 _LIB_PATH = os.environ.get("RGCN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "librgcn_hip.so")
+_HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "include", "rgcn_hip.h")     # as the Makefile: -I../../include
 _lib = None
 
 OK, EINVAL, ENOMEM, ERANGE, EHIP, EUNSUPPORTED = range(6)
 CHUNK = 16
 
-c_i64, c_i32, c_int, c_void_p = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p
+c_i64 = ctypes.c_int64          # out-parameters: ctypes.byref(c_i64(0))
+_CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
 
 
 class NativeLibraryError(RuntimeError):
     pass
+
+
+def _ctype(ctype, where):
+    """a C type of the header (`const int32_t *`, `int64_t`) -> its ctypes type; every pointer but `const char *` is an address"""
+    if "*" in ctype:
+        return ctypes.c_char_p if re.fullmatch(r"const\s+char\s*\*", ctype) else ctypes.c_void_p
+    if ctype not in _CTYPES:
+        raise NativeLibraryError(f"{where}: no ctypes type for `{ctype}`")
+    return _CTYPES[ctype]
+
+
+def _bind(L, header):
+    """declare argtypes and restype of every `RGCN_API <ret> rgcn_name(<params>);` of the header on the loaded library -> their number"""
+    if not os.path.exists(header):
+        raise NativeLibraryError(f"{header} not found: the binding is declared from it")
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*", "", open(header).read(), flags=re.S | re.M)
+    protos = re.findall(r"\bRGCN_API\s+([^;()]+?)\b(rgcn_\w+)\s*\(([^;()]*)\)\s*;", text)
+    if len(protos) != len(re.findall(r"\bRGCN_API\b", text)):
+        raise NativeLibraryError(f"{header}: {len(re.findall('RGCN_API', text))} RGCN_API declarations, {len(protos)} readable prototypes")
+    for ret, name, params in protos:
+        if not hasattr(L, name):
+            raise NativeLibraryError(f"{L._name} does not export {name}, which {header} declares: rebuild the library")
+        fn, where = getattr(L, name), f"{header}: {name}"
+        fn.restype = _ctype(ret.strip(), where)
+        # a parameter is its type followed by its name: `const float *X`, `int64_t n_nodes`
+        fn.argtypes = [] if params.strip() in ("", "void") else [_ctype(re.sub(r"\w+\s*$", "", p).strip(), where) for p in params.split(",")]
+    return len(protos)
 
 
 def lib():
@@ -35,16 +70,7 @@ def lib():
                 f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). torch_rgcn has no CPU/eager fallback.")
         L = ctypes.CDLL(_LIB_PATH)
-        L.rgcn_version.restype = ctypes.c_char_p
-        L.rgcn_csrc_sha.restype = ctypes.c_char_p
-        L.rgcn_bwd_fused_scratch_floats.restype = ctypes.c_int64
-        L.rgcn_bwd_lean_slot_bytes.restype = ctypes.c_int64
-        L.rgcn_bwd_blk_rec_bytes.restype = ctypes.c_int64
-        L.rgcn_softwin_tmp_bytes.restype = ctypes.c_int64
-        L.rgcn_colsum_scratch_floats.restype = ctypes.c_int64
-        L.rgcn_gemm_scratch_floats.restype = ctypes.c_int64
-        L.rgcn_basis_sum_workspace_bytes.restype = ctypes.c_int64
-        L.rgcn_last_error.restype = ctypes.c_char_p
+        _bind(L, _HEADER_PATH)
         _lib = L
         defaults = {}
 
@@ -54,7 +80,7 @@ def lib():
                 L.rgcn_get_option(name.encode(), ctypes.byref(cur))
                 defaults[name] = cur.value
             v = defaults[name] if value is None else value
-            if L.rgcn_set_option(name.encode(), c_i32(v)) != OK:
+            if L.rgcn_set_option(name.encode(), v) != OK:
                 raise NativeLibraryError(f"route {name} = {v}: {L.rgcn_last_error().decode()}")
         routes._native_sink = sink
         routes.push_native()
@@ -88,12 +114,12 @@ def _np(a, dtype):
 
 def _hp(a):
     """host pointer of a numpy array (or None)"""
-    return None if a is None else c_void_p(a.ctypes.data)
+    return None if a is None else a.ctypes.data
 
 
 def _dp(t):
     """device pointer of a torch tensor (or None)"""
-    return None if t is None else c_void_p(t.data_ptr())
+    return None if t is None else t.data_ptr()
 
 
 # ----------------------------------------------------------------------------- per-kernel timing
@@ -148,11 +174,11 @@ _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def _stream(device):
-    """the current HIP stream of `device` as a void* (torch's raw-stream query when it exists: no Stream object per launch)"""
+    """the current HIP stream of `device` as an address (torch's raw-stream query when it exists: no Stream object per launch)"""
     if _RAW_STREAM is not None:
         idx = device.index
-        return c_void_p(_RAW_STREAM(torch.cuda.current_device() if idx is None else idx))
-    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        return _RAW_STREAM(torch.cuda.current_device() if idx is None else idx)
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 class _NoCtx:
@@ -180,7 +206,7 @@ def _on(device):
 def add_inverse_and_self_host(triples, num_nodes, num_rels):
     t = _np(triples, np.int64).reshape(-1, 3)
     out = np.empty((2 * t.shape[0] + num_nodes, 3), np.int64)
-    _check(lib().rgcn_add_inverse_and_self_host(_hp(t), c_i64(t.shape[0]), c_i64(num_nodes), c_i64(num_rels),
+    _check(lib().rgcn_add_inverse_and_self_host(_hp(t), t.shape[0], num_nodes, num_rels,
                                                 _hp(out)), "add_inverse_and_self")
     return out
 
@@ -191,24 +217,22 @@ def lp_augment_host(triples, num_nodes, num_rels, keep=None):
     out = np.empty((3 * E + num_nodes, 3), np.int64)
     k = None if keep is None else _np(keep, np.uint8)
     M, ns = c_i64(0), c_i64(0)
-    _check(lib().rgcn_lp_augment_host(_hp(t), c_i64(E), c_i64(num_nodes), c_i64(num_rels), _hp(k), _hp(out),
-                                      ctypes.byref(M), ctypes.byref(ns)), "lp_augment")
+    _check(lib().rgcn_lp_augment_host(_hp(t), E, num_nodes, num_rels, _hp(k), _hp(out), ctypes.byref(M),
+                                      ctypes.byref(ns)), "lp_augment")
     return out[:M.value], ns.value
 
 
 def edge_norm_host(triples_plus, num_nodes, num_rels, vertical, n_swap, i_tail):
     t = _np(triples_plus, np.int64).reshape(-1, 3)
     val = np.empty(t.shape[0], np.float32)
-    _check(lib().rgcn_edge_norm_host(_hp(t), c_i64(t.shape[0]), c_i64(num_nodes), c_i64(num_rels),
-                                     c_int(int(bool(vertical))), c_i64(n_swap), c_i64(i_tail), _hp(val)),
-           "edge_norm")
+    _check(lib().rgcn_edge_norm_host(_hp(t), t.shape[0], num_nodes, num_rels, int(bool(vertical)), n_swap, i_tail,
+                                     _hp(val)), "edge_norm")
     return val
 
 
 def synthetic_triples_host(num_nodes, num_rels, num_edges, seed=0):
     out = np.empty((num_edges, 3), np.int64)
-    _check(lib().rgcn_synthetic_triples_host(c_i64(num_nodes), c_i64(num_rels), c_i64(num_edges),
-                                             ctypes.c_uint64(seed), _hp(out)), "synthetic_triples")
+    _check(lib().rgcn_synthetic_triples_host(num_nodes, num_rels, num_edges, seed, _hp(out)), "synthetic_triples")
     return out
 
 
@@ -216,8 +240,8 @@ def edge_neighborhood_host(triples, num_nodes, sample_size, seed):
     """indices of `sample_size` triples drawn by edge-neighbourhood sampling (utils/misc.py:125-172)"""
     triples = np.ascontiguousarray(triples, np.int64)
     out = np.empty(sample_size, np.int64)
-    _check(lib().rgcn_edge_neighborhood_host(_hp(triples), c_i64(triples.shape[0]), c_i64(num_nodes),
-                                             c_i64(sample_size), ctypes.c_uint64(seed), _hp(out)), "edge_neighborhood")
+    _check(lib().rgcn_edge_neighborhood_host(_hp(triples), triples.shape[0], num_nodes, sample_size, seed,
+                                             _hp(out)), "edge_neighborhood")
     return out
 
 
@@ -237,9 +261,9 @@ def build_plan_host(dst, src, rel, val, n_dst, n_src, num_rels, tile_rows, max_i
     assert src.shape[0] == M and rel.shape[0] == M and val.shape[0] == M
     m_pad, n_chunks, n_tiles, n_items = c_i64(0), c_i64(0), c_i64(0), c_i64(0)
     L = lib()
-    _check(L.rgcn_plan_count_host(_hp(dst), _hp(rel), c_i64(M), c_i64(n_dst), c_i32(num_rels), c_i32(tile_rows),
-                                  c_i32(max_item_chunks), ctypes.byref(m_pad), ctypes.byref(n_chunks),
-                                  ctypes.byref(n_tiles), ctypes.byref(n_items)), "plan_count")
+    _check(L.rgcn_plan_count_host(_hp(dst), _hp(rel), M, n_dst, num_rels, tile_rows, max_item_chunks,
+                                  ctypes.byref(m_pad), ctypes.byref(n_chunks), ctypes.byref(n_tiles),
+                                  ctypes.byref(n_items)), "plan_count")
     p = HostPlan()
     p.n_dst, p.n_src, p.num_rels, p.tile_rows = n_dst, n_src, num_rels, tile_rows
     p.n_tiles, p.n_chunks, p.m_pad, p.n_items, p.n_messages = n_tiles.value, n_chunks.value, m_pad.value, n_items.value, M
@@ -253,20 +277,19 @@ def build_plan_host(dst, src, rel, val, n_dst, n_src, num_rels, tile_rows, max_i
     p.run_ptr = np.zeros(max(p.n_tiles, 1) * (num_rels + 1), np.int32) if want_runs else None
     can_pack = want_pack and n_src < (1 << 24) and tile_rows <= 255
     p.pack = np.empty((max(p.m_pad, 1), 2), np.int32) if can_pack else None
-    _check(L.rgcn_plan_fill_host(_hp(dst), _hp(src), _hp(rel), _hp(val), c_i64(M), c_i64(n_dst), c_i64(n_src),
-                                 c_i32(num_rels), c_i32(tile_rows), c_i32(max_item_chunks), _hp(p.src), _hp(p.dst),
-                                 _hp(p.val), _hp(p.perm), _hp(p.chunk_rel), _hp(p.tile_ptr), _hp(p.items),
-                                 _hp(p.run_ptr), _hp(p.pack)), "plan_fill")
+    _check(L.rgcn_plan_fill_host(_hp(dst), _hp(src), _hp(rel), _hp(val), M, n_dst, n_src, num_rels, tile_rows,
+                                 max_item_chunks, _hp(p.src), _hp(p.dst), _hp(p.val), _hp(p.perm), _hp(p.chunk_rel),
+                                 _hp(p.tile_ptr), _hp(p.items), _hp(p.run_ptr), _hp(p.pack)), "plan_fill")
     # work units of the tile kernels (hub tiles are cut into pieces)
     nu, ns = c_i64(0), c_i64(0)
-    _check(L.rgcn_plan_units_host(_hp(p.tile_ptr), c_i64(p.n_tiles), c_i32(max_unit_chunks), None, ctypes.byref(nu),
+    _check(L.rgcn_plan_units_host(_hp(p.tile_ptr), p.n_tiles, max_unit_chunks, None, ctypes.byref(nu),
                                   ctypes.byref(ns)), "plan_units")
     p.n_units, p.n_split = nu.value, ns.value
     p.units = np.zeros((max(p.n_units, 1), 4), np.int32)
     p.units_host = p.units
     p._cache = {}
-    _check(L.rgcn_plan_units_host(_hp(p.tile_ptr), c_i64(p.n_tiles), c_i32(max_unit_chunks), _hp(p.units),
-                                  ctypes.byref(nu), ctypes.byref(ns)), "plan_units")
+    _check(L.rgcn_plan_units_host(_hp(p.tile_ptr), p.n_tiles, max_unit_chunks, _hp(p.units), ctypes.byref(nu),
+                                  ctypes.byref(ns)), "plan_units")
     if p.n_chunks:
         cr = p.chunk_rel[:p.n_chunks]
         edges = np.flatnonzero(np.diff(cr) != 0)
@@ -357,8 +380,8 @@ def dev_split_triples(triples_plus, num_nodes, num_rels):
     M, dev = t.shape[0], t.device
     s, p, o, err = _i32(M, dev), _i32(M, dev), _i32(M, dev), _i32(1, dev)
     with _on(dev):
-        _check(lib().rgcn_dev_split_triples(_dp(t), c_i64(M), c_i64(num_nodes), c_i32(num_rels), _dp(s), _dp(p), _dp(o),
-                                            _dp(err), _stream(dev)), "dev_split_triples")
+        _check(lib().rgcn_dev_split_triples(_dp(t), M, num_nodes, num_rels, _dp(s), _dp(p), _dp(o), _dp(err),
+                                            _stream(dev)), "dev_split_triples")
     return s[:M], p[:M], o[:M], err
 
 
@@ -371,8 +394,8 @@ def dev_lp_expand(triples, num_nodes, num_rels0, keep):
     alive = torch.empty(M, dtype=torch.uint8, device=dev)
     k = None if keep is None else keep.to(torch.uint8).contiguous()
     with _on(dev):
-        _check(lib().rgcn_dev_lp_expand(_dp(t), c_i64(E), c_i64(num_nodes), c_i32(num_rels0), _dp(k), _dp(s), _dp(p),
-                                        _dp(o), _dp(alive), _dp(err), _stream(dev)), "dev_lp_expand")
+        _check(lib().rgcn_dev_lp_expand(_dp(t), E, num_nodes, num_rels0, _dp(k), _dp(s), _dp(p), _dp(o), _dp(alive),
+                                        _dp(err), _stream(dev)), "dev_lp_expand")
     return s, p, o, alive, err
 
 
@@ -381,9 +404,8 @@ def dev_edge_norm(s, p, o, alive, num_nodes, num_rels, vertical, n_swap):
     table = _i32(num_nodes * num_rels, dev)
     val = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
     with _on(dev):
-        _check(lib().rgcn_dev_edge_norm(_dp(s), _dp(p), _dp(o), _dp(alive), c_i64(M), c_i64(num_nodes), c_i32(num_rels),
-                                        c_int(int(bool(vertical))), c_i64(n_swap), _dp(table), _dp(val), _stream(dev)),
-               "dev_edge_norm")
+        _check(lib().rgcn_dev_edge_norm(_dp(s), _dp(p), _dp(o), _dp(alive), M, num_nodes, num_rels, int(bool(vertical)),
+                                        n_swap, _dp(table), _dp(val), _stream(dev)), "dev_edge_norm")
     return val[:M]
 
 
@@ -408,9 +430,9 @@ def build_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_ro
     scan_tmp = _i32(max(nbk, nbk * tile_rows if tall else 0) // 1024 + 4, dev)
     L = lib()
     with _on(dev):
-        _check(L.rgcn_dev_plan_count(_dp(dst), _dp(rel), _dp(alive), c_i64(M), c_i64(n_dst), c_i32(num_rels),
-                                     c_i32(tile_rows), _dp(cells), _dp(bucket_cnt), _dp(bucket_base), _dp(scan_tmp),
-                                     _dp(cells_tmp), _stream(dev)), "dev_plan_count")
+        _check(L.rgcn_dev_plan_count(_dp(dst), _dp(rel), _dp(alive), M, n_dst, num_rels, tile_rows, _dp(cells),
+                                     _dp(bucket_cnt), _dp(bucket_base), _dp(scan_tmp), _dp(cells_tmp),
+                                     _stream(dev)), "dev_plan_count")
     if sync_free:
         m_pad = (M + 15 * min(nbk, M) + CHUNK - 1) // CHUNK * CHUNK      # every non-empty bucket pads by < 16 slots
     else:
@@ -428,11 +450,10 @@ def build_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_ro
     p.run_ptr = _i32(n_tiles * (num_rels + 1), dev) if want_runs else None
     p.aux = _i32(m_pad, dev) if aux is not None else None
     with _on(dev):
-        _check(L.rgcn_dev_plan_fill(_dp(dst), _dp(src), _dp(rel), _dp(val), _dp(alive), c_i64(M), c_i64(n_dst),
-                                    c_i64(n_src), c_i32(num_rels), c_i32(tile_rows), _dp(cells), _dp(bucket_cnt),
-                                    _dp(bucket_base), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.pack), _dp(p.chunk_rel),
-                                    _dp(p.tile_ptr), _dp(p.run_ptr), _dp(aux), _dp(p.aux), None, c_i64(p.n_chunks),
-                                    _stream(dev)), "dev_plan_fill")
+        _check(L.rgcn_dev_plan_fill(_dp(dst), _dp(src), _dp(rel), _dp(val), _dp(alive), M, n_dst, n_src, num_rels,
+                                    tile_rows, _dp(cells), _dp(bucket_cnt), _dp(bucket_base), _dp(p.src), _dp(p.dst),
+                                    _dp(p.val), _dp(p.pack), _dp(p.chunk_rel), _dp(p.tile_ptr), _dp(p.run_ptr),
+                                    _dp(aux), _dp(p.aux), None, p.n_chunks, _stream(dev)), "dev_plan_fill")
     if sync_free:
         p.n_units, p.n_split, p.units_host = n_tiles, 0, None
         p.units = torch.empty((max(n_tiles, 1), 4), dtype=torch.int32, device=dev)
@@ -443,20 +464,19 @@ def build_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_ro
         else:
             p.n_items, p.items = 0, None
         with _on(dev):
-            _check(L.rgcn_dev_plan_finish_nosync(_dp(bucket_base), c_i64(n_tiles), c_i32(num_rels), c_i64(m_pad), _dp(p.src),
-                                                 _dp(p.dst), _dp(p.val), _dp(p.pack), _dp(p.aux), _dp(p.tile_ptr), _dp(p.units),
-                                                 _dp(p.items), c_i64(max(p.n_items, 1)), c_i32(max_item_chunks), _stream(dev)),
-                   "dev_plan_finish_nosync")
+            _check(L.rgcn_dev_plan_finish_nosync(_dp(bucket_base), n_tiles, num_rels, m_pad, _dp(p.src), _dp(p.dst), _dp(p.val),
+                                                 _dp(p.pack), _dp(p.aux), _dp(p.tile_ptr), _dp(p.units), _dp(p.items),
+                                                 max(p.n_items, 1), max_item_chunks, _stream(dev)), "dev_plan_finish_nosync")
         if p.items is None:
             p.items = _i32(2, dev).view(1, 2)
         return p
     # work units (hub tiles split) and the relation-major work list are tiny: host side
     tp_host = p.tile_ptr[:n_tiles + 1].cpu().numpy()
     nu, ns = c_i64(0), c_i64(0)
-    _check(L.rgcn_plan_units_host(_hp(tp_host), c_i64(n_tiles), c_i32(max_unit_chunks), None, ctypes.byref(nu),
+    _check(L.rgcn_plan_units_host(_hp(tp_host), n_tiles, max_unit_chunks, None, ctypes.byref(nu),
                                   ctypes.byref(ns)), "plan_units")
     units = np.zeros((max(nu.value, 1), 4), np.int32)
-    _check(L.rgcn_plan_units_host(_hp(tp_host), c_i64(n_tiles), c_i32(max_unit_chunks), _hp(units), ctypes.byref(nu),
+    _check(L.rgcn_plan_units_host(_hp(tp_host), n_tiles, max_unit_chunks, _hp(units), ctypes.byref(nu),
                                   ctypes.byref(ns)), "plan_units")
     p.n_units, p.n_split = nu.value, ns.value
     p.units_host = units
@@ -526,15 +546,15 @@ def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels,
     n_groups = n_tiles * max(own_waves, 1)
     L = lib()
     # (the chunks sorted in the second step number at most M / 16 + one per non-empty bucket)
-    tmp_bytes = int(L.rgcn_softwin_tmp_bytes(c_i64(max(M, nbk + 1, n_groups + 1, M // CHUNK + min(nbk, M) + 1))))
+    tmp_bytes = int(L.rgcn_softwin_tmp_bytes(max(M, nbk + 1, n_groups + 1, M // CHUNK + min(nbk, M) + 1)))
     tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
     keys = torch.empty(2 * max(M, 1), dtype=torch.int64, device=dev)
     order = torch.empty(2 * max(M, 1), dtype=torch.int32, device=dev)
     bucket_cnt, bucket_base, bucket_first = _i32(nbk + 1, dev), _i32(nbk + 1, dev), _i32(nbk + 1, dev)
     with _on(dev):
-        _check(L.rgcn_softwin_order(_dp(dst), _dp(src), _dp(rel), _dp(alive), c_i64(M), c_i64(n_dst), c_i64(n_src), c_i32(num_rels), c_i32(tile_rows),
-                                    _dp(keys[:max(M, 1)]), _dp(keys[max(M, 1):]), _dp(order[:max(M, 1)]), _dp(order[max(M, 1):]), _dp(bucket_cnt),
-                                    _dp(bucket_base), _dp(bucket_first), _dp(tmp), c_i64(tmp_bytes), _stream(dev)), "softwin_order")
+        _check(L.rgcn_softwin_order(_dp(dst), _dp(src), _dp(rel), _dp(alive), M, n_dst, n_src, num_rels, tile_rows, _dp(keys[:max(M, 1)]),
+                                    _dp(keys[max(M, 1):]), _dp(order[:max(M, 1)]), _dp(order[max(M, 1):]), _dp(bucket_cnt), _dp(bucket_base),
+                                    _dp(bucket_first), _dp(tmp), tmp_bytes, _stream(dev)), "softwin_order")
     rel_counts = bucket_cnt[:nbk].view(n_tiles, num_rels).sum(0, dtype=torch.int64)
     host = torch.cat([bucket_base[nbk:nbk + 1].long(), bucket_first[nbk:nbk + 1].long(), bucket_cnt[:nbk].max().view(1).long(), rel_counts]).cpu().numpy()
     m_pad, n_live, max_cnt = int(host[0]), int(host[1]), int(host[2])
@@ -561,11 +581,11 @@ def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels,
         tabs = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in own[:4]]
     nc1, mp1 = max(n_chunks, 1), max(m_pad, 1)
     with _on(dev):
-        _check(L.rgcn_softwin_fill(_dp(dst), _dp(src), _dp(val), _dp(keys[max(M, 1):]), _dp(order[max(M, 1):]), c_i64(n_live), c_i64(n_dst), c_i64(n_src),
-                                   c_i32(num_rels), c_i32(tile_rows), _dp(bucket_base), _dp(bucket_first), c_i64(m_pad), _dp(tabs[0]), _dp(tabs[1]),
-                                   _dp(tabs[2]), _dp(tabs[3]), c_i32(own_waves), _dp(stage[:mp1]), _dp(stage[mp1:]), _dp(stage_val), _dp(ckeys[:nc1]),
-                                   _dp(ckeys[nc1:]), _dp(cidx[:nc1]), _dp(cidx[nc1:]), _dp(crel), _dp(group_cnt), _dp(p.src), _dp(p.dst), _dp(p.val),
-                                   _dp(p.chunk_rel), _dp(group_ptr), _dp(tmp), c_i64(tmp_bytes), _stream(dev)), "softwin_fill")
+        _check(L.rgcn_softwin_fill(_dp(dst), _dp(src), _dp(val), _dp(keys[max(M, 1):]), _dp(order[max(M, 1):]), n_live, n_dst, n_src, num_rels, tile_rows,
+                                   _dp(bucket_base), _dp(bucket_first), m_pad, _dp(tabs[0]), _dp(tabs[1]), _dp(tabs[2]), _dp(tabs[3]), own_waves,
+                                   _dp(stage[:mp1]), _dp(stage[mp1:]), _dp(stage_val), _dp(ckeys[:nc1]), _dp(ckeys[nc1:]), _dp(cidx[:nc1]),
+                                   _dp(cidx[nc1:]), _dp(crel), _dp(group_cnt), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel), _dp(group_ptr),
+                                   _dp(tmp), tmp_bytes, _stream(dev)), "softwin_fill")
     p.tile_ptr = group_ptr[::max(own_waves, 1)].contiguous()
     p.run_ptr = torch.zeros(n_tiles * (num_rels + 1), dtype=torch.int32, device=dev)
     p.run_ptr[0::num_rels + 1] = p.tile_ptr[:-1]
@@ -699,9 +719,8 @@ def build_csr_device(dst, src, rel, val, alive, n_rows, sync_free=False, want_sl
     bucket_cnt, bucket_base, scan_tmp = _i32(1, dev), _i32(2, dev), _i32(n_rows // 1024 + 4, dev)
     L = lib()
     with _on(dev):         # (one bucket, one "relation": the relation array of the builder is NULL)
-        _check(L.rgcn_dev_plan_count(_dp(dst), None, _dp(alive), c_i64(M), c_i64(n_rows), c_i32(1), c_i32(n_rows),
-                                     _dp(cells), _dp(bucket_cnt), _dp(bucket_base), _dp(scan_tmp), _dp(cells_tmp),
-                                     _stream(dev)), "dev_plan_count")
+        _check(L.rgcn_dev_plan_count(_dp(dst), None, _dp(alive), M, n_rows, 1, n_rows, _dp(cells), _dp(bucket_cnt),
+                                     _dp(bucket_base), _dp(scan_tmp), _dp(cells_tmp), _stream(dev)), "dev_plan_count")
     # one bucket: the padded size is the live message count rounded up to 16 -- sized by its bound, the list length (dead
     # messages are few: dropped self loops), so that building a CSR never reads anything back from the device
     m_pad = (M + CHUNK - 1) // CHUNK * CHUNK
@@ -714,11 +733,10 @@ def build_csr_device(dst, src, rel, val, alive, n_rows, sync_free=False, want_sl
     p.val = torch.empty(max(m_pad, 1), dtype=torch.float32, device=dev)
     tile_ptr = _i32(2, dev)
     with _on(dev):
-        _check(L.rgcn_dev_plan_fill(_dp(dst), _dp(src), None, _dp(val), _dp(alive), c_i64(M), c_i64(n_rows),
-                                    c_i64(n_rows), c_i32(1), c_i32(n_rows), _dp(cells), _dp(bucket_cnt), _dp(bucket_base),
-                                    _dp(p.src), _dp(pdst), _dp(p.val), None, None, _dp(tile_ptr), None,
-                                    _dp(rel), _dp(p.rel), _dp(p.msg_slot), c_i64(m_pad // CHUNK), _stream(dev)),
-               "dev_plan_fill")
+        _check(L.rgcn_dev_plan_fill(_dp(dst), _dp(src), None, _dp(val), _dp(alive), M, n_rows, n_rows, 1, n_rows,
+                                    _dp(cells), _dp(bucket_cnt), _dp(bucket_base), _dp(p.src), _dp(pdst), _dp(p.val),
+                                    None, None, _dp(tile_ptr), None, _dp(rel), _dp(p.rel), _dp(p.msg_slot),
+                                    m_pad // CHUNK, _stream(dev)), "dev_plan_fill")
     p.rowptr = rowbuf[: n_rows + 1]
     p.sync_free = sync_free
     p.units = None
@@ -735,7 +753,7 @@ def build_csr_pair_device(a, b, rel, val, alive, n_rows):
     e_other, e_rel = _i32(2 * M, dev), _i32(2 * M, dev)
     e_val = torch.empty(max(2 * M, 1), dtype=torch.float32, device=dev)
     with _on(dev):
-        _check(lib().rgcn_dev_csr_pair(_dp(a), _dp(b), _dp(rel), _dp(val), _dp(alive), c_i64(M), c_i64(n_rows), _dp(rowbuf),
+        _check(lib().rgcn_dev_csr_pair(_dp(a), _dp(b), _dp(rel), _dp(val), _dp(alive), M, n_rows, _dp(rowbuf),
                                        _dp(scan_tmp), _dp(e_other), _dp(e_rel), _dp(e_val), _stream(dev)), "dev_csr_pair")
     out = []
     for k in range(2):
@@ -823,12 +841,12 @@ def fbasis_fwd(table, comps, bias, plan, basis_major=False, relu=False):
     units, n_units, _ = plan.units_src
     with _on(dev), _timed("fbasis_fwd"):
         _check(lib().rgcn_fbasis_fwd_f32(_dp(bases), _dp(comps), _dp(Y), _dp(plan.e_rel), _dp(plan.e_val), _dp(units),
-                                         c_i64(n_units), c_i64(N), c_i32(comps.shape[0]), c_i32(B), c_i32(d),
-                                         c_i32(1 if basis_major else 0), _stream(dev)), "fbasis_fwd")
+                                         n_units, N, comps.shape[0], B, d, 1 if basis_major else 0,
+                                         _stream(dev)), "fbasis_fwd")
         units, n_units, n_split = plan.units_dst
         fused = bool(relu) and n_split == 0
-        _check(lib().rgcn_gather_rows_sum_f32(_dp(Y), _dp(plan.perm_dst), _dp(units), c_i64(n_units), c_i64(n_split),
-                                              _dp(bias), _dp(out), c_i64(N), c_i32(d), c_i32(1 if fused else 0), _stream(dev)), "gather_rows_sum")
+        _check(lib().rgcn_gather_rows_sum_f32(_dp(Y), _dp(plan.perm_dst), _dp(units), n_units, n_split, _dp(bias), _dp(out), N, d,
+                                              1 if fused else 0, _stream(dev)), "gather_rows_sum")
     return (out, fused) if relu else out
 
 
@@ -843,22 +861,22 @@ def fbasis_bwd(table, comps, g, plan, need_bases=True, need_comps=True, basis_ma
     dC = torch.empty(R, B, device=dev, dtype=torch.float32) if need_comps else None
     units, n_units, n_split = plan.units_src
     if need_comps and not routes.flag("deterministic") and \
-            lib().rgcn_fbasis_bwd_dc_supported(c_i32(R), c_i32(B), c_i32(d)):
+            lib().rgcn_fbasis_bwd_dc_supported(R, B, d):
         # dcomps summed in an LDS table of doubles inside the walk: no [M, B] scratch, no second pass
         with _on(dev), _timed("fbasis_bwd"):
             _check(lib().rgcn_fbasis_bwd_dc_f32(_dp(bases), _dp(comps), _dp(g), _dp(dB), _dp(dC), _dp(plan.e_dst), _dp(plan.e_rel),
-                                                _dp(plan.e_val), _dp(units), c_i64(n_units), c_i64(n_split), c_i64(N), c_i32(R),
-                                                c_i32(B), c_i32(d), c_i32(1 if basis_major else 0), _stream(dev)), "fbasis_bwd_dc")
+                                                _dp(plan.e_val), _dp(units), n_units, n_split, N, R, B, d, 1 if basis_major else 0,
+                                                _stream(dev)), "fbasis_bwd_dc")
         return dB, dC
     T = torch.empty(max(plan.n_messages, 1), B, device=dev, dtype=torch.float32) if need_comps else None
     with _on(dev), _timed("fbasis_bwd"):
         _check(lib().rgcn_fbasis_bwd_f32(_dp(bases), _dp(comps), _dp(g), _dp(dB), _dp(T), _dp(plan.e_dst), _dp(plan.e_rel),
-                                         _dp(plan.e_val), _dp(units), c_i64(n_units), c_i64(n_split), c_i64(N), c_i32(R),
-                                         c_i32(B), c_i32(d), c_i32(1 if basis_major else 0), _stream(dev)), "fbasis_bwd")
+                                         _dp(plan.e_val), _dp(units), n_units, n_split, N, R, B, d,
+                                         1 if basis_major else 0, _stream(dev)), "fbasis_bwd")
         if need_comps:
             units, n_units, n_split = plan.units_rel
-            _check(lib().rgcn_gather_rows_sum_f32(_dp(T), _dp(plan.perm_rel), _dp(units), c_i64(n_units), c_i64(n_split),
-                                                  None, _dp(dC), c_i64(R), c_i32(B), c_i32(0), _stream(dev)), "gather_rows_sum")
+            _check(lib().rgcn_gather_rows_sum_f32(_dp(T), _dp(plan.perm_rel), _dp(units), n_units, n_split, None, _dp(dC), R, B,
+                                                  0, _stream(dev)), "gather_rows_sum")
     return dB, dC
 
 
@@ -873,7 +891,7 @@ def fbasis_tile_ok(R, B, d, n_nodes, max_degree=None):
     route = routes.get("fbasis_tile", "1")
     if route == "0" or routes.flag("deterministic"):
         return False, 0
-    m = lib().rgcn_fbasis_tile_supported(c_i32(R), c_i32(B), c_i32(d), c_i64(n_nodes))
+    m = lib().rgcn_fbasis_tile_supported(R, B, d, n_nodes)
     ranges, nodes = (m & 3) == 3, (m & 12) == 12
     if route == "nodes":
         return nodes, 1
@@ -893,19 +911,18 @@ def fbasis_tile_fwd(bases, comps, bias, plan, relu=False, mode=0, padded=False):
     _req(bases, "bases"); _req(comps, "comps"); _req(bias, "bias")
     B, N, d = bases.shape
     dev = bases.device
-    ys = int(lib().rgcn_fbasis_tile_ystride(c_i32(d)))
+    ys = int(lib().rgcn_fbasis_tile_ystride(d))
     Y = torch.empty(max(plan.n_messages, 1), ys, device=dev, dtype=torch.float32)
     ow = d + (-d % 16) if (padded and d % 16 and d + (-d % 16) <= ys) else d
     out = torch.empty(N, ow, device=dev, dtype=torch.float32)
     with _on(dev), _timed("fbasis_tile_fwd"):
-        _check(lib().rgcn_fbasis_tile_fwd_f32(_dp(bases), _dp(comps), _dp(Y), _dp(plan.rowptr_src), _dp(plan.e_rel), _dp(plan.e_val),
-                                              c_i64(plan.n_messages), c_i64(N), c_i32(comps.shape[0]), c_i32(B), c_i32(d), c_i32(1 if mode else 0), _stream(dev)),
-               "fbasis_tile_fwd")
+        _check(lib().rgcn_fbasis_tile_fwd_f32(_dp(bases), _dp(comps), _dp(Y), _dp(plan.rowptr_src), _dp(plan.e_rel), _dp(plan.e_val), plan.n_messages, N,
+                                              comps.shape[0], B, d, 1 if mode else 0, _stream(dev)), "fbasis_tile_fwd")
     units, n_units, n_split = plan.units_dst
     fused = bool(relu) and n_split == 0
     with _on(dev), _timed("gather_rows_sum4"):
-        _check(lib().rgcn_gather_rows_sum4_f32(_dp(Y), c_i32(ys), _dp(plan.perm_dst), _dp(units), c_i64(n_units), c_i64(n_split),
-                                               _dp(bias), _dp(out), c_i64(N), c_i32(d), c_i32(ow), c_i32(1 if fused else 0), _stream(dev)), "gather_rows_sum4")
+        _check(lib().rgcn_gather_rows_sum4_f32(_dp(Y), ys, _dp(plan.perm_dst), _dp(units), n_units, n_split, _dp(bias), _dp(out), N, d, ow, 1 if fused else 0,
+                                               _stream(dev)), "gather_rows_sum4")
     if ow != d:
         out = out[:, :d]
         out._rgcn_zero_padded = True
@@ -929,9 +946,8 @@ def fbasis_tile_bwd(bases, comps, g, plan, need_bases=True, need_comps=True, mod
     if dB is None and dC is None:
         return None, None
     with _on(dev), _timed("fbasis_tile_bwd"):
-        _check(lib().rgcn_fbasis_tile_bwd_f32(_dp(bases), _dp(comps), _dp(g), c_i32(g_stride), _dp(dB), _dp(dC), _dp(plan.rowptr_src), _dp(plan.e_dst),
-                                              _dp(plan.e_rel), _dp(plan.e_val), c_i64(plan.n_messages), c_i64(N), c_i32(R), c_i32(B), c_i32(d), c_i32(mode),
-                                              _stream(dev)), "fbasis_tile_bwd")
+        _check(lib().rgcn_fbasis_tile_bwd_f32(_dp(bases), _dp(comps), _dp(g), g_stride, _dp(dB), _dp(dC), _dp(plan.rowptr_src), _dp(plan.e_dst),
+                                              _dp(plan.e_rel), _dp(plan.e_val), plan.n_messages, N, R, B, d, mode, _stream(dev)), "fbasis_tile_bwd")
     return dB, dC
 
 
@@ -942,19 +958,17 @@ def fbasis_tile_fwd_bf16(bases, comps, bias, plan, relu=False, mode=0):
     _req(bases, "bases", torch.bfloat16); _req(comps, "comps"); _req(bias, "bias")
     B, N, d = bases.shape
     dev = bases.device
-    ys = int(lib().rgcn_fbasis_tile_ystride(c_i32(d)))
+    ys = int(lib().rgcn_fbasis_tile_ystride(d))
     Y = torch.empty(max(plan.n_messages, 1), ys, device=dev, dtype=torch.float32)
     out = torch.empty(N, d, device=dev, dtype=torch.bfloat16)
     units, n_units, n_split = plan.units_dst
     scratch = torch.empty(N, d, device=dev, dtype=torch.float32) if n_split else None
     with _on(dev), _timed("fbasis_tile_fwd_bf16"):
         _check(lib().rgcn_fbasis_tile_fwd_bf16(_dp(bases), _dp(comps), _dp(Y), _dp(plan.rowptr_src), _dp(plan.e_rel), _dp(plan.e_val),
-                                               c_i64(plan.n_messages), c_i64(N), c_i32(comps.shape[0]), c_i32(B), c_i32(d), c_i32(1 if mode else 0),
-                                               _stream(dev)), "fbasis_tile_fwd_bf16")
+                                               plan.n_messages, N, comps.shape[0], B, d, 1 if mode else 0, _stream(dev)), "fbasis_tile_fwd_bf16")
     with _on(dev), _timed("gather_rows_sum4_bf16"):
-        _check(lib().rgcn_gather_rows_sum4_bf16(_dp(Y), c_i32(ys), _dp(plan.perm_dst), _dp(units), c_i64(n_units), c_i64(n_split), _dp(bias),
-                                                _dp(out), _dp(scratch), c_i64(N), c_i32(d), c_i32(d), c_i32(1 if relu else 0), _stream(dev)),
-               "gather_rows_sum4_bf16")
+        _check(lib().rgcn_gather_rows_sum4_bf16(_dp(Y), ys, _dp(plan.perm_dst), _dp(units), n_units, n_split, _dp(bias), _dp(out),
+                                                _dp(scratch), N, d, d, 1 if relu else 0, _stream(dev)), "gather_rows_sum4_bf16")
     return (out, True) if relu else out
 
 
@@ -976,9 +990,9 @@ def fbasis_tile_bwd_bf16(bases, comps, g, plan, need_bases=True, need_comps=True
     if dB is None and dC is None:
         return None, None
     with _on(dev), _timed("fbasis_tile_bwd_bf16"):
-        _check(lib().rgcn_fbasis_tile_bwd_bf16(_dp(bases), _dp(comps), _dp(g), c_i32(g_stride), _dp(dB), _dp(dC), _dp(plan.rowptr_src),
-                                               _dp(plan.e_dst), _dp(plan.e_rel), _dp(plan.e_val), c_i64(plan.n_messages), c_i64(N), c_i32(R),
-                                               c_i32(B), c_i32(d), c_i32(mode), _stream(dev)), "fbasis_tile_bwd_bf16")
+        _check(lib().rgcn_fbasis_tile_bwd_bf16(_dp(bases), _dp(comps), _dp(g), g_stride, _dp(dB), _dp(dC), _dp(plan.rowptr_src),
+                                               _dp(plan.e_dst), _dp(plan.e_rel), _dp(plan.e_val), plan.n_messages, N, R, B, d, mode,
+                                               _stream(dev)), "fbasis_tile_bwd_bf16")
     return dB, dC
 
 
@@ -987,13 +1001,13 @@ def basis_aggregate(X, comps, csr, B, d, n_b_in):
     out = torch.empty((csr.n_rows, B * d) if n_b_in == 1 else (csr.n_rows, d), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("basis_aggregate"):
         _check(lib().rgcn_basis_aggregate_f32(_dp(X), _dp(comps), _dp(out), _dp(csr.rowptr), _dp(csr.src), _dp(csr.rel),
-                                              _dp(csr.val), c_i64(csr.n_rows), c_i32(comps.shape[0]), c_i32(B), c_i32(d),
-                                              c_i32(n_b_in), _stream(X.device)), "basis_aggregate")
+                                              _dp(csr.val), csr.n_rows, comps.shape[0], B, d, n_b_in,
+                                              _stream(X.device)), "basis_aggregate")
     return out
 
 
 def fbasis_small_ok(R, B, d):
-    return bool(lib().rgcn_fbasis_small_supported(c_i32(R), c_i32(B), c_i32(d)))
+    return bool(lib().rgcn_fbasis_small_supported(R, B, d))
 
 
 def fbasis_small_bwd(G, table, comps, csr, B, d, basis_major=False):
@@ -1006,8 +1020,7 @@ def fbasis_small_bwd(G, table, comps, csr, B, d, basis_major=False):
     dC = torch.empty((R, B), device=G.device, dtype=torch.float32)
     with _on(G.device), _timed("fbasis_small_bwd"):
         _check(lib().rgcn_fbasis_small_bwd_f32(_dp(G), _dp(table), _dp(comps), _dp(dB), _dp(dC), _dp(csr.rowptr), _dp(csr.src), _dp(csr.rel),
-                                               _dp(csr.val), c_i64(csr.n_rows), c_i32(R), c_i32(B), c_i32(d), c_i32(1 if basis_major else 0),
-                                               _stream(G.device)),
+                                               _dp(csr.val), csr.n_rows, R, B, d, 1 if basis_major else 0, _stream(G.device)),
                "fbasis_small_bwd")
     return dB, dC
 
@@ -1021,9 +1034,9 @@ def basis_dcomps(X, D, plan, R, B, d, swap=False):
     dc = torch.empty((copies, R, B), device=X.device, dtype=torch.float32)
     a, b = (plan.dst, plan.src) if swap else (plan.src, plan.dst)
     with _on(X.device), _timed("basis_dcomps"):
-        _check(lib().rgcn_basis_dcomps_f32(_dp(X), _dp(D), _dp(dc), _dp(a), _dp(b), _dp(plan.val),
-                                           _dp(plan.chunk_rel), _dp(plan.items), c_i64(plan.n_items), c_i32(R), c_i32(B),
-                                           c_i32(d), c_i32(copies), _stream(X.device)), "basis_dcomps")
+        _check(lib().rgcn_basis_dcomps_f32(_dp(X), _dp(D), _dp(dc), _dp(a), _dp(b), _dp(plan.val), _dp(plan.chunk_rel),
+                                           _dp(plan.items), plan.n_items, R, B, d, copies,
+                                           _stream(X.device)), "basis_dcomps")
     return dc.sum(0) if copies > 1 else dc[0]
 
 
@@ -1037,7 +1050,7 @@ def _table_workspace(dev, R, B):
     zeroed), replaced by a larger one when a larger table comes along; a capture has its own (the capture stream's, allocated from the
     graph's pool) and a buffer a captured graph may still point at is never released"""
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)      # per stream: two streams' launches would race on the ticket and the partials
-    need = int(lib().rgcn_basis_sum_workspace_bytes(c_i32(R), c_i32(B)))
+    need = int(lib().rgcn_basis_sum_workspace_bytes(R, B))
     ws = _TABLE_WS.get(key)
     if ws is None or ws.numel() < need:
         if ws is not None and torch.cuda.is_current_stream_capturing():
@@ -1047,7 +1060,7 @@ def _table_workspace(dev, R, B):
 
 
 def basis_dcomps_csr_ok(R, B, d):
-    return bool(lib().rgcn_basis_dcomps_csr_supported(c_i32(R), c_i32(B), c_i32(d)))
+    return bool(lib().rgcn_basis_dcomps_csr_supported(R, B, d))
 
 
 def basis_dcomps_csr(X, D, csr, R, B, d):
@@ -1056,7 +1069,7 @@ def basis_dcomps_csr(X, D, csr, R, B, d):
     dc = torch.empty((R, B), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("basis_dcomps_csr"):
         _check(lib().rgcn_basis_dcomps_csr_f32(_dp(X), _dp(D), _dp(dc), _dp(csr.rowptr), _dp(csr.src), _dp(csr.rel), _dp(csr.val),
-                                               c_i64(csr.n_rows), c_i32(R), c_i32(B), c_i32(d), _dp(_table_workspace(X.device, R, B)),
+                                               csr.n_rows, R, B, d, _dp(_table_workspace(X.device, R, B)),
                                                _stream(X.device)), "basis_dcomps_csr")
     return dc
 
@@ -1077,13 +1090,12 @@ def gemm(A, B, bias=None, trans_a=False, trans_b=False, split_k=1):
         return C
     scratch = None
     if split_k > 1:
-        scratch = torch.empty(int(lib().rgcn_gemm_scratch_floats(c_i64(M), c_i64(N), c_i64(K), c_i32(split_k))),
+        scratch = torch.empty(int(lib().rgcn_gemm_scratch_floats(M, N, K, split_k)),
                               device=A.device, dtype=torch.float32)
     flags = (G_TRANS_A if trans_a else 0) | (G_TRANS_B if trans_b else 0)
     with _on(A.device), _timed("gemm"):
-        _check(lib().rgcn_gemm_f32(_dp(A), _dp(B), _dp(bias), _dp(C), _dp(scratch), c_i64(M), c_i64(N), c_i64(K),
-                                   c_i64(A.shape[1]), c_i64(B.shape[1]), c_i64(N), c_i32(flags), c_i32(split_k),
-                                   _stream(A.device)), "gemm")
+        _check(lib().rgcn_gemm_f32(_dp(A), _dp(B), _dp(bias), _dp(C), _dp(scratch), M, N, K, A.shape[1], B.shape[1], N,
+                                   flags, split_k, _stream(A.device)), "gemm")
     return C
 
 
@@ -1148,7 +1160,7 @@ def _packed_w16(W):
             return hit
     Wp, Wtp = torch.empty_like(W), torch.empty_like(W)
     with _on(W.device):
-        _check(lib().rgcn_pack_w16_pair_f32(_dp(W), _dp(Wp), _dp(Wtp), c_i32(W.shape[0]), _stream(W.device)), "pack_w16_pair")
+        _check(lib().rgcn_pack_w16_pair_f32(_dp(W), _dp(Wp), _dp(Wtp), W.shape[0], _stream(W.device)), "pack_w16_pair")
     if sc is not None:
         sc.map[id(W)] = (W, (Wp, Wtp))
     return Wp, Wtp
@@ -1165,16 +1177,15 @@ def _spmm_launch(X, W, bias, plan, out, flags, u0, u1, n_split, tag):
     units = plan.units if u0 == 0 else plan.units[u0:]
     with _on(X.device), _timed(tag):
         _check(lib().rgcn_spmm_f32(_dp(X), _dp(W), _dp(bias), _dp(out), _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                   _dp(plan.pack), _dp(plan.chunk_rel), _dp(units), c_i64(u1 - u0), c_i64(n_split),
-                                   c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src), c_i32(R), c_i32(d_in),
-                                   c_i32(d_out), c_i32(flags), _stream(X.device)), "spmm")
+                                   _dp(plan.pack), _dp(plan.chunk_rel), _dp(units), u1 - u0, n_split, plan.tile_rows,
+                                   plan.n_dst, plan.n_src, R, d_in, d_out, flags, _stream(X.device)), "spmm")
 
 
 def pack_w_blocks(W):
     """[R, 16 NI, 16 NJ] weights -> per-(input block, output block) MFMA fragments for the wide spmm kernel"""
     Wp = torch.empty_like(W)
     with _on(W.device):
-        _check(lib().rgcn_pack_w_blocks_f32(_dp(W), _dp(Wp), c_i32(W.shape[0]), c_i32(W.shape[1]), c_i32(W.shape[2]),
+        _check(lib().rgcn_pack_w_blocks_f32(_dp(W), _dp(Wp), W.shape[0], W.shape[1], W.shape[2],
                                             _stream(W.device)), "pack_w_blocks")
     return Wp
 
@@ -1254,11 +1265,11 @@ def _segment_gather_sum(Y, perm, csr, bias, out, relu):
     than 512 entries) go over work units -- the pieces of a hub row merge with atomics; returns whether a ReLU is still owed"""
     units, n_units, n_split = _csr_units(csr)
     if units is not None and n_split:
-        _check(lib().rgcn_segment_gather_sum_units_f32(_dp(Y), _dp(perm), _dp(units), c_i64(n_units), c_i64(n_split), _dp(bias), _dp(out),
-                                                       c_i64(csr.n_rows), c_i32(16), c_i32(0), _stream(Y.device)), "segment_gather_sum_units")
+        _check(lib().rgcn_segment_gather_sum_units_f32(_dp(Y), _dp(perm), _dp(units), n_units, n_split, _dp(bias), _dp(out), csr.n_rows, 16,
+                                                       0, _stream(Y.device)), "segment_gather_sum_units")
         return relu
-    _check(lib().rgcn_segment_gather_sum_f32(_dp(Y), _dp(perm), _dp(csr.rowptr), _dp(bias), _dp(out), c_i64(csr.n_rows), c_i32(16),
-                                             c_i32(F_RELU if relu else 0), _stream(Y.device)), "segment_gather_sum")
+    _check(lib().rgcn_segment_gather_sum_f32(_dp(Y), _dp(perm), _dp(csr.rowptr), _dp(bias), _dp(out), csr.n_rows, 16,
+                                             F_RELU if relu else 0, _stream(Y.device)), "segment_gather_sum")
     return False
 
 
@@ -1279,14 +1290,14 @@ def spmm_two_pass(X, W, bias, scatter_plan, csr, relu=False):
         Y = torch.empty((max(n_msg, 1), 16), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("spmm_scatter"):
         _check(lib().rgcn_spmm_scatter_f32(_dp(X), _dp(Wp), _dp(Y), _dp(p.src), _dp(p.val), None if gather else _dp(p.aux),
-                                           _dp(p.chunk_rel), _dp(p.items), c_i64(p.n_items), c_i32(16), _stream(X.device)),
+                                           _dp(p.chunk_rel), _dp(p.items), p.n_items, 16, _stream(X.device)),
                "spmm_scatter")
     with _on(X.device), _timed("segment_sum"):
         if gather:
             relu = _segment_gather_sum(Y, p._inv, csr, bias, out, relu)
         else:
-            _check(lib().rgcn_segment_sum_f32(_dp(Y), _dp(csr.rowptr), _dp(bias), _dp(out), c_i64(csr.n_rows), c_i32(16),
-                                              c_i32(F_RELU if relu else 0), _stream(X.device)), "segment_sum")
+            _check(lib().rgcn_segment_sum_f32(_dp(Y), _dp(csr.rowptr), _dp(bias), _dp(out), csr.n_rows, 16,
+                                              F_RELU if relu else 0, _stream(X.device)), "segment_sum")
             relu = False
     return out.relu_() if relu else out
 
@@ -1303,11 +1314,10 @@ def spmm_wide_two_pass(X, W, bias, scatter_plan, csr, relu=False):
     out = torch.empty((csr.n_rows, d_out), device=dev, dtype=torch.float32)
     with _on(dev), _timed("rel_rows"):
         _check(lib().rgcn_rel_rows_f32(_dp(X), _dp(W), _dp(Y), _dp(p.src), _dp(p.val), _dp(p.chunk_rel), _dp(p.items),
-                                       c_i64(p.n_items), c_i32(R), c_i32(d_in), c_i32(d_out), _stream(dev)), "rel_rows")
+                                       p.n_items, R, d_in, d_out, _stream(dev)), "rel_rows")
     with _on(dev), _timed("segment_sum_wide"):
-        _check(lib().rgcn_segment_gather_sum_wide_f32(_dp(Y), _dp(perm), _dp(csr.rowptr), _dp(bias), _dp(out), c_i64(csr.n_rows),
-                                                      c_i32(d_out), c_i32(F_RELU if relu else 0), _stream(dev)),
-               "segment_gather_sum_wide")
+        _check(lib().rgcn_segment_gather_sum_wide_f32(_dp(Y), _dp(perm), _dp(csr.rowptr), _dp(bias), _dp(out), csr.n_rows, d_out,
+                                                      F_RELU if relu else 0, _stream(dev)), "segment_gather_sum_wide")
     return out
 
 
@@ -1318,7 +1328,7 @@ def wgrad_wide(X, G, scatter_plan, num_rels):
     dW = torch.empty((num_rels, X.shape[1], G.shape[1]), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("rel_wgrad"):
         _check(lib().rgcn_rel_wgrad_f32(_dp(X), _dp(G), _dp(dW), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
-                                        _dp(p.items), c_i64(p.n_items), c_i32(num_rels), c_i32(X.shape[1]), c_i32(G.shape[1]),
+                                        _dp(p.items), p.n_items, num_rels, X.shape[1], G.shape[1],
                                         _stream(X.device)), "rel_wgrad")
     return dW
 
@@ -1338,8 +1348,8 @@ def bwd_two_pass_fused(G, X, W, scatter_plan, csr, relu=False):
     dX = torch.empty((csr.n_rows, 16), device=dev, dtype=torch.float32)
     with _on(dev), _timed("bwd_scatter_dw"):
         _check(lib().rgcn_bwd_scatter_dw_f32(_dp(G), _dp(X), _dp(Wtp), _dp(Y), _dp(dW), _dp(p.src), _dp(p.dst), _dp(p.val),
-                                             _dp(p.chunk_rel), _dp(p.items), c_i64(p.n_items), c_i32(W.shape[0]), c_i32(16),
-                                             c_i32(F_RELU if relu else 0), _stream(dev)), "bwd_scatter_dw")
+                                             _dp(p.chunk_rel), _dp(p.items), p.n_items, W.shape[0], 16,
+                                             F_RELU if relu else 0, _stream(dev)), "bwd_scatter_dw")
     with _on(dev), _timed("segment_sum"):
         _segment_gather_sum(Y, p._inv, csr, None, dX, False)
     return dX, dW
@@ -1353,9 +1363,8 @@ def wgrad(X, G, plan, num_rels):
     dW = torch.empty((num_rels, d_in, d_out), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("wgrad"):
         _check(lib().rgcn_wgrad_f32(_dp(X), _dp(G), _dp(dW), _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                    _dp(plan.chunk_rel), _dp(plan.items), c_i64(plan.n_items), c_i64(plan.n_dst),
-                                    c_i64(plan.n_src), c_i32(num_rels), c_i32(d_in), c_i32(d_out),
-                                    _stream(X.device)), "wgrad")
+                                    _dp(plan.chunk_rel), _dp(plan.items), plan.n_items, plan.n_dst, plan.n_src,
+                                    num_rels, d_in, d_out, _stream(X.device)), "wgrad")
     return dW
 
 
@@ -1366,10 +1375,9 @@ def wgrad_tiled(X, G, plan, num_rels, tiles_per_item=4):
     dW = torch.empty((num_rels, X.shape[1], G.shape[1]), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("wgrad"):
         _check(lib().rgcn_wgrad_tiled_f32(_dp(X), _dp(G), _dp(dW), _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                          _dp(plan.chunk_rel), _dp(plan.run_ptr), c_i64(plan.n_tiles),
-                                          c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src),
-                                          c_i32(num_rels), c_i32(X.shape[1]), c_i32(G.shape[1]),
-                                          c_i32(tiles_per_item), _stream(X.device)), "wgrad_tiled")
+                                          _dp(plan.chunk_rel), _dp(plan.run_ptr), plan.n_tiles, plan.tile_rows,
+                                          plan.n_dst, plan.n_src, num_rels, X.shape[1], G.shape[1], tiles_per_item,
+                                          _stream(X.device)), "wgrad_tiled")
     return dW
 
 
@@ -1399,7 +1407,7 @@ def bwd_blk_rows(n_nodes, num_rels, deterministic=False, device=None, diag4=Fals
     diag4: the weights are block_diag() of 4 x 4 blocks (only the diagonal blocks of dW are kept: AM's 267 relations leave 406 rows)"""
     if bwd_route() != "blk" or deterministic or n_nodes < (_BLK_MIN_NODES_SPARSE if sparse else _BLK_MIN_NODES):
         return 0
-    cap = int(lib().rgcn_bwd_blk_max_rows(c_i32(num_rels), c_i32(F_DIAG4 if diag4 else 0)))
+    cap = int(lib().rgcn_bwd_blk_max_rows(num_rels, F_DIAG4 if diag4 else 0))
     cap = min(cap, int(routes.get("bwd_blk_cap", "512")))
     if cap < 64:
         return 0
@@ -1439,9 +1447,9 @@ def spmm_blk(X, W, bias, plan, relu=False):
     if relu and n_split:
         raise NativeLibraryError("spmm_blk: relu in the epilogue needs a plan without hub pieces")
     with _on(dev), _timed("spmm_blk"):
-        _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(rec), _dp(plan.run_ptr), c_i64(plan.n_tiles),
-                                       c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]), c_i32(F_RELU if relu else 0),
-                                       _dp(units), c_i64(n_units), c_i64(n_split), _stream(dev)), "spmm_blk")
+        _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
+                                       plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(units), n_units,
+                                       n_split, _stream(dev)), "spmm_blk")
     return out
 
 
@@ -1458,8 +1466,8 @@ def spmm_bf16(X, W, bias, plan, relu=False):
     fused = relu and not plan.n_split
     with _on(X.device), _timed("spmm_bf16"):
         _check(lib().rgcn_spmm_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(plan.pack), _dp(plan.chunk_rel), _dp(plan.units),
-                                    c_i64(plan.n_units), c_i64(plan.n_split), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src),
-                                    c_i32(d_in), c_i32(d_out), c_i32(F_RELU if fused else 0), _stream(X.device)), "spmm_bf16")
+                                    plan.n_units, plan.n_split, plan.tile_rows, plan.n_dst, plan.n_src, d_in, d_out, F_RELU if fused else 0,
+                                    _stream(X.device)), "spmm_bf16")
     return torch.relu_(out) if (relu and not fused) else out
 
 
@@ -1470,8 +1478,7 @@ def wgrad_bf16(X, G, plan, num_rels):
     dW = torch.empty((num_rels, d_in, d_out), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("wgrad_bf16"):
         _check(lib().rgcn_wgrad_bf16(_dp(X), _dp(G), _dp(dW), _dp(plan.src), _dp(plan.dst), _dp(plan.val), _dp(plan.chunk_rel),
-                                     _dp(plan.items), c_i64(plan.n_items), c_i32(num_rels), c_i32(d_in), c_i32(d_out),
-                                     _stream(X.device)), "wgrad_bf16")
+                                     _dp(plan.items), plan.n_items, num_rels, d_in, d_out, _stream(X.device)), "wgrad_bf16")
     return dW
 
 
@@ -1479,9 +1486,9 @@ def colsum_bf16(G):
     """db [d] fp32 = column sums of bf16 G (rgcn_colsum_bf16; any width)"""
     _req(G, "grad_output", torch.bfloat16)
     db = torch.empty(G.shape[1], device=G.device, dtype=torch.float32)
-    scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(c_i64(G.shape[0]), c_i32(G.shape[1]))), device=G.device, dtype=torch.float32)
+    scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(G.shape[0], G.shape[1])), device=G.device, dtype=torch.float32)
     with _on(G.device), _timed("colsum_bf16"):
-        _check(lib().rgcn_colsum_bf16(_dp(G), _dp(db), _dp(scratch), c_i64(G.shape[0]), c_i32(G.shape[1]), _stream(G.device)), "colsum_bf16")
+        _check(lib().rgcn_colsum_bf16(_dp(G), _dp(db), _dp(scratch), G.shape[0], G.shape[1], _stream(G.device)), "colsum_bf16")
     return db
 
 
@@ -1499,15 +1506,15 @@ def spmm_blk_bf16(X, W, bias, plan, relu=False):
         raise NativeLibraryError("spmm_blk_bf16: relu in the epilogue needs a plan without hub pieces")
     scratch = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.float32) if n_split else None
     with _on(dev), _timed("spmm_blk_bf16"):
-        _check(lib().rgcn_spmm_blk_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(rec), _dp(plan.run_ptr), c_i64(plan.n_tiles),
-                                        c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i64(plan.n_src), c_i32(W.shape[0]),
-                                        c_i32(F_RELU if relu else 0), _dp(units), c_i64(n_units), c_i64(n_split), _stream(dev)), "spmm_blk_bf16")
+        _check(lib().rgcn_spmm_blk_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
+                                        plan.tile_rows, plan.n_dst, plan.n_src, W.shape[0], F_RELU if relu else 0, _dp(units), n_units, n_split,
+                                        _stream(dev)), "spmm_blk_bf16")
     return out
 
 
 def _bwd_blk_plan(plan, diag4=False):
     return (plan.tile_rows > 160 or (plan.tile_rows > 64 and bwd_route() == "blk")) and \
-        bool(lib().rgcn_bwd_blk_supported(c_i32(plan.tile_rows), c_i32(plan.num_rels), c_i32(F_DIAG4 if diag4 else 0)))
+        bool(lib().rgcn_bwd_blk_supported(plan.tile_rows, plan.num_rels, F_DIAG4 if diag4 else 0))
 
 
 def bwd_fused_ok(plan, diag4=False):
@@ -1521,7 +1528,7 @@ def bwd_fused_ok(plan, diag4=False):
     # (the lean window kernel: its LDS holds the dX tile + X tile + scratch of at least 8 waves; round 2's staging kernel, which took the
     # taller wave-owned tiles up to 160 rows, is gone -- such plans only come from experimental routes and take the two-pass backward)
     return plan.pack is not None and plan.n_split == 0 and plan.n_units == plan.n_tiles and \
-        bool(lib().rgcn_bwd_lean_supported(c_i32(plan.tile_rows))) and plan.num_rels < 65536
+        bool(lib().rgcn_bwd_lean_supported(plan.tile_rows)) and plan.num_rels < 65536
 
 
 def _blk_units(plan):
@@ -1548,15 +1555,15 @@ def _lean_plan(plan):
     if lean is None:
         n_chunks = plan.chunk_rel.shape[0]
         dev = plan.chunk_rel.device
-        slots = torch.empty(int(lib().rgcn_bwd_lean_slot_bytes(c_i64(n_chunks))) + 16, device=dev, dtype=torch.uint8)
+        slots = torch.empty(int(lib().rgcn_bwd_lean_slot_bytes(n_chunks)) + 16, device=dev, dtype=torch.uint8)
         hdr = torch.empty(max(n_chunks, 1), device=dev, dtype=torch.int32)
         with _on(dev):
             if plan.pack is not None:
-                _check(lib().rgcn_bwd_lean_prepare_f32(_dp(plan.pack), _dp(plan.chunk_rel), c_i64(n_chunks), _dp(slots), _dp(hdr), _stream(dev)),
+                _check(lib().rgcn_bwd_lean_prepare_f32(_dp(plan.pack), _dp(plan.chunk_rel), n_chunks, _dp(slots), _dp(hdr), _stream(dev)),
                        "bwd_lean_prepare")
             else:
-                _check(lib().rgcn_bwd_lean_prepare_unpacked_f32(_dp(plan.src), _dp(plan.dst), _dp(plan.val), c_i32(plan.tile_rows),
-                                                                _dp(plan.chunk_rel), c_i64(n_chunks), _dp(slots), _dp(hdr), _stream(dev)),
+                _check(lib().rgcn_bwd_lean_prepare_unpacked_f32(_dp(plan.src), _dp(plan.dst), _dp(plan.val), plan.tile_rows,
+                                                                _dp(plan.chunk_rel), n_chunks, _dp(slots), _dp(hdr), _stream(dev)),
                        "bwd_lean_prepare_unpacked")
         lean = plan._lean = (slots, hdr)
     return lean
@@ -1569,11 +1576,11 @@ def _blk_rec(plan):
     if rec is None:
         n_chunks = plan.chunk_rel.shape[0]
         dev = plan.chunk_rel.device
-        rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(c_i64(n_chunks))) + 16, device=dev, dtype=torch.uint8)
+        rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(n_chunks)) + 16, device=dev, dtype=torch.uint8)
         packed = plan.pack is not None and plan.tile_rows <= 255
         with _on(dev):
             _check(lib().rgcn_bwd_blk_prepare_f32(_dp(plan.pack) if packed else None, _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                                  c_i32(plan.tile_rows), _dp(plan.chunk_rel), c_i64(n_chunks), _dp(rec), _stream(dev)),
+                                                  plan.tile_rows, _dp(plan.chunk_rel), n_chunks, _dp(rec), _stream(dev)),
                    "bwd_blk_prepare")
         plan._blk_rec = rec
     return rec
@@ -1612,8 +1619,8 @@ def bwd_own(G, X, W, plan, relu=False, want_db=False):
     rec = _blk_rec(plan)
     with _on(dev), _timed("bwd_fused"):
         _check(lib().rgcn_bwd_own_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel),
-                                      c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
-                                      c_i32(F_RELU if relu else 0), _dp(db) if want_db else None, c_i64(plan.n_src), _stream(dev)), "bwd_own")
+                                      plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0,
+                                      _dp(db) if want_db else None, plan.n_src, _stream(dev)), "bwd_own")
     return (dX, dW, db if want_db else None)
 
 
@@ -1629,9 +1636,9 @@ def bwd_own_bf16(G, X, W, plan, relu=False, want_db=False):
     dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
     rec = _blk_rec(plan)
     with _on(dev), _timed("bwd_own_bf16"):
-        _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel),
-                                       c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
-                                       c_i32(F_RELU if relu else 0), _dp(db) if want_db else None, c_i64(plan.n_src), _stream(dev)), "bwd_own_bf16")
+        _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel), plan.n_tiles,
+                                       plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(db) if want_db else None, plan.n_src,
+                                       _stream(dev)), "bwd_own_bf16")
     return (dX, dW, db if want_db else None)
 
 
@@ -1663,7 +1670,7 @@ def bwd_fused(G, X, W, plan, atomic=False, relu=False, want_db=False, diag4=Fals
     ret = (lambda: (dX, dW, db)) if want_db else (lambda: (dX, dW))
     scratch = None
     if not atomic:
-        n = int(lib().rgcn_bwd_fused_scratch_floats(c_i64(plan.n_tiles), c_i32(W.shape[0])))
+        n = int(lib().rgcn_bwd_fused_scratch_floats(plan.n_tiles, W.shape[0]))
         scratch = torch.empty(n, device=dev, dtype=torch.float32)
     if blk:     # a plan of tall tiles (graph.bwd_plan asked bwd_blk_rows): one tile per workgroup
         if not atomic:
@@ -1671,19 +1678,18 @@ def bwd_fused(G, X, W, plan, atomic=False, relu=False, want_db=False, diag4=Fals
         rec = _blk_rec(plan)
         units, n_units, n_split = _blk_units(plan)
         with _on(dev), _timed("bwd_fused"):
-            _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.run_ptr),
-                                          c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
-                                          c_i32((F_RELU if relu else 0) | (F_DIAG4 if diag4 else 0)), _dp(db), c_i64(plan.n_src),
-                                          _dp(units), c_i64(n_units), c_i64(n_split), _stream(dev)), "bwd_blk")
+            _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
+                                          plan.tile_rows, plan.n_dst, W.shape[0],
+                                          (F_RELU if relu else 0) | (F_DIAG4 if diag4 else 0), _dp(db), plan.n_src, _dp(units),
+                                          n_units, n_split, _stream(dev)), "bwd_blk")
         return ret()
-    if not (lib().rgcn_bwd_lean_supported(c_i32(plan.tile_rows)) and W.shape[0] < 65536):
+    if not (lib().rgcn_bwd_lean_supported(plan.tile_rows) and W.shape[0] < 65536):
         raise NativeLibraryError(f"bwd_fused: no fused kernel for wave-owned tiles of {plan.tile_rows} rows (bwd_fused_ok)")
     slots, hdr = _lean_plan(plan)
     with _on(dev), _timed("bwd_fused"):
         _check(lib().rgcn_bwd_lean_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(scratch), _dp(slots), _dp(hdr),
-                                       _dp(plan.run_ptr), c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst),
-                                       c_i32(W.shape[0]), c_i32((F_DW_ATOMIC if atomic else 0) | (1 if relu else 0)),
-                                       _stream(dev)), "bwd_lean")
+                                       _dp(plan.run_ptr), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0],
+                                       (F_DW_ATOMIC if atomic else 0) | (1 if relu else 0), _stream(dev)), "bwd_lean")
     return ret()
 
 
@@ -1711,10 +1717,10 @@ def bwd_fused_slabs(G, X, W, plan, n_slabs, after_slab):
     cuts = sorted({(plan.n_tiles * k) // n_slabs for k in range(n_slabs + 1)})
     for i, (ta, tb) in enumerate(zip(cuts[:-1], cuts[1:])):
         with _on(dev), _timed("bwd_fused"):
-            _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.run_ptr),
-                                          c_i64(plan.n_tiles), c_i32(plan.tile_rows), c_i64(plan.n_dst), c_i32(W.shape[0]),
-                                          c_i32(F_PARTIAL if i == 0 else F_ACCUMULATE), _dp(db) if i == 0 else None, c_i64(plan.n_src),
-                                          c_void_p(tiles.data_ptr() + 16 * ta), c_i64(tb - ta), c_i64(0), _stream(dev)), "bwd_blk")
+            _check(lib().rgcn_bwd_blk_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
+                                          plan.tile_rows, plan.n_dst, W.shape[0], F_PARTIAL if i == 0 else F_ACCUMULATE,
+                                          _dp(db) if i == 0 else None, plan.n_src, tiles.data_ptr() + 16 * ta, tb - ta, 0,
+                                          _stream(dev)), "bwd_blk")
         after_slab(dX, ta * plan.tile_rows, min(plan.n_dst, tb * plan.tile_rows))
     return dX, dW, db
 
@@ -1726,11 +1732,9 @@ def featureless_fwd(table, bias, plan):
     assert R == plan.num_rels and n_src == plan.n_src
     out = torch.empty((plan.n_dst, d), device=table.device, dtype=torch.float32)
     with _on(table.device), _timed("featureless_fwd"):
-        _check(lib().rgcn_featureless_fwd_f32(_dp(table), _dp(bias), _dp(out), _dp(plan.src), _dp(plan.dst),
-                                              _dp(plan.val), _dp(plan.chunk_rel), _dp(plan.units),
-                                              c_i64(plan.n_units), c_i64(plan.n_split), c_i32(plan.tile_rows), c_i64(plan.n_dst),
-                                              c_i64(n_src), c_i32(R), c_i32(d), _stream(table.device)),
-               "featureless_fwd")
+        _check(lib().rgcn_featureless_fwd_f32(_dp(table), _dp(bias), _dp(out), _dp(plan.src), _dp(plan.dst), _dp(plan.val),
+                                              _dp(plan.chunk_rel), _dp(plan.units), plan.n_units, plan.n_split, plan.tile_rows,
+                                              plan.n_dst, n_src, R, d, _stream(table.device)), "featureless_fwd")
     return out
 
 
@@ -1744,9 +1748,9 @@ def featureless_csr_fwd(table, bias, csr, relu=False):
     out = torch.empty((csr.n_rows, d), device=table.device, dtype=torch.float32)
     fused = bool(relu) and n_split == 0          # relu in the epilogue unless hub rows are cut into shared pieces
     with _on(table.device), _timed("featureless_csr_fwd"):
-        _check(lib().rgcn_featureless_csr_fwd_f32(_dp(table), _dp(bias), _dp(out), _dp(units), c_i64(n_units), c_i64(n_split),
-                                                  _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i64(n_src),
-                                                  c_i32(R), c_i32(d), c_i32(1 if fused else 0), _stream(table.device)), "featureless_csr_fwd")
+        _check(lib().rgcn_featureless_csr_fwd_f32(_dp(table), _dp(bias), _dp(out), _dp(units), n_units, n_split, _dp(csr.src), _dp(csr.rel),
+                                                  _dp(csr.val), csr.n_rows, n_src, R, d, 1 if fused else 0,
+                                                  _stream(table.device)), "featureless_csr_fwd")
     return (out, fused) if relu else out
 
 
@@ -1759,7 +1763,7 @@ def featureless_csr_wgrad(G, csr, num_rels, n_src):
     dT = torch.empty((num_rels, n_src, d), device=G.device, dtype=torch.float32)
     with _on(G.device), _timed("featureless_csr_wgrad"):
         _check(lib().rgcn_featureless_csr_wgrad_f32(_dp(G), _dp(dT), _dp(csr.rowptr), _dp(csr.src), _dp(csr.rel), _dp(csr.val),
-                                                    c_i64(csr.n_entries), c_i64(csr.n_rows), c_i64(n_src), c_i32(num_rels), c_i32(d),
+                                                    csr.n_entries, csr.n_rows, n_src, num_rels, d,
                                                     _stream(G.device)), "featureless_csr_wgrad")
     return dT
 
@@ -1788,7 +1792,7 @@ def _empty_csr_out(csr, width, bias, relu, device):
 
 
 def block_supported(bi, bo):
-    return bool(lib().rgcn_block_supported(c_i32(bi), c_i32(bo)))
+    return bool(lib().rgcn_block_supported(bi, bo))
 
 
 def block_spmm(X, blocks, bias, csr, transposed=False, relu=False):
@@ -1805,9 +1809,9 @@ def block_spmm(X, blocks, bias, csr, transposed=False, relu=False):
     out = torch.empty((csr.n_rows, nb * (bi if transposed else bo)), device=X.device, dtype=torch.float32)
     flags = (F_TRANSPOSE_W if transposed else 0) | (F_RELU if fuse_relu else 0)
     with _on(X.device), _timed("block_spmm"):
-        _check(lib().rgcn_block_spmm_f32(_dp(X), _dp(blocks), _dp(bias), _dp(out), _dp(units), _dp(csr.rowptr), c_i64(n_units),
-                                         c_i64(n_split), _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i32(Rb),
-                                         c_i32(nb), c_i32(bi), c_i32(bo), c_i32(flags), _stream(X.device)), "block_spmm")
+        _check(lib().rgcn_block_spmm_f32(_dp(X), _dp(blocks), _dp(bias), _dp(out), _dp(units), _dp(csr.rowptr), n_units,
+                                         n_split, _dp(csr.src), _dp(csr.rel), _dp(csr.val), csr.n_rows, Rb, nb, bi, bo, flags,
+                                         _stream(X.device)), "block_spmm")
     if relu and not fuse_relu:
         out.relu_()
     return out
@@ -1817,7 +1821,7 @@ def spmm_csr_d16_ok(csr, R):
     """dense 16 x 16 weights on the destination-major CSR in one pass: the table of R relations has to fit the LDS (R <= 120) and
     the CSR needs its work units (static graphs)"""
     return not getattr(csr, "sync_free", False) and not getattr(csr, "per_call", False) and \
-        bool(lib().rgcn_spmm_csr_d16_supported(c_i32(R)))
+        bool(lib().rgcn_spmm_csr_d16_supported(R))
 
 
 def spmm_csr_d16(X, W, bias, csr, relu=False):
@@ -1832,9 +1836,9 @@ def spmm_csr_d16(X, W, bias, csr, relu=False):
     fuse_relu = relu and n_split == 0
     out = torch.empty((csr.n_rows, 16), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("spmm_csr"):
-        _check(lib().rgcn_spmm_csr_d16_f32(_dp(X), _dp(W), _dp(bias), _dp(out), _dp(units), c_i64(n_units), c_i64(n_split),
-                                           _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i32(W.shape[0]),
-                                           c_i32(F_RELU if fuse_relu else 0), _stream(X.device)), "spmm_csr_d16")
+        _check(lib().rgcn_spmm_csr_d16_f32(_dp(X), _dp(W), _dp(bias), _dp(out), _dp(units), n_units, n_split, _dp(csr.src),
+                                           _dp(csr.rel), _dp(csr.val), csr.n_rows, W.shape[0], F_RELU if fuse_relu else 0,
+                                           _stream(X.device)), "spmm_csr_d16")
     if relu and not fuse_relu:
         out.relu_()
     return out
@@ -1848,8 +1852,7 @@ def block_wgrad(X, G, scatter_plan, shape):
     dB = torch.empty(shape, device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("block_wgrad"):
         _check(lib().rgcn_block_wgrad_f32(_dp(X), _dp(G), _dp(dB), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
-                                          _dp(p.items), c_i64(p.n_items), c_i32(Rb), c_i32(nb), c_i32(bi), c_i32(bo),
-                                          _stream(X.device)), "block_wgrad")
+                                          _dp(p.items), p.n_items, Rb, nb, bi, bo, _stream(X.device)), "block_wgrad")
     return dB
 
 
@@ -1862,9 +1865,8 @@ def diag_spmm(X, w, bias, csr):
     assert units is not None, "the diagonal layer is not part of the sync-free LP step"
     out = torch.empty((csr.n_rows, d), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("diag_spmm"):
-        _check(lib().rgcn_diag_spmm_f32(_dp(X), _dp(w), _dp(bias), _dp(out), _dp(units), c_i64(n_units), c_i64(n_split),
-                                        _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i32(R), c_i32(d),
-                                        _stream(X.device)), "diag_spmm")
+        _check(lib().rgcn_diag_spmm_f32(_dp(X), _dp(w), _dp(bias), _dp(out), _dp(units), n_units, n_split, _dp(csr.src),
+                                        _dp(csr.rel), _dp(csr.val), csr.n_rows, R, d, _stream(X.device)), "diag_spmm")
     return out
 
 
@@ -1875,8 +1877,7 @@ def diag_wgrad(X, G, scatter_plan, num_rels):
     dw = torch.empty((num_rels, d), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("diag_wgrad"):
         _check(lib().rgcn_diag_wgrad_f32(_dp(X), _dp(G), _dp(dw), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
-                                         _dp(p.items), c_i64(p.n_items), c_i32(num_rels), c_i32(d), _stream(X.device)),
-               "diag_wgrad")
+                                         _dp(p.items), p.n_items, num_rels, d, _stream(X.device)), "diag_wgrad")
     return dw
 
 
@@ -1886,19 +1887,18 @@ def featureless_wgrad(G, plan, num_rels):
     dT = torch.empty((num_rels, plan.n_src, d), device=G.device, dtype=torch.float32)
     with _on(G.device), _timed("featureless_wgrad"):
         _check(lib().rgcn_featureless_wgrad_f32(_dp(G), _dp(dT), _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                                _dp(plan.chunk_rel), c_i64(plan.n_chunks), c_i64(plan.n_dst),
-                                                c_i64(plan.n_src), c_i32(num_rels), c_i32(d), _stream(G.device)),
-               "featureless_wgrad")
+                                                _dp(plan.chunk_rel), plan.n_chunks, plan.n_dst, plan.n_src, num_rels, d,
+                                                _stream(G.device)), "featureless_wgrad")
     return dT
 
 
 def colsum(G):
     _req(G, "grad_output")
     db = torch.empty(G.shape[1], device=G.device, dtype=torch.float32)
-    scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(c_i64(G.shape[0]), c_i32(G.shape[1]))), device=G.device,
+    scratch = torch.empty(int(lib().rgcn_colsum_scratch_floats(G.shape[0], G.shape[1])), device=G.device,
                           dtype=torch.float32)
     with _on(G.device), _timed("colsum"):
-        _check(lib().rgcn_colsum_f32(_dp(G), _dp(db), _dp(scratch), c_i64(G.shape[0]), c_i32(G.shape[1]),
+        _check(lib().rgcn_colsum_f32(_dp(G), _dp(db), _dp(scratch), G.shape[0], G.shape[1],
                                      _stream(G.device)), "colsum")
     return db
 
@@ -1920,9 +1920,9 @@ def block_spmm_bf16(X, blocks, bias, csr, transposed=False, relu=False, out_f32=
     scratch = torch.empty((csr.n_rows, width), device=X.device, dtype=torch.float32) if (out_f32 or n_split) else None
     flags = (F_TRANSPOSE_W if transposed else 0) | (F_RELU if fuse_relu else 0)
     with _on(X.device), _timed("block_spmm_bf16"):
-        _check(lib().rgcn_block_spmm_bf16(_dp(X), _dp(blocks), _dp(bias), _dp(out), _dp(scratch), _dp(units), _dp(csr.rowptr),
-                                          c_i64(n_units), c_i64(n_split), _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows),
-                                          c_i32(Rb), c_i32(nb), c_i32(bi), c_i32(bo), c_i32(flags), _stream(X.device)), "block_spmm_bf16")
+        _check(lib().rgcn_block_spmm_bf16(_dp(X), _dp(blocks), _dp(bias), _dp(out), _dp(scratch), _dp(units), _dp(csr.rowptr), n_units,
+                                          n_split, _dp(csr.src), _dp(csr.rel), _dp(csr.val), csr.n_rows, Rb, nb, bi, bo, flags,
+                                          _stream(X.device)), "block_spmm_bf16")
     res = scratch if out_f32 else out
     return res.relu_() if (relu and not fuse_relu) else res
 
@@ -1935,7 +1935,7 @@ def block_wgrad_bf16(X, G, scatter_plan, shape):
     dB = torch.empty(shape, device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("block_wgrad_bf16"):
         _check(lib().rgcn_block_wgrad_bf16(_dp(X), _dp(G), _dp(dB), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
-                                           _dp(p.items), c_i64(p.n_items), c_i32(Rb), c_i32(nb), c_i32(bi), c_i32(bo),
+                                           _dp(p.items), p.n_items, Rb, nb, bi, bo,
                                            _stream(X.device)), "block_wgrad_bf16")
     return dB
 
@@ -1950,9 +1950,8 @@ def diag_spmm_bf16(X, w, bias, csr):
     out = torch.empty((csr.n_rows, d), device=X.device, dtype=torch.bfloat16)
     scratch = torch.empty((csr.n_rows, d), device=X.device, dtype=torch.float32) if n_split else None
     with _on(X.device), _timed("diag_spmm_bf16"):
-        _check(lib().rgcn_diag_spmm_bf16(_dp(X), _dp(w), _dp(bias), _dp(out), _dp(scratch), _dp(units), c_i64(n_units), c_i64(n_split),
-                                         _dp(csr.src), _dp(csr.rel), _dp(csr.val), c_i64(csr.n_rows), c_i32(R), c_i32(d),
-                                         _stream(X.device)), "diag_spmm_bf16")
+        _check(lib().rgcn_diag_spmm_bf16(_dp(X), _dp(w), _dp(bias), _dp(out), _dp(scratch), _dp(units), n_units, n_split, _dp(csr.src),
+                                         _dp(csr.rel), _dp(csr.val), csr.n_rows, R, d, _stream(X.device)), "diag_spmm_bf16")
     return out
 
 
@@ -1963,8 +1962,7 @@ def diag_wgrad_bf16(X, G, scatter_plan, num_rels):
     dw = torch.empty((num_rels, d), device=X.device, dtype=torch.float32)
     with _on(X.device), _timed("diag_wgrad_bf16"):
         _check(lib().rgcn_diag_wgrad_bf16(_dp(X), _dp(G), _dp(dw), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel),
-                                          _dp(p.items), c_i64(p.n_items), c_i32(num_rels), c_i32(d), _stream(X.device)),
-               "diag_wgrad_bf16")
+                                          _dp(p.items), p.n_items, num_rels, d, _stream(X.device)), "diag_wgrad_bf16")
     return dw
 
 
@@ -1978,9 +1976,8 @@ def resize3(src, shape, src1=None, n1d=None):
     dst = torch.empty((A, Bd, Cd) if src.dim() == 3 else (Bd, Cd), device=src.device, dtype=torch.float32)
     dst1 = None if src1 is None else torch.empty(n1d, device=src.device, dtype=torch.float32)
     with _on(src.device):
-        _check(lib().rgcn_resize3_f32(_dp(s3), _dp(dst), c_i64(A), c_i32(B), c_i32(C), c_i32(Bd), c_i32(Cd), _dp(src1), _dp(dst1),
-                                      c_i32(0 if src1 is None else src1.numel()), c_i32(0 if src1 is None else n1d), _stream(src.device)),
-               "resize3")
+        _check(lib().rgcn_resize3_f32(_dp(s3), _dp(dst), A, B, C, Bd, Cd, _dp(src1), _dp(dst1), 0 if src1 is None else src1.numel(),
+                                      0 if src1 is None else n1d, _stream(src.device)), "resize3")
     return dst if src1 is None else (dst, dst1)
 
 
@@ -1994,8 +1991,8 @@ def ce_head(logits, row_label, lab_rows):
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     full = torch.empty((N, ld), device=logits.device, dtype=torch.float32)
     with _on(logits.device), _timed("ce_head"):
-        _check(lib().rgcn_ce_head_f32(_dp(logits), _dp(row_label), _dp(lab_rows), _dp(loss), _dp(full), c_i64(N), c_i32(C), c_i32(ld),
-                                      c_i32(lab_rows.shape[0]), _stream(logits.device)), "ce_head")
+        _check(lib().rgcn_ce_head_f32(_dp(logits), _dp(row_label), _dp(lab_rows), _dp(loss), _dp(full), N, C, ld, lab_rows.shape[0],
+                                      _stream(logits.device)), "ce_head")
     return (loss, full, None) if ld == C else (loss, full[:, :C], full)
 
 
@@ -2016,7 +2013,7 @@ def bce_head(scores, labels):
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     ds = torch.empty_like(scores)
     with _on(dev), _timed("bce_head"):
-        _check(lib().rgcn_bce_head_f32(_dp(scores), _dp(labels), _dp(loss), _dp(ds), _dp(ws), c_i64(scores.shape[0]), _stream(dev)), "bce_head")
+        _check(lib().rgcn_bce_head_f32(_dp(scores), _dp(labels), _dp(loss), _dp(ds), _dp(ws), scores.shape[0], _stream(dev)), "bce_head")
     return loss, ds
 
 
@@ -2033,10 +2030,9 @@ def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
     if ranks and T:
         counts, rk = _i32(2 * nodes.shape[0] + 3, nodes.device), _i32(2 * T, nodes.device)
     with _on(nodes.device), _timed("distmult_fwd"):
-        _check(lib().rgcn_distmult_fwd_f32(_dp(triples), c_i64(T), _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                           _dp(obias), _dp(scores), c_i64(nodes.shape[0]), c_i32(rel.shape[0]),
-                                           c_i32(nodes.shape[1]), _dp(err), _dp(counts), _dp(rk), _stream(nodes.device)),
-               "distmult_fwd")
+        _check(lib().rgcn_distmult_fwd_f32(_dp(triples), T, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                           _dp(scores), nodes.shape[0], rel.shape[0], nodes.shape[1], _dp(err),
+                                           _dp(counts), _dp(rk), _stream(nodes.device)), "distmult_fwd")
     # the reference indexes nodes[s], relations[p], nodes[o] (layers.py:89-93) and raises IndexError on a bad index
     dev_check_err(err, "DistMult triples (s, o < num_nodes, p < num_relations)", IndexError)
     return (scores, [counts, rk, False]) if ranks else scores
@@ -2060,10 +2056,9 @@ def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=No
     qvec = torch.empty(Q, d, device=nodes.device, dtype=torch.float32)
     qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
     with _on(nodes.device), _timed("score_all"):
-        _check(lib().rgcn_distmult_score_all_f32(_dp(batch), c_i64(Q), c_i32(1 if head else 0), _dp(nodes), _dp(rel),
-                                                 _dp(sbias), _dp(pbias), _dp(obias), _dp(qvec), _dp(qb), _dp(scores),
-                                                 c_i64(N), c_i32(rel.shape[0]), c_i32(d), _stream(nodes.device)),
-               "distmult_score_all")
+        _check(lib().rgcn_distmult_score_all_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias),
+                                                 _dp(pbias), _dp(obias), _dp(qvec), _dp(qb), _dp(scores), N,
+                                                 rel.shape[0], d, _stream(nodes.device)), "distmult_score_all")
     return scores
 
 
@@ -2072,8 +2067,8 @@ def rank_filter(scores, filt_q, filt_n):
     _req(scores, "scores"); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
     assert filt_q.shape == filt_n.shape and filt_q.dim() == 1
     with _on(scores.device):
-        _check(lib().rgcn_rank_filter_f32(_dp(scores), c_i64(scores.shape[0]), c_i64(scores.shape[1]), _dp(filt_q),
-                                          _dp(filt_n), c_i64(filt_q.shape[0]), _stream(scores.device)), "rank_filter")
+        _check(lib().rgcn_rank_filter_f32(_dp(scores), scores.shape[0], scores.shape[1], _dp(filt_q), _dp(filt_n),
+                                          filt_q.shape[0], _stream(scores.device)), "rank_filter")
     return scores
 
 
@@ -2085,9 +2080,8 @@ def rank_count(scores, batch, head):
     greater = torch.empty(Q, device=scores.device, dtype=torch.int64)
     ties = torch.empty(Q, device=scores.device, dtype=torch.int64)
     with _on(scores.device), _timed("rank_count"):
-        _check(lib().rgcn_rank_count_f32(_dp(scores), _dp(batch), c_i64(Q), c_i32(1 if head else 0),
-                                         c_i64(scores.shape[1]), _dp(greater), _dp(ties), _stream(scores.device)),
-               "rank_count")
+        _check(lib().rgcn_rank_count_f32(_dp(scores), _dp(batch), Q, 1 if head else 0, scores.shape[1], _dp(greater),
+                                         _dp(ties), _stream(scores.device)), "rank_count")
     return greater, ties
 
 
@@ -2101,15 +2095,14 @@ def distmult_bwd(triples, nodes, rel, gs, with_bias, nodes_grad=True):
     dob = torch.empty(nodes.shape[0], device=nodes.device) if with_bias else None
     dpb = torch.empty(rel.shape[0], device=nodes.device) if with_bias else None
     with _on(nodes.device), _timed("distmult_bwd"):
-        _check(lib().rgcn_distmult_bwd_f32(_dp(triples), c_i64(triples.shape[0]), _dp(nodes), _dp(rel), _dp(gs),
-                                           _dp(dn), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), c_i64(nodes.shape[0]),
-                                           c_i32(rel.shape[0]), c_i32(nodes.shape[1]), _stream(nodes.device)),
-               "distmult_bwd")
+        _check(lib().rgcn_distmult_bwd_f32(_dp(triples), triples.shape[0], _dp(nodes), _dp(rel), _dp(gs), _dp(dn),
+                                           _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), nodes.shape[0], rel.shape[0],
+                                           nodes.shape[1], _stream(nodes.device)), "distmult_bwd")
     return dn, dr, dsb, dpb, dob
 
 
 def distmult_bwd_all_supported(n_rel, d):
-    return bool(lib().rgcn_distmult_bwd_all_supported(c_i32(n_rel), c_i32(d)))
+    return bool(lib().rgcn_distmult_bwd_all_supported(n_rel, d))
 
 
 def distmult_csrs(triples, ranks, nodes, rel, gs):
@@ -2123,8 +2116,8 @@ def distmult_csrs(triples, ranks, nodes, rel, gs):
     ranks[2] = True
     entries = torch.empty((max(2 * T, 1), 4), dtype=torch.int32, device=dev)
     with _on(dev):
-        _check(lib().rgcn_distmult_csr_place(_dp(triples), c_i64(T), c_i64(N), c_i32(R), _dp(rk), _dp(counts), _dp(scan_tmp), _dp(gs),
-                                             _dp(entries), _stream(dev)), "distmult_csr_place")
+        _check(lib().rgcn_distmult_csr_place(_dp(triples), T, N, R, _dp(rk), _dp(counts), _dp(scan_tmp), _dp(gs), _dp(entries),
+                                             _stream(dev)), "distmult_csr_place")
     return counts[1: N + 2], counts[N + 2: 2 * N + 3], entries
 
 
@@ -2143,7 +2136,7 @@ def distmult_bwd_all(triples, ranks, nodes, rel, gs, with_bias):
         dpb = torch.empty(R, device=dev, dtype=torch.float32)
     with _on(dev), _timed("distmult_bwd_all"):
         _check(lib().rgcn_distmult_bwd_all_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), _dp(dr), _dp(dsb),
-                                               _dp(dpb), _dp(dob), c_i64(N), c_i32(R), c_i32(d), _stream(dev)), "distmult_bwd_all")
+                                               _dp(dpb), _dp(dob), N, R, d, _stream(dev)), "distmult_bwd_all")
     return dn, dr, dsb, dpb, dob
 
 
@@ -2156,6 +2149,6 @@ def distmult_bwd_nodes(triples, ranks, nodes, rel, gs):
     rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
     dn = torch.empty_like(nodes)
     with _on(dev), _timed("distmult_bwd_nodes"):
-        _check(lib().rgcn_distmult_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), c_i64(N), c_i32(d),
+        _check(lib().rgcn_distmult_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d,
                                                  _stream(dev)), "distmult_bwd_nodes")
     return dn
