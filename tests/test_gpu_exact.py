@@ -168,10 +168,15 @@ def make_layer(fx, params, bias, d_in, d_out, mode, featureless, vertical, num_b
 
 
 def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, relu=False, dtype=torch.float32, pdtype=torch.float32,
-              num_bases=3, num_blocks=2, vmax=2, density=0.5, expect=(), forbid=(), split=None, seed=0, param_dtypes=None, lp=False):
+              num_bases=3, num_blocks=2, vmax=2, density=0.5, expect=(), forbid=(), split=None, seed=0, param_dtypes=None, lp=False,
+              frozen=(), counts=None):
     """one layer, forward and backward, on the fixture `fix`; every result equal to the oracle.  lp: the link-prediction layer in eval mode
-    (no dropout), the graph handed over per call.  -> (profile tags, the layer)"""
+    (no dropout), the graph handed over per call.  frozen: names out of "X", the layer's parameter names and "bias" that get no gradient
+    (requires_grad False before the forward) -- their .grad must stay None, and everything else is compared with the SAME reference: the
+    gradient of a tensor does not depend on which other tensors are frozen.  counts: {profile tag: launches} that must match exactly (the
+    forward and the feature gradient share a tag: only the count tells them apart).  -> (profile tags, the layer)"""
     from torch_rgcn import _native
+    frozen = frozenset(frozen)
     fx = lp_fixture(fix) if lp else fixture(fix)
     params, bias, X, g, ref, bits = exact_case(fix, lp, d_in, d_out, mode, featureless, vertical, relu, num_bases, num_blocks, vmax, density,
                                                seed)                                  # the proof: on the CPU, before any launch
@@ -180,7 +185,11 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
         layer = layer.to(pdtype)
     for n, dt in (param_dtypes or {}).items():
         getattr(layer, n).data = getattr(layer, n).data.to(dt)
-    Xd = None if featureless else _dev(X, dtype).requires_grad_(True)
+    names = {n for n, _ in layer.named_parameters()} | (set() if featureless else {"X"})
+    assert frozen <= names and frozen != names, (sorted(frozen), sorted(names))
+    for n in frozen - {"X"}:
+        getattr(layer, n).requires_grad_(False)
+    Xd = None if featureless else _dev(X, dtype).requires_grad_("X" not in frozen)
     _native.profile_start()
     if lp:
         out = layer(torch.from_numpy(fx["T"]).to(DEV), Xd)
@@ -189,10 +198,12 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
     else:
         out = layer(Xd) if Xd is not None else layer()
     out.backward(_dev(g, out.dtype))
-    tags = set(_native.profile_stop())
+    launches = {k: len(v) for k, v in _native.profile_stop().items()}
+    tags = set(launches)
     ind = None if split is None else int(_split(layer._graph, split, d_in, d_out))
     case = f"{fx['name']} {d_in}x{d_out} {mode}{' featureless' if featureless else ''}{' vertical' if vertical else ''}{' relu' if relu else ''}" \
-           f"{' bf16' if dtype == BF or param_dtypes else ''}{' p16' if pdtype == BF else ''}"
+           f"{' bf16' if dtype == BF or param_dtypes else ''}{' p16' if pdtype == BF else ''}" \
+           f"{' frozen {' + ', '.join(sorted(frozen)) + '}' if frozen else ''}"
     print(f"[exact] {case}: tags {sorted(tags)} | split {ind} | proof bits " + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
 
     problems = []
@@ -206,13 +217,18 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
     if out.dtype != want_dtype:
         problems.append(f"out is {out.dtype}")
     check(out, ref["out"], "out", fx["deg_s"])
-    if Xd is not None:
+    for n in sorted(frozen):
+        if (Xd if n == "X" else getattr(layer, n)).grad is not None:
+            problems.append(f"{n} is frozen and has a gradient")
+    if Xd is not None and "X" not in frozen:
         if Xd.grad.dtype != dtype:
             problems.append(f"dX is {Xd.grad.dtype}")
         check(Xd.grad, ref["dX"], "dX", fx["deg_o"])
-    if bias is not None:
+    if bias is not None and "bias" not in frozen:
         check(layer.bias.grad, ref["db"], "db")
     for n, gv in ref["grads"].items():
+        if n in frozen:
+            continue
         p = getattr(layer, n)
         if p.grad.dtype != p.dtype:
             problems.append(f"grad of {n} is {p.grad.dtype}, the parameter {p.dtype}")
@@ -223,6 +239,9 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
     for t in forbid:
         if t in tags:
             problems.append(f"kernel tag {t} ran: {sorted(tags)}")
+    for t, n in (counts or {}).items():
+        if launches.get(t, 0) != n:
+            problems.append(f"kernel tag {t}: {launches.get(t, 0)} launches, {n} expected: {launches}")
     if split is not None and ind <= 0:
         problems.append(f"split indicator '{split}' is {ind}: the hub is not cut into pieces on this route")
     assert not problems, case + "\n" + "\n".join(problems)
@@ -530,7 +549,16 @@ def test_lp_layer(fix, case):
 def test_distmult(monkeypatch, bwd, d, with_bias):
     """integer embeddings, repeated triples, a hub subject that is a hub object too: scores and every gradient equal to the oracle.  All
     terms are integers (grid 1): the proof bound is the oracle on the absolute values"""
+    distmult_exact(monkeypatch, bwd, d, with_bias)
+
+
+def distmult_exact(monkeypatch, bwd, d, with_bias, frozen=()):
+    """the body of test_distmult.  frozen: names out of "nodes", "relations", "biases" (the three bias vectors together) that get no
+    gradient: theirs must stay None, the others equal the same oracle gradients.  All of them frozen: forward only -- the scores exact and
+    no CSR ranks counted by the scoring kernel"""
     from torch_rgcn import _native
+    frozen = frozenset(frozen)
+    assert frozen <= {"nodes", "relations", "biases"} and (with_bias or "biases" not in frozen)
     from torch_rgcn.layers import DistMult
     routes.patch(monkeypatch, "distmult_bwd", bwd)
     N, R0, T = 300, 5, 4000
@@ -559,24 +587,47 @@ def test_distmult(monkeypatch, bwd, d, with_bias):
         dm.relations.copy_(torch.from_numpy(rel))
         if with_bias:
             dm.sbias.copy_(torch.from_numpy(sb)); dm.obias.copy_(torch.from_numpy(ob)); dm.pbias.copy_(torch.from_numpy(pb))
-    nd = torch.from_numpy(nodes).to(DEV).requires_grad_(True)
+    dm.relations.requires_grad_("relations" not in frozen)
+    if with_bias:
+        for b in (dm.sbias, dm.pbias, dm.obias):
+            b.requires_grad_("biases" not in frozen)
+    nd = torch.from_numpy(nodes).to(DEV).requires_grad_("nodes" not in frozen)
+    any_grad = frozen != ({"nodes", "relations", "biases"} if with_bias else {"nodes", "relations"})
+    asked = []                                                  # ranks= of every call of the scoring kernel's wrapper
+    inner = _native.distmult_fwd
+    monkeypatch.setattr(_native, "distmult_fwd", lambda *a, ranks=False: (asked.append(ranks), inner(*a, ranks=ranks))[1])
     _native.profile_start()
     sc = dm(torch.from_numpy(tr).to(DEV), nd)
-    sc.backward(torch.from_numpy(gs).to(DEV))
+    if any_grad:
+        sc.backward(torch.from_numpy(gs).to(DEV))
     tags = set(_native.profile_stop())
-    print(f"[exact] distmult {bwd} d={d} bias={with_bias}: tags {sorted(tags)} | proof bits " + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
+    print(f"[exact] distmult {bwd} d={d} bias={with_bias}{' frozen {' + ', '.join(sorted(frozen)) + '}' if frozen else ''}: tags {sorted(tags)} "
+          f"| proof bits " + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
+    # the scoring kernel counts the CSR ranks when anything needs a gradient and the backward will walk the CSRs
+    assert asked == [any_grad and bwd != "atomic"], asked
     # csr: every gradient from the two CSR walks where the relation table fits (distmult_bwd_all_supported), else the split form; split:
-    # predicate-sorted kernel + entity gradients from the CSRs; atomic: the scatter kernel alone
+    # predicate-sorted kernel + entity gradients from the CSRs; atomic: the scatter kernel alone.  (The backward computes every gradient
+    # whatever is frozen: autograd drops what nobody asked for.)
     want = {"atomic": {"distmult_bwd"}, "split": {"distmult_bwd", "distmult_bwd_nodes"},
             "csr": {"distmult_bwd_all"} if _native.distmult_bwd_all_supported(R0, d) else {"distmult_bwd", "distmult_bwd_nodes"}}[bwd]
+    if not any_grad:
+        want = set()
     assert "distmult_fwd" in tags and {t for t in tags if t.startswith("distmult_bwd")} == want, (sorted(tags), sorted(want))
     if d <= 52:
         assert _native.distmult_bwd_all_supported(R0, d), "the csr route's own kernel is not exercised at any tested width"
     ex.assert_equal_exact(sc, sc_ref, "scores")
-    ex.assert_equal_exact(nd.grad, dn, "dnodes")
-    ex.assert_equal_exact(dm.relations.grad, dr, "drelations")
-    if with_bias:
+    if "nodes" in frozen:
+        assert nd.grad is None
+    else:
+        ex.assert_equal_exact(nd.grad, dn, "dnodes")
+        assert float(nd.grad[3].abs().max()) == 0.0
+    if "relations" in frozen:
+        assert dm.relations.grad is None
+    else:
+        ex.assert_equal_exact(dm.relations.grad, dr, "drelations")
+    if with_bias and "biases" in frozen:
+        assert dm.sbias.grad is None and dm.pbias.grad is None and dm.obias.grad is None
+    elif with_bias:
         ex.assert_equal_exact(dm.sbias.grad, dsb, "dsbias")
         ex.assert_equal_exact(dm.pbias.grad, dpb, "dpbias")
         ex.assert_equal_exact(dm.obias.grad, dob, "dobias")
-    assert float(nd.grad[3].abs().max()) == 0.0

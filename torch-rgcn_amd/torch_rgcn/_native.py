@@ -859,6 +859,8 @@ def fbasis_bwd(table, comps, g, plan, need_bases=True, need_comps=True, basis_ma
     dev = bases.device
     dB = torch.empty_like(bases) if need_bases else None
     dC = torch.empty(R, B, device=dev, dtype=torch.float32) if need_comps else None
+    if dB is None and dC is None:          # bases and comps frozen (a trainable bias still brings the backward here): nothing to launch
+        return None, None
     units, n_units, n_split = plan.units_src
     if need_comps and not routes.flag("deterministic") and \
             lib().rgcn_fbasis_bwd_dc_supported(R, B, d):
