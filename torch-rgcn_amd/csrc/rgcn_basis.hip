@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "rgcn_hip.h"
+#include "rgcn_launch.h"
 #include "rgcn_zero.h"
 #include "rgcn_options.h"
 
@@ -401,24 +402,15 @@ extern "C" int rgcn_fbasis_bwd_dc_f32(const float *bases, const float *comps, co
   HIP_TRY(zero_async(dcomps, (size_t)R * B * sizeof(float), st));
   if (dbases && n_split) HIP_TRY(zero_async(dbases, (size_t)B * n_nodes * d * sizeof(float), st));
   if (n_units == 0) return RGCN_OK;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   const size_t lds = (size_t)R * B * sizeof(double);
   const int per_cu = lds <= 72 * 1024 ? 2 : 1;
   const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_units + DC_WG / 64 - 1) / (DC_WG / 64), (int64_t)n_cu * per_cu)));
   const int4 *un = reinterpret_cast<const int4 *>(units);
 #define RGCN_FB_DC(DPC)                                                                                                            \
   {                                                                                                                                \
-    static bool raised = false;                                                                                                    \
-    if (lds > 64 * 1024 && !raised) {                                                                                              \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fbasis_bwd_dc_kernel<DPC>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024)); \
-      raised = true;                                                                                                               \
-    }                                                                                                                              \
+    HIP_TRY(allow_lds<fbasis_bwd_dc_kernel<DPC>>(dev, lds, 120 * 1024));                                                           \
     hipLaunchKernelGGL(fbasis_bwd_dc_kernel<DPC>, grid, dim3(DC_WG), lds, st, bases, comps, G, dbases, dcomps, e_dst, e_rel, e_val, un, \
                        (int)n_units, R, B, d, sn, sb);                                                                             \
   }
@@ -792,13 +784,8 @@ extern "C" int rgcn_basis_aggregate_f32(const float *X, const float *comps, floa
     int lpm = 1;
     while (lpm < 64 && 4 * lpm < d) lpm *= 2;
     if (d <= 256 && B <= 4) {                            // one pass per row, few bases: the rows pipelined over persistent waves
-      static int n_cu = 0;
-      if (!n_cu) {
-        int dev = 0, v = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-        n_cu = v > 0 ? v : 256;
-      }
+      int dev = 0, n_cu = 0;
+      HIP_TRY(launch_device(&dev, &n_cu));
       const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows * 64 + TB - 1) / TB, (int64_t)n_cu * 8));
 #define RGCN_BAP(MODE_, NB_) hipLaunchKernelGGL((basis_aggregate_pipe_kernel<MODE_, NB_>), dim3(grid), dim3(TB), 0, (hipStream_t)stream, X, comps, \
                                                 out, rowptr, p_src, p_rel, p_val, (long long)n_rows, B, d, lpm)
@@ -892,7 +879,7 @@ inline unsigned persistent_grid(int64_t n_rows, int n_cu) {
 
 extern "C" int64_t rgcn_basis_sum_workspace_bytes(int32_t R, int32_t B) {
   int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+  if (launch_device(&dev, &v) != hipSuccess) v = 256;
   return (int64_t)2 * v * (((int64_t)R * B + 15) & ~(int64_t)15) * (int64_t)sizeof(double) + 256;     // (rows of whole lines; ticket + alignment slack)
 }
 
@@ -1075,13 +1062,8 @@ extern "C" int rgcn_basis_dcomps_csr_f32(const float *X, const float *D, float *
   if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(D)) & 15) != 0) { rgcn_set_error("basis_dcomps_csr: X / D must be 16-byte aligned"); return RGCN_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   if (!n_rows) { HIP_TRY(zero_async(dcomps, (size_t)R * B * sizeof(float), st)); return RGCN_OK; }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   const unsigned grid = persistent_grid(n_rows, n_cu);
   const size_t lds = (size_t)R * B * sizeof(double);
   int lpm = 1;
@@ -1112,13 +1094,8 @@ extern "C" int rgcn_fbasis_small_bwd_f32(const float *G, const float *table, con
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(zero_async(dcomps, (size_t)R * B * sizeof(float), st));
   if (!n_rows) return RGCN_OK;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows * 64 + TB - 1) / TB, (int64_t)n_cu * 8));
   const size_t lds = (size_t)R * B * sizeof(double);
   const int lpm = d / 4;

@@ -508,41 +508,36 @@ int block_spmm_launch(const float *X, const float *blocks, const float *bias, fl
   const size_t lds_bytes = table_bytes + (size_t)n_rel_blocks * 4 * sizeof(float);          // + the per-relation pad
   if (bi == 4 && bo == 4 && lds_bytes <= LDS_TABLE_BYTES && n_units >= 64 * 1024) {
     const dim3 pgrid((unsigned)std::min<int64_t>(512, (n_units * lr + BIG_WG - 1) / BIG_WG));
-    auto launch = [&](auto kern, bool &raised, auto... o16) -> hipError_t {
-      if (lds_bytes > 64 * 1024 && !raised) {     // once per process and kernel (not a stream operation: keep it out of captures)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)LDS_TABLE_BYTES);
-        if (e != hipSuccess) return e;
-        raised = true;
-      }
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    auto launch = [&](auto k, auto... o16) -> hipError_t {
+      constexpr auto kern = decltype(k)::value;
+      hipError_t e = allow_lds<kern>(dev, lds_bytes, (int)LDS_TABLE_BYTES);     // once per device and kernel (not a stream operation: keep it out of captures)
+      if (e != hipSuccess) return e;
       hipLaunchKernelGGL(kern, pgrid, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, rowptr, (long long)n_units, e_src,
                          e_rel, e_val, nb, bi, bo, n_rel_blocks, lpm, lr, (int)relu, (int)(table_bytes / sizeof(float)), o16...);
       return hipGetLastError();
     };
-    static bool raised_t = false, raised_n = false, raised_pt = false, raised_pn = false;
     if constexpr (BF) {           // (width 16 too: block44_csr_kernel has no bf16 form)
-      (void)raised_pt; (void)raised_pn;
-      if (tr) HIP_TRY(launch(block_csr_lds_kernel<4, 4, true, uint16_t *>, raised_t, out16));
-      else HIP_TRY(launch(block_csr_lds_kernel<4, 4, false, uint16_t *>, raised_n, out16));
+      if (tr) HIP_TRY(launch(kern_c<block_csr_lds_kernel<4, 4, true, uint16_t *>>, out16));
+      else HIP_TRY(launch(kern_c<block_csr_lds_kernel<4, 4, false, uint16_t *>>, out16));
     } else {
       if (nb == 4 && un) {          // width 16: the software-pipelined form
         const dim3 pg((unsigned)std::min<int64_t>(512, (n_units + BIG_WG / 16 - 1) / (BIG_WG / 16)));
-        auto launch_p = [&](auto kern, bool &raised) -> hipError_t {
-          if (lds_bytes > 64 * 1024 && !raised) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TABLE_BYTES);
-            if (e != hipSuccess) return e;
-            raised = true;
-          }
+        auto launch_p = [&](auto k) -> hipError_t {
+          constexpr auto kern = decltype(k)::value;
+          hipError_t e = allow_lds<kern>(dev, lds_bytes, (int)LDS_TABLE_BYTES);
+          if (e != hipSuccess) return e;
           hipLaunchKernelGGL(kern, pg, dim3(BIG_WG), lds_bytes, st, X, blocks, bias, out, un, (long long)n_units, e_src, e_rel, e_val,
                              n_rel_blocks, (int)relu, (int)(table_bytes / sizeof(float)));
           return hipGetLastError();
         };
-        if (tr) HIP_TRY(launch_p(block44_csr_kernel<true>, raised_pt));
-        else HIP_TRY(launch_p(block44_csr_kernel<false>, raised_pn));
+        if (tr) HIP_TRY(launch_p(kern_c<block44_csr_kernel<true>>));
+        else HIP_TRY(launch_p(kern_c<block44_csr_kernel<false>>));
         return RGCN_OK;
       }
-      if (tr) HIP_TRY(launch(block_csr_lds_kernel<4, 4, true>, raised_t));
-      else HIP_TRY(launch(block_csr_lds_kernel<4, 4, false>, raised_n));
+      if (tr) HIP_TRY(launch(kern_c<block_csr_lds_kernel<4, 4, true>>));
+      else HIP_TRY(launch(kern_c<block_csr_lds_kernel<4, 4, false>>));
     }
     return RGCN_OK;
   }
@@ -636,11 +631,9 @@ extern "C" int rgcn_spmm_csr_d16_f32(const float *X, const float *W, const float
   hipStream_t st = (hipStream_t)stream;
   if (n_split) HIP_TRY(zero_async(out, (size_t)n_rows * 16 * sizeof(float), st));
   const size_t lds = (size_t)R * CSRW_REL * sizeof(float);
-  static bool raised = false;
-  if (lds > 64 * 1024 && !raised) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(spmm_csr_d16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    raised = true;
-  }
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(allow_lds<spmm_csr_d16_kernel>(dev, lds, 150 * 1024));
   const unsigned gx = (unsigned)std::min<int64_t>(256 * (lds <= 76 * 1024 ? 2 : 1), (n_units + BIG_WG / 16 - 1) / (BIG_WG / 16));
   hipLaunchKernelGGL(spmm_csr_d16_kernel, dim3(gx), dim3(BIG_WG), lds, st, X, W, bias, out, reinterpret_cast<const int4 *>(units),
                      (long long)n_units, e_src, e_rel, e_val, R, (int)relu);

@@ -599,13 +599,11 @@ struct LeanLaunch {
 };
 template <int NW, int NG, bool AT, bool RELU, int ABL = 0>
 hipError_t launch_bwd_lean(const LeanLaunch &a) {
-  auto kern = bwd_lean_d16_kernel<NW, NG, AT, RELU, ABL>;
-  static bool raised = false;                    // once per process and instantiation (not a stream operation)
-  if (a.lds > 64 * 1024 && !raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    raised = true;
-  }
+  constexpr auto kern = bwd_lean_d16_kernel<NW, NG, AT, RELU, ABL>;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = allow_lds<kern>(dev, a.lds, 160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)a.n_blocks), dim3(64 * NW), a.lds, a.st, a.G, a.X, a.Wtp, a.dX, a.dWout, a.slots, a.hdr,
                      a.run_ptr, a.n_tiles, a.n_blocks, a.tile_rows, a.n_dst, a.R);
   return hipGetLastError();

@@ -713,30 +713,20 @@ extern "C" int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_
   const int tq = tile_rows > 256 ? 2 : 1;
   const size_t lds = bwd_blk_lds(R, diag4, tile_rows);
   hipStream_t st = (hipStream_t)stream;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   if (dbias && (n_src <= 0 || n_src >= (int64_t(1) << 29))) { rgcn_set_error("bwd_blk: dbias needs 0 < n_src < 2^29"); return RGCN_EINVAL; }
   if (flags & RGCN_F_ACCUMULATE) {
     // a later slab of the same backward (relation-sharded layers: the slab before is being all-reduced while this one runs): dW / dbias keep adding
-  } else if (dbias == dW + (size_t)R * 256) {     // one fill for both when the caller laid them out back to back
-    HIP_TRY(zero_async(dW, ((size_t)R * 256 + 16) * sizeof(float), st));
   } else {
-    HIP_TRY(zero_async(dW, (size_t)R * 256 * sizeof(float), st));
-    if (dbias) HIP_TRY(zero_async(dbias, 16 * sizeof(float), st));
+    HIP_TRY(zero_dw_dbias_async(dW, (size_t)R, dbias, st));
   }
   if (n_split) HIP_TRY(zero_async(dX, (size_t)n_dst * 16 * sizeof(float), st));        // pieces of hub tiles add their rows
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
-  auto launch = [&](auto kern, bool &raised) -> hipError_t {
-    if (lds > 64 * 1024 && !raised) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BLK_LDS_MAX);
-      if (e != hipSuccess) return e;
-      raised = true;
-    }
+  auto launch = [&](auto k) -> hipError_t {
+    constexpr auto kern = decltype(k)::value;
+    hipError_t e = allow_lds<kern>(dev, lds, BLK_LDS_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * BLK_NW), lds, st, G, X, Wt_packed, dX, dW, static_cast<const char *>(rec), run_ptr,
                        (int)n_tiles, tile_rows, (int)n_dst, R, dbias, (int)n_src, reinterpret_cast<const int4 *>(units), (int)n_units);
     return hipGetLastError();
@@ -744,28 +734,26 @@ extern "C" int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_
 #ifdef RGCN_ABLATIONS
   {
     const int ABLV = rgcn_option_value(RGCN_OPT_BWD_ABL);     // timing experiments (wrong results): this library only
-    static bool a0 = false, a1 = false, a2 = false, a3 = false, a4 = false, a5 = false, a6 = false, a7 = false;
     if (tq != 1 || diag4) { rgcn_set_error("bwd_blk (ablation library): only dense weights on tiles of up to 256 rows"); return RGCN_EUNSUPPORTED; }
-    if (ABLV == 2) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 2>, a0));
-    else if (ABLV == 8) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 8>, a1));
-    else if (ABLV == 10) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 10>, a2));
-    else if (ABLV == 16) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 16>, a3));
-    else if (ABLV == 4) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 4>, a4));
-    else if (ABLV == 32) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 32>, a5));
-    else if (ABLV == 36) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 36>, a6));
-    else HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1, 0>, a7));
+    if (ABLV == 2) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 2>>));
+    else if (ABLV == 8) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 8>>));
+    else if (ABLV == 10) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 10>>));
+    else if (ABLV == 16) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 16>>));
+    else if (ABLV == 4) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 4>>));
+    else if (ABLV == 32) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 32>>));
+    else if (ABLV == 36) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 36>>));
+    else HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1, 0>>));
     return RGCN_OK;
   }
 #else
-  static bool r0 = false, r1 = false, r2 = false, r3 = false, r4 = false, r5 = false, r6 = false, r7 = false;
-  if (tq == 2 && diag4 && relu) HIP_TRY(launch(bwd_blk_d16_kernel<true, true, 2>, r0));
-  else if (tq == 2 && diag4) HIP_TRY(launch(bwd_blk_d16_kernel<false, true, 2>, r1));
-  else if (tq == 2 && relu) HIP_TRY(launch(bwd_blk_d16_kernel<true, false, 2>, r2));
-  else if (tq == 2) HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 2>, r3));
-  else if (diag4 && relu) HIP_TRY(launch(bwd_blk_d16_kernel<true, true, 1>, r4));
-  else if (diag4) HIP_TRY(launch(bwd_blk_d16_kernel<false, true, 1>, r5));
-  else if (relu) HIP_TRY(launch(bwd_blk_d16_kernel<true, false, 1>, r6));
-  else HIP_TRY(launch(bwd_blk_d16_kernel<false, false, 1>, r7));
+  if (tq == 2 && diag4 && relu) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<true, true, 2>>));
+  else if (tq == 2 && diag4) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, true, 2>>));
+  else if (tq == 2 && relu) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<true, false, 2>>));
+  else if (tq == 2) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 2>>));
+  else if (diag4 && relu) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<true, true, 1>>));
+  else if (diag4) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, true, 1>>));
+  else if (relu) HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<true, false, 1>>));
+  else HIP_TRY(launch(kern_c<bwd_blk_d16_kernel<false, false, 1>>));
 #endif
   return RGCN_OK;
 }
@@ -785,38 +773,30 @@ extern "C" int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const fl
   const bool relu = (flags & RGCN_F_RELU) != 0;
   if (relu && n_split) { rgcn_set_error("spmm_blk: relu in the epilogue needs tiles that are not cut into shared pieces"); return RGCN_EUNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   if (n_split) HIP_TRY(zero_async(out, (size_t)n_dst * 16 * sizeof(float), st));          // pieces of hub tiles add their rows
   const size_t lds = (size_t)tile_rows * 128 + 64;
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
-  auto launch = [&](auto kern, bool &raised) -> hipError_t {
-    if (lds > 64 * 1024 && !raised) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BLK_LDS_MAX);
-      if (e != hipSuccess) return e;
-      raised = true;
-    }
+  auto launch = [&](auto k) -> hipError_t {
+    constexpr auto kern = decltype(k)::value;
+    hipError_t e = allow_lds<kern>(dev, lds, BLK_LDS_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * BLK_FWD_NW), lds, st, X, W_packed, bias, out, static_cast<const char *>(rec), run_ptr, (int)n_tiles,
                        tile_rows, (int)n_dst, R, reinterpret_cast<const int4 *>(units), (int)n_units);
     return hipGetLastError();
   };
-  static bool r[8] = {false, false, false, false, false, false, false, false};
   const int tq = (tile_rows + 255) / 256;
   if (relu) {
-    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS>, r[0]));
-    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS>, r[1]));
-    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS>, r[2]));
-    else HIP_TRY(launch(spmm_blk_d16_kernel<true, 4 * BLK_FWD_TQS>, r[3]));
+    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS>>));
+    else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS>>));
+    else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS>>));
+    else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 4 * BLK_FWD_TQS>>));
   } else {
-    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS>, r[4]));
-    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS>, r[5]));
-    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS>, r[6]));
-    else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS>, r[7]));
+    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS>>));
+    else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS>>));
+    else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS>>));
+    else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS>>));
   }
   return RGCN_OK;
 }
@@ -842,50 +822,42 @@ extern "C" int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, cons
   if (relu && n_split) { rgcn_set_error("spmm_blk_bf16: relu in the epilogue needs tiles that are not cut into shared pieces"); return RGCN_EUNSUPPORTED; }
   if (n_split && !scratch) { rgcn_set_error("spmm_blk_bf16: a plan with hub pieces needs the fp32 scratch (n_dst x 16 floats)"); return RGCN_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
   // hub pieces add fp32 rows into the scratch (zeroed), rounded to bf16 once afterwards: never bf16 atomics (rounded at every add)
   float *dst32 = n_split ? scratch : reinterpret_cast<float *>(out);
   if (n_split) HIP_TRY(zero_async(scratch, (size_t)n_dst * 16 * sizeof(float), st));
   const size_t lds = (size_t)tile_rows * 128 + 64;
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
   const float *Xf = reinterpret_cast<const float *>(X);
-  auto launch = [&](auto kern, bool &raised) -> hipError_t {
-    if (lds > 64 * 1024 && !raised) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BLK_LDS_MAX);
-      if (e != hipSuccess) return e;
-      raised = true;
-    }
+  auto launch = [&](auto k) -> hipError_t {
+    constexpr auto kern = decltype(k)::value;
+    hipError_t e = allow_lds<kern>(dev, lds, BLK_LDS_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * BLK_FWD_NW), lds, st, Xf, W_packed, bias, dst32, static_cast<const char *>(rec), run_ptr,
                        (int)n_tiles, tile_rows, (int)n_dst, R, reinterpret_cast<const int4 *>(units), (int)n_units);
     return hipGetLastError();
   };
-  static bool r[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
   const int tq = (tile_rows + 255) / 256;
   if (n_split) {
-    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 1>, r[0]));
-    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 1>, r[1]));
-    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 1>, r[2]));
-    else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 1>, r[3]));
+    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 1>>));
+    else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 1>>));
+    else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 1>>));
+    else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 1>>));
     const long long n4 = n_dst * 4;
     hipLaunchKernelGGL(round_rows_bf16_kernel, dim3((unsigned)std::min<long long>((n4 + WG - 1) / WG, 4096)), dim3(WG), 0, st,
                        reinterpret_cast<const float4 *>(scratch), reinterpret_cast<uint2 *>(out), n4);
     HIP_TRY(hipGetLastError());
   } else if (relu) {
-    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS, 3>, r[4]));
-    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS, 3>, r[5]));
-    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS, 3>, r[6]));
-    else HIP_TRY(launch(spmm_blk_d16_kernel<true, 4 * BLK_FWD_TQS, 3>, r[7]));
+    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS, 3>>));
+    else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS, 3>>));
+    else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS, 3>>));
+    else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 4 * BLK_FWD_TQS, 3>>));
   } else {
-    if (tq == 1) HIP_TRY(launch(spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 3>, r[8]));
-    else if (tq == 2) HIP_TRY(launch(spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 3>, r[9]));
-    else if (tq == 3) HIP_TRY(launch(spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 3>, r[10]));
-    else HIP_TRY(launch(spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 3>, r[11]));
+    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 3>>));
+    else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 3>>));
+    else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 3>>));
+    else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 3>>));
   }
   return RGCN_OK;
 }

@@ -46,7 +46,7 @@ constexpr int OWN_LDS_MAX = 160 * 1024;
 constexpr int OWN_NW = RGCN_OWN_NW;  // waves per workgroup
 constexpr int OWN_K = RGCN_OWN_K;    // relations per wave (accumulators in registers)
 constexpr int OWN_U = RGCN_OWN_U;    // chunks per loop trip
-constexpr int OWN_MAX_ROWS = (OWN_LDS_MAX - OWN_NW * BW_SCR2 * 4 - 64) / 192;      // 789: dX tile (doubles) + X tile + the waves' scratch
+constexpr int OWN_MAX_ROWS = (OWN_LDS_MAX - OWN_NW * BW_SCR2 * 4 - 64) / 192;      // 767: dX tile (doubles) + X tile + the waves' scratch
 
 // the first 8 accumulators of a wave: ONE register vector indexed by the chunk's local relation number (a <32 x float> is the largest
 // the compiler keeps in registers under a dynamic index: s_set_gpr_idx_on + v_mov; <36 x float> goes to scratch); the ninth is a
@@ -357,27 +357,15 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
   }
   if (dbias && (n_src <= 0 || n_src >= (int64_t(1) << 29))) { rgcn_set_error("bwd_own: dbias needs 0 < n_src < 2^29"); return RGCN_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
-  if (dbias == dW + (size_t)R * 256) {     // one fill for both when the caller laid them out back to back
-    HIP_TRY(zero_async(dW, ((size_t)R * 256 + 16) * sizeof(float), st));
-  } else {
-    HIP_TRY(zero_async(dW, (size_t)R * 256 * sizeof(float), st));
-    if (dbias) HIP_TRY(zero_async(dbias, 16 * sizeof(float), st));
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  HIP_TRY(zero_dw_dbias_async(dW, (size_t)R, dbias, st));
   const size_t lds = bwd_own_lds(tile_rows);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_tiles, n_cu);
-  auto launch = [&](auto kern, bool &raised) -> hipError_t {
-    if (lds > 64 * 1024 && !raised) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, OWN_LDS_MAX);
-      if (e != hipSuccess) return e;
-      raised = true;
-    }
+  auto launch = [&](auto k) -> hipError_t {
+    constexpr auto kern = decltype(k)::value;
+    hipError_t e = allow_lds<kern>(dev, lds, OWN_LDS_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, G, X, Wt_packed, dX, dW, static_cast<const char *>(rec), own_ptr, (int)n_tiles,
                        tile_rows, (int)n_dst, dbias, (int)n_src, unit_rel);
     return hipGetLastError();
@@ -385,19 +373,17 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
 #ifdef RGCN_ABLATIONS
   {
     const int ABLV = rgcn_option_value(RGCN_OPT_BWD_ABL);
-    static bool a[8] = {false, false, false, false, false, false, false, false};
-    if (ABLV == 2) HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 2>, a[1]));
-    else if (ABLV == 4) HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 4>, a[3]));
-    else if (ABLV == 8) HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 8>, a[4]));
-    else if (ABLV == 16) HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 16>, a[5]));
-    else if (ABLV == 6) HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 6>, a[6]));
-    else HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0>, a[7]));
+    if (ABLV == 2) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 2>>));
+    else if (ABLV == 4) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 4>>));
+    else if (ABLV == 8) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 8>>));
+    else if (ABLV == 16) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 16>>));
+    else if (ABLV == 6) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 6>>));
+    else HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0>>));
     return RGCN_OK;
   }
 #endif
-  static bool r0 = false, r1 = false;
-  if (flags & RGCN_F_RELU) HIP_TRY(launch(bwd_own_d16_kernel<true, OWN_NW, OWN_K>, r0));
-  else HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K>, r1));
+  if (flags & RGCN_F_RELU) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<true, OWN_NW, OWN_K>>));
+  else HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K>>));
   return RGCN_OK;
 }
 
@@ -414,33 +400,20 @@ extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const flo
     return RGCN_EUNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = v > 0 ? v : 256;
-  }
-  if (dbias == dW + (size_t)R * 256) {
-    HIP_TRY(zero_async(dW, ((size_t)R * 256 + 16) * sizeof(float), st));
-  } else {
-    HIP_TRY(zero_async(dW, (size_t)R * 256 * sizeof(float), st));
-    if (dbias) HIP_TRY(zero_async(dbias, 16 * sizeof(float), st));
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  HIP_TRY(zero_dw_dbias_async(dW, (size_t)R, dbias, st));
   const size_t lds = bwd_own_lds(tile_rows);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_tiles, n_cu);
-  auto launch = [&](auto kern, bool &raised) -> hipError_t {
-    if (lds > 64 * 1024 && !raised) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, OWN_LDS_MAX);
-      if (e != hipSuccess) return e;
-      raised = true;
-    }
+  auto launch = [&](auto k) -> hipError_t {
+    constexpr auto kern = decltype(k)::value;
+    hipError_t e = allow_lds<kern>(dev, lds, OWN_LDS_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, reinterpret_cast<const float *>(G), reinterpret_cast<const float *>(X),
                        Wt_packed, reinterpret_cast<float *>(dX), dW, static_cast<const char *>(rec), own_ptr, (int)n_tiles, tile_rows, (int)n_dst,
                        dbias, (int)n_src, unit_rel);
     return hipGetLastError();
   };
-  static bool r1 = false;
-  HIP_TRY(launch(bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>, r1));
+  HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>>));
   return RGCN_OK;
 }

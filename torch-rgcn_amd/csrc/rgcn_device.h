@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "rgcn_hip.h"
+#include "rgcn_launch.h"
 #include "rgcn_zero.h"
 
 extern "C" void rgcn_set_error(const char *fmt, ...);

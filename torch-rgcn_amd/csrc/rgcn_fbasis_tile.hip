@@ -1420,19 +1420,6 @@ inline bool tile_shape(int R, int B, int d, long long N, TileShape &s) {
 inline size_t fused_lds(const TileShape &s, int R, int B, int /*gn*/) {
   return ((size_t)((2 * R * B + 3) & ~3) + (size_t)((R * B + 3) & ~3) + (size_t)B * s.ts_f) * 4;
 }
-int n_cus() {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cu = v;
-    else n_cu = 256;
-  }
-  return n_cu;
-}
-template <typename K>
-hipError_t raise_lds(K kernel, size_t bytes) {
-  return bytes > 64 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) : hipSuccess;
-}
 
 }  // namespace
 
@@ -1477,13 +1464,15 @@ int fbasis_tile_fwd(const T *bases, const float *comps, float *Y, const int32_t 
   if (!tile_shape(R, B, d, n_nodes, s) || (mode ? s.lds_fwd_n : s.lds_fwd) > (size_t)LDS_MAX || (mode != 0 && mode != 1)) { rgcn_set_error("fbasis_tile_fwd: shape outside the tile kernel (rgcn_fbasis_tile_supported)"); return RGCN_EUNSUPPORTED; }
   const int n_tiles = (int)((n_nodes + TN - 1) / TN);
   const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % (4 * sizeof(T)) == 0);
-  const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cus()));
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cu));
   hipStream_t st = (hipStream_t)stream;
   if (mode == 1) {                                          // one wave per node, MFMA
     const int ys = pow2_at_least(d, 4);
 #define FBN_FWD3(NK_, KL_, VE_)                                                                                                 \
   {                                                                                                                             \
-    HIP_TRY(raise_lds(fbn_fwd_kernel<NK_, KL_, VE_, T>, s.lds_fwd_n));                                                          \
+    HIP_TRY((allow_lds<fbn_fwd_kernel<NK_, KL_, VE_, T>>(dev, s.lds_fwd_n, LDS_MAX)));                                          \
     hipLaunchKernelGGL((fbn_fwd_kernel<NK_, KL_, VE_, T>), grid, dim3(TW), s.lds_fwd_n, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                        (int)n_nodes, R, B, d, s.ts_f, last, ys, abl);                                                            \
   }
@@ -1499,11 +1488,11 @@ int fbasis_tile_fwd(const T *bases, const float *comps, float *Y, const int32_t 
 #define FBT_FWD3(DP_, NR_, KL_)                                                                                                   \
   {                                                                                                                               \
     if (vec) {                                                                                                                    \
-      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, true, T>, s.lds_fwd));                                                      \
+      HIP_TRY((allow_lds<fbt_fwd_kernel<DP_, NR_, KL_, true, T>>(dev, s.lds_fwd, LDS_MAX)));                                      \
       hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, true, T>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                          (int)n_nodes, R, B, d, s.ts_f, last, abl);                                                                          \
     } else {                                                                                                                      \
-      HIP_TRY(raise_lds(fbt_fwd_kernel<DP_, NR_, KL_, false, T>, s.lds_fwd));                                                     \
+      HIP_TRY((allow_lds<fbt_fwd_kernel<DP_, NR_, KL_, false, T>>(dev, s.lds_fwd, LDS_MAX)));                                     \
       hipLaunchKernelGGL((fbt_fwd_kernel<DP_, NR_, KL_, false, T>), grid, dim3(TW), s.lds_fwd, st, bases, comps, Y, rowptr, e_rel, e_val, n_tiles, \
                          (int)n_nodes, R, B, d, s.ts_f, last, abl);                                                                          \
     }                                                                                                                             \
@@ -1545,13 +1534,11 @@ __global__ __launch_bounds__(1024) void poison_lds_kernel(int n_words) {
 
 extern "C" int rgcn_poison_lds(void *stream) {
   const int bytes = 160 * 1024;
-  static bool raised = false;
-  if (!raised) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    raised = true;
-  }
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  HIP_TRY(allow_lds<poison_lds_kernel>(dev, bytes, bytes));
   // one workgroup per CU holds the whole LDS, so 4 x the CU count of them visit every CU at least once
-  hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)(4 * n_cus())), dim3(1024), bytes, (hipStream_t)stream, bytes / 4);
+  hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)(4 * n_cu)), dim3(1024), bytes, (hipStream_t)stream, bytes / 4);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1569,7 +1556,9 @@ extern "C" int rgcn_gather_rows_sum4_f32(const float *Y, int32_t ys, const int32
   if (n_split) HIP_TRY(zero_async(out, (size_t)n_rows * ow * sizeof(float), st));
   if (n_units == 0) return RGCN_OK;
   const int lpr = ys / 4;
-  const dim3 grid((unsigned)std::min<int64_t>((n_units * lpr + 255) / 256, (int64_t)n_cus() * 64));
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const dim3 grid((unsigned)std::min<int64_t>((n_units * lpr + 255) / 256, (int64_t)n_cu * 64));
   const int4 *un = reinterpret_cast<const int4 *>(units);
   const int vec_out = (ow & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   if (lpr == 1) hipLaunchKernelGGL(gather_rows_sum4_kernel<1>, grid, dim3(256), 0, st, Y, perm, un, bias, out, (long long)n_units, w, ow, relu ? 1 : 0, vec_out);
@@ -1621,7 +1610,9 @@ extern "C" int rgcn_gather_rows_sum4_bf16(const float *Y, int32_t ys, const int3
   }
   if (n_units == 0) return RGCN_OK;
   const int lpr = ys / 4;
-  const dim3 grid((unsigned)std::min<int64_t>((n_units * lpr + 255) / 256, (int64_t)n_cus() * 64));
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const dim3 grid((unsigned)std::min<int64_t>((n_units * lpr + 255) / 256, (int64_t)n_cu * 64));
   const int4 *un = reinterpret_cast<const int4 *>(units);
   const int vec_out = (ow & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
   if (lpr == 1) hipLaunchKernelGGL((gather_rows_sum4_kernel<1, uint16_t>), grid, dim3(256), 0, st, Y, perm, un, bias, out, (long long)n_units, w, ow, relu ? 1 : 0, vec_out);
@@ -1662,15 +1653,17 @@ int fbasis_tile_bwd(const T *bases, const float *comps, const T *G, int32_t g_st
   const int n_tiles = (int)((n_nodes + TN - 1) / TN);
   const size_t al = 4 * sizeof(T);                          // a piece: 16 (fp32) or 8 (bf16) bytes
   const bool vec = ((n_nodes * d) % 4 == 0) && (reinterpret_cast<uintptr_t>(bases) % al == 0) && (!dbases || reinterpret_cast<uintptr_t>(dbases) % al == 0);
-  const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cus()));
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const dim3 grid((unsigned)std::min<int64_t>(n_tiles, n_cu));
   hipStream_t st = (hipStream_t)stream;
 #define FBT_BWD3(KERNEL, LDSB, DPB_, KL_, ...)                                                                            \
   {                                                                                                                       \
     if (vec) {                                                                                                            \
-      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, true, T>, LDSB));                                                               \
+      HIP_TRY((allow_lds<KERNEL<DPB_, KL_, true, T>>(dev, LDSB, LDS_MAX)));                                               \
       hipLaunchKernelGGL((KERNEL<DPB_, KL_, true, T>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                            \
     } else {                                                                                                              \
-      HIP_TRY(raise_lds(KERNEL<DPB_, KL_, false, T>, LDSB));                                                              \
+      HIP_TRY((allow_lds<KERNEL<DPB_, KL_, false, T>>(dev, LDSB, LDS_MAX)));                                              \
       hipLaunchKernelGGL((KERNEL<DPB_, KL_, false, T>), grid, dim3(TW), LDSB, st, __VA_ARGS__);                           \
     }                                                                                                                     \
   }
@@ -1685,7 +1678,7 @@ int fbasis_tile_bwd(const T *bases, const float *comps, const T *G, int32_t g_st
     const size_t lds_f = fused_lds(s, R, B, gn_fused);
 #define FBN_F4(NK_, KL_, VE_, NB_)                                                                                                  \
   {                                                                                                                                 \
-    HIP_TRY(raise_lds(fbn_bwd_kernel<NK_, KL_, VE_, NB_, T>, lds_f));                                                               \
+    HIP_TRY((allow_lds<fbn_bwd_kernel<NK_, KL_, VE_, NB_, T>>(dev, lds_f, LDS_MAX)));                                               \
     hipLaunchKernelGGL((fbn_bwd_kernel<NK_, KL_, VE_, NB_, T>), grid, dim3(TW), lds_f, st, bases, comps, G, dbases, dcomps, rowptr, e_dst, e_rel, e_val, \
                        n_tiles, (int)n_nodes, R, B, d, s.ts_f, last, gstride, gn_fused, abl);                                        \
   }
@@ -1714,10 +1707,10 @@ int fbasis_tile_bwd(const T *bases, const float *comps, const T *G, int32_t g_st
       const int ts_db = two ? 2 * TN * d + 4 : s.ts_f;
       const size_t lds_db = pair ? s.lds_db_n8 : (two ? s.lds_db_n2 : s.lds_db_n);
       const int kld_db = pair ? s.kld8 : (two ? s.kld2 : s.kld);
-      const dim3 grid_db((unsigned)std::min<int64_t>(tiles_db, (int64_t)n_cus() * (pair ? 2 : 1)));
+      const dim3 grid_db((unsigned)std::min<int64_t>(tiles_db, (int64_t)n_cu * (pair ? 2 : 1)));
 #define FBN_DB3(NK_, KL_, VE_, NP_, NW_)                                                                                          \
   {                                                                                                                               \
-    HIP_TRY(raise_lds(fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_, T>, lds_db));                                                     \
+    HIP_TRY((allow_lds<fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_, T>>(dev, lds_db, LDS_MAX)));                                     \
     hipLaunchKernelGGL((fbn_dbases_kernel<NK_, KL_, VE_, NP_, NW_, T>), grid_db, dim3(64 * NW_), lds_db, st, comps, G, dbases, rowptr, e_dst, e_rel, \
                        e_val, tiles_db, (int)n_nodes, R, B, d, ts_db, last, gstride, abl);                                                  \
   }

@@ -30,4 +30,12 @@ inline hipError_t zero_async(void *ptr, size_t bytes, hipStream_t st) {
   return hipGetLastError();
 }
 
+// dW [R][16][16] and dbias [16] (may be null) of a hidden-16 backward: one fill for both when the caller laid them out back to back
+inline hipError_t zero_dw_dbias_async(float *dW, size_t R, float *dbias, hipStream_t st) {
+  if (dbias == dW + R * 256) return zero_async(dW, (R * 256 + 16) * sizeof(float), st);
+  hipError_t e = zero_async(dW, R * 256 * sizeof(float), st);
+  if (e != hipSuccess || !dbias) return e;
+  return zero_async(dbias, 16 * sizeof(float), st);
+}
+
 }  // namespace

@@ -1402,6 +1402,13 @@ _BLK_MIN_NODES = 32768      # below: a tile per workgroup leaves most CUs idle; 
 _BLK_MIN_NODES_SPARSE = 4096   # graphs with sparse (tile, relation) buckets: the alternative is the two-pass backward (three launches)
 
 
+def _even_tile_rows(n_nodes, cap, device):
+    """the tallest tile of at most `cap` rows that gives every CU of `device` the same number of tiles"""
+    n_cu = torch.cuda.get_device_properties(device if device is not None else torch.cuda.current_device()).multi_processor_count
+    per_cu = -(-n_nodes // (n_cu * cap))
+    return -(-n_nodes // (n_cu * per_cu))
+
+
 def bwd_blk_rows(n_nodes, num_rels, deterministic=False, device=None, diag4=False, sparse=False):
     """tile height of the transposed plan for the block-tile backward kernel (rgcn_bwd_blk_f32), 0 when it does not apply:
     the tallest tile the kernel's LDS holds next to the relations' dW (rgcn_bwd_blk_max_rows: 192 bytes per row) that gives every CU
@@ -1413,10 +1420,7 @@ def bwd_blk_rows(n_nodes, num_rels, deterministic=False, device=None, diag4=Fals
     cap = min(cap, int(routes.get("bwd_blk_cap", "512")))
     if cap < 64:
         return 0
-    n_cu = torch.cuda.get_device_properties(device if device is not None else torch.cuda.current_device()).multi_processor_count
-    per_cu = -(-n_nodes // (n_cu * cap))
-    rows = -(-n_nodes // (n_cu * per_cu))
-    return max(rows, min(cap, 128))      # small graphs: fewer, taller tiles (fuller buckets, fewer dW flushes) rather than one per CU
+    return max(_even_tile_rows(n_nodes, cap, device), min(cap, 128))      # small graphs: fewer, taller tiles (fuller buckets, fewer dW flushes) rather than one per CU
 
 
 def poison_lds(device=None):
@@ -1432,9 +1436,7 @@ def spmm_blk_rows(n_nodes, device=None):
     if n_nodes < _BLK_MIN_NODES or routes.get("spmm_csr", "1") == "0":
         return 0
     cap = min(1000, int(lib().rgcn_spmm_blk_max_rows()), int(routes.get("fwd_rows_cap", "1000")))
-    n_cu = torch.cuda.get_device_properties(device if device is not None else torch.cuda.current_device()).multi_processor_count
-    per_cu = -(-n_nodes // (n_cu * cap))
-    return -(-n_nodes // (n_cu * per_cu))
+    return _even_tile_rows(n_nodes, cap, device)
 
 
 def spmm_blk(X, W, bias, plan, relu=False):
@@ -1597,18 +1599,16 @@ def bwd_own_geometry():
 
 def bwd_own_rows(n_nodes, device=None):
     """tile height of the relation-owner backward's plan: the tallest tile the kernel's LDS holds that gives every CU the same number of
-    tiles (S1: 782 rows, 5 tiles per CU); 0 for graphs too small to fill the chip with one tile per workgroup"""
+    tiles (S1: 652 rows, 6 tiles per CU); 0 for graphs too small to fill the chip with one tile per workgroup"""
     if n_nodes < _BLK_MIN_NODES:
         return 0
-    cap = min(bwd_own_geometry()[2], int(routes.get("own_rows_cap", "789")))
-    n_cu = torch.cuda.get_device_properties(device if device is not None else torch.cuda.current_device()).multi_processor_count
-    per_cu = -(-n_nodes // (n_cu * cap))
-    return -(-n_nodes // (n_cu * per_cu))
+    cap = min(bwd_own_geometry()[2], int(routes.get("own_rows_cap", "767")))
+    return _even_tile_rows(n_nodes, cap, device)
 
 
 def bwd_own(G, X, W, plan, relu=False, want_db=False):
     """(dX, dW[, db]) of the hidden-16 layer from one walk of a soft-window plan with relation ownership (build_softwin_plan(own_waves=...)):
-    rgcn_bwd_own_f32 -- dX tile in LDS doubles, every relation's dW in the registers of its owner wave, X rows of the tile from global memory.
+    rgcn_bwd_own_f32 -- dX tile in LDS doubles, every relation's dW in the registers of its owner wave, the X rows of the tile in LDS next to it.
     relu: X is the output of a ReLU and dX is wanted BEFORE it.  Sums in arrival order (not bit-reproducible)."""
     _req(G, "grad_output"); _req(X, "features"); _req(W, "weights")
     assert W.shape[1:] == (16, 16) and G.shape == (plan.n_src, 16) and X.shape == (plan.n_dst, 16) and W.shape[0] == plan.num_rels
