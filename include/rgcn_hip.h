@@ -752,6 +752,30 @@ RGCN_API int rgcn_distmult_bwd_all_f32(const int32_t *rowptr_s, const int32_t *r
                                        const float *rel, float *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
                                        int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
+/* DistMult on a bf16 entity table: `nodes` holds bf16 rows, `rel`, the biases, the scores and every parameter gradient
+ * are fp32, every product and sum is fp32, `dnodes` is the fp32 row sum rounded to bf16 once (nearest even) and fully written.  No entry
+ * allocates or synchronises.
+ * rgcn_distmult_fwd_bf16: rgcn_distmult_fwd_f32 (layers.py:86-98), the CSR counting pass riding along in the same way.
+ * rgcn_distmult_bwd_all_bf16: rgcn_distmult_bwd_all_f32 (the autograd dual of layers.py:87-101) in ONE launch -- both CSR sides of an
+ * entity are summed in the registers of its wave before the one rounding (the fp32 entry's two launches meet in the dnodes rows, which
+ * bf16 rows cannot carry unrounded); same LDS table of doubles, same n_rel (d + 1) <= 4096.
+ * rgcn_distmult_bwd_nodes_bf16: rgcn_distmult_bwd_nodes_f32.
+ * rgcn_distmult_bwd_rel_bf16: relation and bias gradients only, from predicate-sorted triples (rgcn_distmult_bwd_f32 with dnodes = NULL):
+ * for relation tables beyond the LDS table; drel / the bias gradients are zeroed first and summed with fp32 atomics.
+ * rgcn_distmult_csr_place serves both storage types. */
+RGCN_API int rgcn_distmult_fwd_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                    const float *sbias, const float *pbias, const float *obias, float *scores,
+                                    int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
+                                    int32_t *ranks, void *stream);
+RGCN_API int rgcn_distmult_bwd_all_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                        const float *rel, uint16_t *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                        int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_bwd_nodes_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                          const float *rel, uint16_t *dnodes, int64_t n_nodes, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_bwd_rel_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                        const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                        int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+
 /* Ranking evaluator (utils/misc.py:60-110 + torch_rgcn/layers.py:87-98 on the expanded
  * [bn, N, 3] candidate tensor, which is never built here).  For each of the Q test triples in `batch` (int64
  * [Q,3], device) every entity n is scored as its head (head != 0: (n, p, o)) or tail ((s, p, n)):
@@ -762,6 +786,18 @@ RGCN_API int rgcn_distmult_score_all_f32(const int64_t *batch, int64_t Q, int32_
                                          const float *rel, const float *sbias, const float *pbias,
                                          const float *obias, float *qvec, float *qbias, float *scores,
                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* The same scores (utils/misc.py:71-88, layers.py:87-98) from a bf16 entity table on v_mfma_f32_16x16x32_bf16: nodes bf16 [n_nodes, d],
+ * rel and the biases fp32, scores fp32.  The query vector nodes[fixed_q] * rel[p_q] is an fp32 number and is not rounded: it is
+ * written to `qsplit` as three bf16 terms hi + mid + lo that sum to it exactly, and every bf16 x bf16 product is exact in fp32 -- the
+ * kernel adds what rgcn_distmult_score_all_f32 adds on the widened table, in another order.  (The product is the rounded fp32 one: the
+ * query kernel is compiled with contraction off.  A finite element above the largest bf16 takes hi = the largest bf16, not inf; an inf or
+ * NaN element is its own hi with mid = lo = 0.)  qsplit: caller-provided scratch of
+ * rgcn_distmult_score_all_bf16_workspace_bytes(Q, d) bytes ([3][Q][d rounded up to 32] bf16), 16-byte aligned; qbias [2Q] as above. */
+RGCN_API int64_t rgcn_distmult_score_all_bf16_workspace_bytes(int64_t Q, int32_t d);
+RGCN_API int rgcn_distmult_score_all_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes,
+                                          const float *rel, const float *sbias, const float *pbias,
+                                          const float *obias, uint16_t *qsplit, float *qbias, float *scores,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 /* filter_scores (utils/misc.py:40-58): scores[filt_q[e], filt_n[e]] = -inf for the F known true completions that
  * are not the target (list built by the caller; duplicates allowed). */
 RGCN_API int rgcn_rank_filter_f32(float *scores, int64_t Q, int64_t n_nodes, const int32_t *filt_q,

@@ -2,7 +2,9 @@
 """Ranking evaluation at WN18 size: N = 40,943 entities, d = 200, 5,000 test triples (10,000 head /
 tail queries), filtered against ~150k known triples.  Prints one JSON line: whole evaluate() wall time, the score-all
 kernel's MFMA roofline, and the CPU oracle (reference algorithm, numpy) on a bounded sample.
-    python tools/eval_bench.py [--test 5000] [--cpu-sample 48] [--no-cpu]"""
+    python tools/eval_bench.py [--test 5000] [--cpu-sample 48] [--no-cpu] [--bf16]
+--bf16: the entity table is rounded to bf16 and, in the same process, the fp32 evaluator on the widened table is measured against the bf16
+evaluator on the bf16 table (launches alternate): "bf16" in the result."""
 import argparse
 import json
 import os
@@ -39,11 +41,34 @@ def main():
     ap.add_argument("--test", type=int, default=5000)
     ap.add_argument("--cpu-sample", type=int, default=48)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--bf16", action="store_true")
     a = ap.parse_args()
-    print(json.dumps(run(a.test, 0 if a.no_cpu else a.cpu_sample)), flush=True)
+    print(json.dumps(run(a.test, 0 if a.no_cpu else a.cpu_sample, a.bf16)), flush=True)
 
 
-def run(test=5000, cpu_sample=48):
+def bf16_against_fp32(batch, x, rel, out, launches=10):
+    """x: the widened bf16 table.  -> per-launch medians of the fp32 evaluator on x and of the bf16 evaluator on x.bfloat16(), taking turns"""
+    xb = x.to(torch.bfloat16)
+    runs = {"score_all": lambda: _native.distmult_score_all(batch, True, x, rel, out=out),
+            "distmult_score_all_bf16": lambda: _native.distmult_score_all_bf16(batch, True, xb, rel, out=out)}
+    for r in runs.values():
+        for _ in range(3):
+            r()
+    torch.cuda.synchronize()
+    _native.profile_start()
+    for _ in range(launches):
+        for r in runs.values():
+            r()
+    torch.cuda.synchronize()
+    ks = {k: float(np.median(v)) for k, v in _native.profile_stop().items()}
+    a = runs["score_all"]().double()                   # (a copy: both write `out`)
+    b = runs["distmult_score_all_bf16"]().double()
+    return {"fp32_on_widened_ms": round(ks["score_all"], 4), "bf16_ms": round(ks["distmult_score_all_bf16"], 4),
+            "bf16_speedup": round(ks["score_all"] / ks["distmult_score_all_bf16"], 3),
+            "max_abs_difference_over_max_score": float((a - b).abs().max() / a.abs().max())}
+
+
+def run(test=5000, cpu_sample=48, bf16=False):
     """-> the result dict (bench.py's detail file carries it as the evaluator line: tools/config_bench.py line_eval)"""
     import types
     a = types.SimpleNamespace(test=test, cpu_sample=cpu_sample, no_cpu=cpu_sample <= 0)
@@ -51,6 +76,8 @@ def run(test=5000, cpu_sample=48):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     x = torch.randn(N, d, device=dev)
+    if bf16:
+        x = x.to(torch.bfloat16).float()
     dm = DistMult(R0, d, N, R0).to(dev)
     test = _native.synthetic_triples_host(N, R0, Q, 5)
     known = _native.synthetic_triples_host(N, R0, 146_442, 6)
@@ -85,6 +112,8 @@ def run(test=5000, cpu_sample=48):
            "roofline": {"kernel": "score_all_lds_kernel<true> (+ rank_query_kernel)", "bound": "mfma", "achieved": round(flops / (k_ms * 1e-3) / 1e12, 2),
                         "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(flops / (k_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
                         "avg_launch_ms": round(k_ms, 4), "flops_per_launch": flops, "traffic": None}}
+    if bf16:
+        res["bf16"] = bf16_against_fp32(batch, x, dm.relations.detach(), out)
     if not a.no_cpu:
         from oracle import oracle
         xs, rel = x.cpu().numpy(), dm.relations.detach().cpu().numpy()

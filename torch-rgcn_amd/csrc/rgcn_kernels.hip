@@ -1205,6 +1205,9 @@ __global__ __launch_bounds__(WG) void colsum_b_kernel(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ DistMult
+// BF (here and in the two backward kernels below): the entity table `nodes` holds bf16 rows behind the float pointer --
+// 8-byte quarter rows when d % 4 == 0, 2-byte elements otherwise; the relation table, the biases, the scores and every sum stay fp32.
+template <bool BF = false>
 __global__ __launch_bounds__(WG) void distmult_fwd_kernel(
     const long long *__restrict__ tr, long long T, const float *__restrict__ nodes, const float *__restrict__ rel,
     const float *__restrict__ sb, const float *__restrict__ pb, const float *__restrict__ ob,
@@ -1225,7 +1228,19 @@ __global__ __launch_bounds__(WG) void distmult_fwd_kernel(
     if (counts && lane == 0) { rk_s = atomicAdd(counts + 1 + s, 1); rk_o = atomicAdd(counts + n_nodes + 2 + o, 1); }
     const float *ns = nodes + (size_t)s * d, *rp = rel + (size_t)p * d, *no = nodes + (size_t)o * d;
     float a = 0.f;
-    if (vec) {                                            // 16-byte pieces (d % 4 == 0, aligned tables): a 200-wide row is ONE load of 50 lanes instead of four passes of 64
+    if constexpr (BF) {
+      const uint16_t *hs = reinterpret_cast<const uint16_t *>(nodes) + (size_t)s * d, *ho = reinterpret_cast<const uint16_t *>(nodes) + (size_t)o * d;
+      if (vec) {
+        for (int j = 4 * lane; j < d; j += 256) {
+          const float4 x = bf16x4_widen(*reinterpret_cast<const uint2 *>(hs + j)), y = bf16x4_widen(*reinterpret_cast<const uint2 *>(ho + j));
+          const f32x4 w = *reinterpret_cast<const f32x4 *>(rp + j);
+          const f32x4 q = f32x4{x.x, x.y, x.z, x.w} * w * f32x4{y.x, y.y, y.z, y.w};
+          a += (q[0] + q[1]) + (q[2] + q[3]);
+        }
+      } else {
+        for (int j = lane; j < d; j += 64) a += bf16_widen(hs[j]) * rp[j] * bf16_widen(ho[j]);
+      }
+    } else if (vec) {                                            // 16-byte pieces (d % 4 == 0, aligned tables): a 200-wide row is ONE load of 50 lanes instead of four passes of 64
       for (int j = 4 * lane; j < d; j += 256) {
         const f32x4 x = *reinterpret_cast<const f32x4 *>(ns + j), w = *reinterpret_cast<const f32x4 *>(rp + j),
                     y = *reinterpret_cast<const f32x4 *>(no + j);
@@ -1248,6 +1263,7 @@ __global__ __launch_bounds__(WG) void distmult_fwd_kernel(
 // Each wave walks 64 consecutive triples.  The relation gradient is accumulated in registers while the
 // predicate stays the same and flushed with one atomic per (run, feature): callers that sort the triples by
 // predicate (functional.py does) turn T*d contended atomics on R*d addresses into ~(T/64 + R)*d.
+template <bool BF = false>
 __global__ __launch_bounds__(WG) void distmult_bwd_kernel(
     const long long *__restrict__ tr, long long T, const float *__restrict__ nodes, const float *__restrict__ rel,
     const float *__restrict__ gs, float *__restrict__ dnodes, float *__restrict__ drel, float *__restrict__ dsb,
@@ -1277,8 +1293,15 @@ __global__ __launch_bounds__(WG) void distmult_bwd_kernel(
         for (int q = 0; q < 4; ++q) {
           const int j = i0 + q * 64 + lane;
           if (j < d) {
-            const float a = nodes[(size_t)s * d + j], b = rel[(size_t)p * d + j], c = nodes[(size_t)o * d + j];
-            if (!skip_nodes) {
+            float a, b, c;
+            if constexpr (BF) {       // (relation and bias gradients only: bf16 rows are never accumulated with atomics)
+              a = bf16_widen(reinterpret_cast<const uint16_t *>(nodes)[(size_t)s * d + j]);
+              b = rel[(size_t)p * d + j];
+              c = bf16_widen(reinterpret_cast<const uint16_t *>(nodes)[(size_t)o * d + j]);
+            } else {
+              a = nodes[(size_t)s * d + j], b = rel[(size_t)p * d + j], c = nodes[(size_t)o * d + j];
+            }
+            if (!BF && !skip_nodes) {
               atomicAdd(&dnodes[(size_t)s * d + j], g * b * c);
               atomicAdd(&dnodes[(size_t)o * d + j], g * b * a);
             }
@@ -1330,7 +1353,9 @@ __global__ __launch_bounds__(WG) void distmult_bwd_kernel(
 // VEC: d is a multiple of 4 -- every lane loads whole float4s without a branch (lanes past the row's end from feature 0, and keep nothing).
 // TABLE = false: entity gradients only (relation tables too large for the LDS: the predicate-sorted kernel above does the rest); SIDES = 3.
 // Entries: int4 {other end, predicate, score gradient (bits), -} -- one 16-byte load per lane (rgcn_distmult_csr_place writes them).
-template <int SIDES, bool VEC, bool TABLE>
+// BF: bf16 entity rows in, the row sum rounded to bf16 once on the way out -- SIDES = 3 only: both sides of an entity meet in the
+// registers of its wave, not in the dnodes row as the two fp32 launches do.
+template <int SIDES, bool VEC, bool TABLE, bool BF = false>
 __global__ __launch_bounds__(WG) void distmult_bwd_all_kernel(
     const int *__restrict__ rp_s, const int *__restrict__ rp_o, const int4 *__restrict__ entries, const float *__restrict__ nodes,
     const float *__restrict__ rel, float *__restrict__ dnodes, float *__restrict__ drel, float *__restrict__ dsb,
@@ -1358,8 +1383,25 @@ __global__ __launch_bounds__(WG) void distmult_bwd_all_kernel(
           if (f + q < d) v[q] = row[f + q];
         return v;
       };
+      auto node4 = [&](long long row) -> f32x4 {       // features f .. f + 3 of an entity's row
+        if constexpr (BF) {
+          const uint16_t *h = reinterpret_cast<const uint16_t *>(nodes) + (size_t)row * d;
+          if (VEC) {
+            const float4 t = bf16x4_widen(*reinterpret_cast<const uint2 *>(h + fc));
+            return f32x4{t.x, t.y, t.z, t.w};
+          }
+          f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (f + q < d) v[q] = bf16_widen(h[f + q]);
+          return v;
+        } else {
+          return load4(nodes + (size_t)row * d);
+        }
+      };
+      static_assert(!BF || SIDES == 3, "bf16 rows: one launch for both sides");
       float *o = dnodes + (size_t)n * d;
-      const f32x4 xn = load4(nodes + (size_t)n * d);
+      const f32x4 xn = node4(n);
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       if (SIDES == 1) acc = load4(o);                  // the object-side launch wrote this row
 #pragma unroll
@@ -1381,7 +1423,7 @@ __global__ __launch_bounds__(WG) void distmult_bwd_all_kernel(
               const int oe = __builtin_amdgcn_readlane(mo, j + u);
               pe[u] = __builtin_amdgcn_readlane(mr, j + u);
               ge[u] = __int_as_float(__builtin_amdgcn_readlane(mg, j + u));
-              xe[u] = load4(nodes + (size_t)oe * d);
+              xe[u] = node4(oe);
               we[u] = load4(rel + (size_t)pe[u] * d);
             }
 #pragma unroll
@@ -1401,7 +1443,16 @@ __global__ __launch_bounds__(WG) void distmult_bwd_all_kernel(
         }
         if (f0 == 0 && lane == 0 && dsb) (side ? dob : dsb)[n] = gsum;
       }
-      if (VEC) {
+      if constexpr (BF) {
+        uint16_t *oh = reinterpret_cast<uint16_t *>(dnodes) + (size_t)n * d;
+        if (VEC) {
+          if (act) *reinterpret_cast<uint2 *>(oh + f) = bf16x4_round(make_float4(acc[0], acc[1], acc[2], acc[3]));
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (f + q < d) oh[f + q] = bf16_round(acc[q]);
+        }
+      } else if (VEC) {
         if (act) *reinterpret_cast<f32x4 *>(o + f) = acc;
       } else {
 #pragma unroll
@@ -1998,7 +2049,7 @@ extern "C" int rgcn_distmult_fwd_f32(const int64_t *triples, int64_t T, const fl
   if (rank_counts) HIP_TRY(zero_async(rank_counts, (size_t)(2 * n_nodes + 3) * sizeof(int32_t), (hipStream_t)stream));
   if (T == 0) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((T + 3) / 4, 256 * 32);
-  hipLaunchKernelGGL(distmult_fwd_kernel, dim3(gx), dim3(WG), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(distmult_fwd_kernel<false>, dim3(gx), dim3(WG), 0, (hipStream_t)stream,
                      reinterpret_cast<const long long *>(triples), (long long)T, nodes, rel, sbias, pbias, obias,
                      scores, d, (long long)n_nodes, n_rel, err_flag, rank_counts, ranks,
                      (int)((d & 3) == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(rel)) & 15) == 0));
@@ -2022,7 +2073,7 @@ extern "C" int rgcn_distmult_bwd_f32(const int64_t *triples, int64_t T, const fl
   }
   if (T == 0) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((T + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(distmult_bwd_kernel, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples),
+  hipLaunchKernelGGL(distmult_bwd_kernel<false>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples),
                      (long long)T, nodes, rel, gs, dnodes, drel, dsbias, dpbias, dobias, d, (long long)n_nodes, n_rel, dnodes ? 0 : 1);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -2069,6 +2120,90 @@ extern "C" int rgcn_distmult_bwd_nodes_f32(const int32_t *rowptr_s, const int32_
   };
   if (d % 4 == 0) go(distmult_bwd_all_kernel<3, true, false>);
   else go(distmult_bwd_all_kernel<3, false, false>);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+// ------------------------------------------------------------------ DistMult on a bf16 entity table
+// reference lines as their fp32 twins above: layers.py:86-98 (forward) and its autograd dual
+extern "C" int rgcn_distmult_fwd_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                      const float *sbias, const float *pbias, const float *obias, float *scores,
+                                      int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
+                                      int32_t *ranks, void *stream) {
+  if (T < 0 || d <= 0 || (T && (!triples || !nodes || !rel || !scores)) || (rank_counts != nullptr) != (ranks != nullptr) ||
+      (rank_counts && (n_nodes <= 0 || 2 * T > INT32_MAX))) { rgcn_set_error("distmult_fwd_bf16: bad argument"); return RGCN_EINVAL; }
+  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) { rgcn_set_error("distmult_fwd_bf16: biases must be all set or all NULL"); return RGCN_EINVAL; }
+  if (err_flag) HIP_TRY(zero_async(err_flag, sizeof(int32_t), (hipStream_t)stream));
+  if (rank_counts) HIP_TRY(zero_async(rank_counts, (size_t)(2 * n_nodes + 3) * sizeof(int32_t), (hipStream_t)stream));
+  if (T == 0) return RGCN_OK;
+  const unsigned gx = (unsigned)std::min<int64_t>((T + 3) / 4, 256 * 32);
+  // quarter rows: 8 bytes of the entity table, 16 of the relation table
+  const int vec = (d & 3) == 0 && (reinterpret_cast<uintptr_t>(nodes) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0;
+  hipLaunchKernelGGL(distmult_fwd_kernel<true>, dim3(gx), dim3(WG), 0, (hipStream_t)stream,
+                     reinterpret_cast<const long long *>(triples), (long long)T, reinterpret_cast<const float *>(nodes), rel, sbias, pbias, obias,
+                     scores, d, (long long)n_nodes, n_rel, err_flag, rank_counts, ranks, vec);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_distmult_bwd_all_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                          const float *rel, uint16_t *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || !drel || n_nodes < 0 || d <= 0 || n_rel <= 0) { rgcn_set_error("distmult_bwd_all_bf16: bad argument"); return RGCN_EINVAL; }
+  if ((dsbias != nullptr) != (dpbias != nullptr) || (dsbias != nullptr) != (dobias != nullptr)) { rgcn_set_error("distmult_bwd_all_bf16: bias gradients must be all set or all NULL"); return RGCN_EINVAL; }
+  if (!rgcn_distmult_bwd_all_supported(n_rel, d)) { rgcn_set_error("distmult_bwd_all_bf16: n_rel (d + 1) = %lld floats do not fit the LDS table (4096)", (long long)n_rel * (d + 1)); return RGCN_EUNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
+  if (dpbias) HIP_TRY(zero_async(dpbias, (size_t)n_rel * sizeof(float), st));
+  if (!n_nodes) return RGCN_OK;
+  const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 1024);
+  const size_t lds = ((size_t)n_rel * 4 * ((d + 3) / 4) + n_rel) * sizeof(double);
+  const int4 *en = reinterpret_cast<const int4 *>(entries);
+  auto go = [&](auto k) {
+    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), lds, st, rowptr_s, rowptr_o, en, reinterpret_cast<const float *>(nodes), rel,
+                       reinterpret_cast<float *>(dnodes), drel, dsbias, dpbias, dobias, (long long)n_nodes, n_rel, d);
+  };
+  // quarter rows: 8 bytes of the entity table and of dnodes, 16 of the relation table (as rgcn_distmult_fwd_bf16)
+  if (d % 4 == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(dnodes)) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0)
+    go(distmult_bwd_all_kernel<3, true, true, true>);
+  else go(distmult_bwd_all_kernel<3, false, true, true>);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_distmult_bwd_nodes_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                            const float *rel, uint16_t *dnodes, int64_t n_nodes, int32_t d, void *stream) {
+  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || n_nodes < 0 || d <= 0) { rgcn_set_error("distmult_bwd_nodes_bf16: bad argument"); return RGCN_EINVAL; }
+  if (!n_nodes) return RGCN_OK;
+  const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 256 * 32);
+  const int4 *en = reinterpret_cast<const int4 *>(entries);
+  auto go = [&](auto k) {
+    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), 0, (hipStream_t)stream, rowptr_s, rowptr_o, en, reinterpret_cast<const float *>(nodes), rel,
+                       reinterpret_cast<float *>(dnodes), (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (long long)n_nodes, 0, d);
+  };
+  if (d % 4 == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(dnodes)) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0)
+    go(distmult_bwd_all_kernel<3, true, false, true>);
+  else go(distmult_bwd_all_kernel<3, false, false, true>);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_distmult_bwd_rel_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                          const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  if (T < 0 || d <= 0 || n_nodes < 0 || n_rel <= 0 || !drel || (T && (!triples || !nodes || !rel || !gs))) { rgcn_set_error("distmult_bwd_rel_bf16: bad argument"); return RGCN_EINVAL; }
+  if ((dsbias != nullptr) != (dpbias != nullptr) || (dsbias != nullptr) != (dobias != nullptr)) { rgcn_set_error("distmult_bwd_rel_bf16: bias gradients must be all set or all NULL"); return RGCN_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
+  if (dsbias) {
+    HIP_TRY(zero_async(dsbias, (size_t)n_nodes * sizeof(float), st));
+    HIP_TRY(zero_async(dobias, (size_t)n_nodes * sizeof(float), st));
+    HIP_TRY(zero_async(dpbias, (size_t)n_rel * sizeof(float), st));
+  }
+  if (T == 0) return RGCN_OK;
+  const unsigned gx = (unsigned)std::min<int64_t>((T + 255) / 256, 256 * 32);
+  hipLaunchKernelGGL(distmult_bwd_kernel<true>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples),
+                     (long long)T, reinterpret_cast<const float *>(nodes), rel, gs, (float *)nullptr, drel, dsbias, dpbias, dobias, d, (long long)n_nodes, n_rel, 1);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

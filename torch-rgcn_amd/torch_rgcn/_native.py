@@ -2154,3 +2154,104 @@ def distmult_bwd_nodes(triples, ranks, nodes, rel, gs):
         _check(lib().rgcn_distmult_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d,
                                                  _stream(dev)), "distmult_bwd_nodes")
     return dn
+
+
+# ----------------------------------------------------------------------------- DistMult on a bf16 entity table
+# nodes bf16; the relation table, the biases, the scores and the parameter gradients fp32 (bf16 parameters are widened by the caller,
+# once per call); dnodes bf16, an fp32 sum per entity rounded once.
+
+
+def _req_distmult_bf16(nodes, rel, sbias, pbias, obias):
+    _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
+    if (sbias is None) != (pbias is None) or (sbias is None) != (obias is None):
+        raise AssertionError("DistMult biases must be all set or all None")
+    for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
+        _req(b, n)
+    assert nodes.dim() == 2 and rel.dim() == 2 and rel.shape[1] == nodes.shape[1], "relation and node embeddings differ in width"
+
+
+def distmult_fwd_bf16(triples, nodes, rel, sbias, pbias, obias, ranks=False):
+    """distmult_fwd for bf16 nodes: fp32 scores [T]; ranks=True as there (the CSR counting pass rides along)"""
+    _req_distmult_bf16(nodes, rel, sbias, pbias, obias); _req(triples, "triples", torch.int64)
+    T = triples.shape[0]
+    scores = torch.empty(T, device=nodes.device, dtype=torch.float32)
+    err = _i32(1, nodes.device)
+    counts = rk = None
+    if ranks and T:
+        counts, rk = _i32(2 * nodes.shape[0] + 3, nodes.device), _i32(2 * T, nodes.device)
+    with _on(nodes.device), _timed("distmult_fwd_bf16"):
+        _check(lib().rgcn_distmult_fwd_bf16(_dp(triples), T, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                            _dp(scores), nodes.shape[0], rel.shape[0], nodes.shape[1], _dp(err),
+                                            _dp(counts), _dp(rk), _stream(nodes.device)), "distmult_fwd_bf16")
+    dev_check_err(err, "DistMult triples (s, o < num_nodes, p < num_relations)", IndexError)
+    return (scores, [counts, rk, False]) if ranks else scores
+
+
+def distmult_bwd_all_bf16(triples, ranks, nodes, rel, gs, with_bias):
+    """distmult_bwd_all for bf16 nodes: (dnodes bf16, drel, dsbias, dpbias, dobias fp32) from ONE walk of the two CSRs"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
+    N, d = nodes.shape
+    R = rel.shape[0]
+    dev = nodes.device
+    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
+    dn, dr = torch.empty_like(nodes), torch.empty_like(rel)
+    dsb = dpb = dob = None
+    if with_bias:
+        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
+        dpb = torch.empty(R, device=dev, dtype=torch.float32)
+    with _on(dev), _timed("distmult_bwd_all_bf16"):
+        _check(lib().rgcn_distmult_bwd_all_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), _dp(dr), _dp(dsb),
+                                                _dp(dpb), _dp(dob), N, R, d, _stream(dev)), "distmult_bwd_all_bf16")
+    return dn, dr, dsb, dpb, dob
+
+
+def distmult_bwd_nodes_bf16(triples, ranks, nodes, rel, gs):
+    """distmult_bwd_nodes for bf16 nodes: the entity gradients, bf16, every row written"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
+    N, d = nodes.shape
+    dev = nodes.device
+    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
+    dn = torch.empty_like(nodes)
+    with _on(dev), _timed("distmult_bwd_nodes_bf16"):
+        _check(lib().rgcn_distmult_bwd_nodes_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d,
+                                                  _stream(dev)), "distmult_bwd_nodes_bf16")
+    return dn
+
+
+def distmult_bwd_rel_bf16(triples, nodes, rel, gs, with_bias):
+    """(drel, dsbias, dpbias, dobias), fp32, from predicate-sorted triples and bf16 nodes: the relation tables the LDS table of
+    distmult_bwd_all_bf16 does not hold; the entity gradients come from distmult_bwd_nodes_bf16"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations"); _req(triples, "triples", torch.int64)
+    N, R, dev = nodes.shape[0], rel.shape[0], nodes.device
+    dr = torch.empty_like(rel)
+    dsb = dpb = dob = None
+    if with_bias:
+        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
+        dpb = torch.empty(R, device=dev, dtype=torch.float32)
+    with _on(dev), _timed("distmult_bwd_rel_bf16"):
+        _check(lib().rgcn_distmult_bwd_rel_bf16(_dp(triples), triples.shape[0], _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb),
+                                                _dp(dpb), _dp(dob), N, R, nodes.shape[1], _stream(dev)), "distmult_bwd_rel_bf16")
+    return dr, dsb, dpb, dob
+
+
+def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None):
+    """distmult_score_all for bf16 nodes [N, d] (rel and biases fp32): fp32 scores [Q, N] on the bf16 matrix instructions, the fp32
+    query vectors carried as three bf16 terms -- the sums of the fp32 evaluator on the widened table, in another order.  The C entry does not
+    range-check the triples on the device (neither does the fp32 one): this wrapper does, and raises IndexError; whoever calls
+    rgcn_distmult_score_all_bf16 directly passes entities in [0, N) and predicates in [0, n_rel)"""
+    _req_distmult_bf16(nodes, rel, sbias, pbias, obias); _req(batch, "batch", torch.int64)
+    Q, (N, d) = batch.shape[0], nodes.shape
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    if Q:
+        lo, hi = batch.amin(0), batch.amax(0)
+        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
+            raise IndexError("triple index out of range")
+    scores = out if out is not None else torch.empty(Q, N, device=nodes.device, dtype=torch.float32)
+    assert scores.shape == (Q, N) and scores.is_contiguous() and scores.dtype == torch.float32
+    qsplit = torch.empty(max(int(lib().rgcn_distmult_score_all_bf16_workspace_bytes(Q, d)), 16), device=nodes.device, dtype=torch.uint8)
+    qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
+    with _on(nodes.device), _timed("distmult_score_all_bf16"):
+        _check(lib().rgcn_distmult_score_all_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias),
+                                                  _dp(pbias), _dp(obias), _dp(qsplit), _dp(qb), _dp(scores), N,
+                                                  rel.shape[0], d, _stream(nodes.device)), "distmult_score_all_bf16")
+    return scores

@@ -1179,8 +1179,69 @@ class _DistMultScore(torch.autograd.Function):
         return None, dn, dr, dsb, dpb, dob
 
 
+class _DistMultScoreBF16(torch.autograd.Function):
+    """_DistMultScore on bf16 node embeddings: relations and biases arrive as fp32 (distmult_score widened bf16 parameters),
+    scores are fp32, dnodes is bf16 -- an fp32 sum per entity rounded once --, the parameter gradients fp32.  Routes as in fp32: csr = every
+    gradient from one walk of the two CSRs where the relation table fits the LDS, else split = entity gradients from the CSRs + the
+    predicate-sorted kernel for relations and biases.  atomic (RGCN_DISTMULT_BWD=atomic) is CORRECTNESS ONLY: bf16 is never accumulated
+    with atomics, so the fp32 scatter kernel runs on the widened table and its dnodes is rounded once."""
+
+    @staticmethod
+    def forward(ctx, triples, nodes, relations, sbias, pbias, obias):
+        shape = triples.shape[:-1]
+        tr = triples.reshape(-1, 3).contiguous()
+        nodes = dense(nodes)
+        relations = dense(relations)
+        ctx.ranks = None
+        if any(ctx.needs_input_grad[1:]) and tr.shape[0] and routes.get("distmult_bwd", "csr") != "atomic":
+            scores, ctx.ranks = _native.distmult_fwd_bf16(tr, nodes, relations, sbias, pbias, obias, ranks=True)
+        else:
+            scores = _native.distmult_fwd_bf16(tr, nodes, relations, sbias, pbias, obias)
+        ctx.save_for_backward(tr, nodes, relations)
+        ctx.with_bias = sbias is not None
+        return scores.view(shape)
+
+    @staticmethod
+    def backward(ctx, gs):
+        tr, nodes, relations = ctx.saved_tensors
+        gs = dense(gs.reshape(-1).float())
+        if ctx.ranks is None:                          # atomic route (or no triples)
+            order = torch.argsort(tr[:, 1], stable=True)
+            dn, dr, dsb, dpb, dob = _native.distmult_bwd(tr[order].contiguous(), nodes.float(), relations, gs[order].contiguous(),
+                                                         ctx.with_bias, nodes_grad=True)
+            return None, dn.to(torch.bfloat16), dr, dsb, dpb, dob
+        if routes.get("distmult_bwd", "csr") != "split" and _native.distmult_bwd_all_supported(relations.shape[0], nodes.shape[1]):
+            dn, dr, dsb, dpb, dob = _native.distmult_bwd_all_bf16(tr, ctx.ranks, nodes, relations, gs, ctx.with_bias)
+            return None, dn, dr, dsb, dpb, dob
+        order = torch.argsort(tr[:, 1], stable=True)   # predicate runs -> relation gradient accumulates in registers
+        dr, dsb, dpb, dob = _native.distmult_bwd_rel_bf16(tr[order].contiguous(), nodes, relations, gs[order].contiguous(), ctx.with_bias)
+        dn = _native.distmult_bwd_nodes_bf16(tr, ctx.ranks, nodes, relations, gs)
+        return None, dn, dr, dsb, dpb, dob
+
+
 def distmult_score(triples, nodes, relations, sbias=None, pbias=None, obias=None):
+    """DistMult scores of `triples` [..., 3].  fp32 nodes: everything fp32.  bf16 nodes: relations and biases fp32 or bf16
+    -- bf16 parameters are widened here, once per call, and autograd carries the cast back --, scores fp32, dnodes bf16."""
+    if nodes.dtype == torch.bfloat16:
+        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+        widen = lambda t: None if t is None else t.float()     # noqa: E731  (a no-op on fp32)
+        return _DistMultScoreBF16.apply(triples, nodes, widen(relations), widen(sbias), widen(pbias), widen(obias))
     return _DistMultScore.apply(triples, nodes, relations, sbias, pbias, obias)
+
+
+def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, out=None):
+    """fp32 scores [Q, N] of every entity as the head (head=True) or the tail of each triple of `batch` (int64 [Q, 3] on the device), no
+    autograd: the ranking evaluator's product (utils/misc.py:71-88).  fp32 nodes run the fp32 matrix instructions; bf16 nodes (DESIGN.md
+    4.6) the bf16 ones on the bf16 table, with relations and biases fp32 or bf16 (widened here) -- same sums, another order."""
+    if nodes.dtype == torch.bfloat16:
+        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+        widen = lambda t: None if t is None else t.float()     # noqa: E731
+        return _native.distmult_score_all_bf16(batch, head, nodes, widen(relations), widen(sbias), widen(pbias), widen(obias), out=out)
+    return _native.distmult_score_all(batch, head, nodes, relations, sbias, pbias, obias, out=out)
 
 
 _UNIT = {}

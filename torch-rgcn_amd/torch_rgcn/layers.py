@@ -78,14 +78,16 @@ class DistMult(Module):
         s, p, o = split_spo(triples)
         s, p, o = s.reshape(-1), p.reshape(-1), o.reshape(-1)
         scale = 1.0 / (s.numel() * nodes.shape[-1])
-        node_sq = nodes.pow(2).sum(dim=-1)
-        rel_sq = self.relations.pow(2).sum(dim=-1)
+        # counts and square sums in fp32 whatever the storage type (a bf16 count stops at 256: 256 + 1 rounds back to 256); .float() is a
+        # no-op on fp32 tensors, and the result is returned in nodes.dtype
+        node_sq = nodes.float().pow(2).sum(dim=-1)
+        rel_sq = self.relations.float().pow(2).sum(dim=-1)
         def count(idx, n):       # occurrence histogram without torch.bincount (which reads the maximum back: a sync)
-            return torch.zeros(n, device=nodes.device, dtype=nodes.dtype).index_add_(
-                0, idx.to(nodes.device), torch.ones(idx.numel(), device=nodes.device, dtype=nodes.dtype))
+            return torch.zeros(n, device=nodes.device, dtype=torch.float32).index_add_(
+                0, idx.to(nodes.device), torch.ones(idx.numel(), device=nodes.device, dtype=torch.float32))
         n_nodes, n_rel = nodes.shape[0], self.relations.shape[0]
         return (((count(s, n_nodes) * node_sq).sum() + (count(o, n_nodes) * node_sq).sum()) * scale
-                + (count(p, n_rel) * rel_sq).sum() * (1.0 / (p.numel() * self.relations.shape[-1])))
+                + (count(p, n_rel) * rel_sq).sum() * (1.0 / (p.numel() * self.relations.shape[-1]))).to(nodes.dtype)
 
     def forward(self, triples, nodes):
         _require_gpu(nodes, "DistMult node embeddings")

@@ -3,7 +3,7 @@ same function names, arguments and return values.
 
 evaluate(): the reference expands every batch of test triples to a [bn, N, 3] candidate tensor and calls the whole
 model on it, which re-runs the encoder for each of the ~2 * len(test) / batch_size batches (misc.py:78-85).  Here the
-graph is encoded ONCE and the candidates are scored by the MFMA kernel behind `_native.distmult_score_all`
+graph is encoded ONCE and the candidates are scored by the MFMA kernels behind `functional.distmult_score_all`
 ("encode once, score many"); filtering and rank counting are HIP kernels too.  Ranks are defined
 exactly as in the reference: known true completions other than the target are set to -inf (misc.py:40-58), and the
 target sits halfway down its ties (misc.py:93-101).
@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from torch_rgcn import _native
+from torch_rgcn.functional import distmult_score_all
 from torch_rgcn.layers import DistMult
 
 _SCORE_BYTES = 1 << 30     # score-matrix budget per chunk of queries
@@ -127,10 +128,10 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
         for fr in range(0, len(test_set), batch_size):
             batch = test_set[fr:fr + batch_size].to(device).contiguous()
             bn = batch.shape[0]
-            if fast:
-                scores = _native.distmult_score_all(batch, head, x, decoder.relations.detach(),
-                                                    *((decoder.sbias.detach(), decoder.pbias.detach(), decoder.obias.detach())
-                                                      if decoder.b_init else ()))
+            if fast:        # (bf16 embeddings: the bf16 matrix instructions on the bf16 table, fp32 scores -- DESIGN.md 4.6)
+                scores = distmult_score_all(batch, head, x, decoder.relations.detach(),
+                                            *((decoder.sbias.detach(), decoder.pbias.detach(), decoder.obias.detach())
+                                              if decoder.b_init else ()))
             else:
                 ar = torch.arange(num_nodes, device=device).view(1, num_nodes, 1).expand(bn, num_nodes, 1)
                 bexp = (batch[:, 1:] if head else batch[:, :2]).view(bn, 1, 2).expand(bn, num_nodes, 2)
