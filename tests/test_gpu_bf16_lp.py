@@ -8,6 +8,8 @@ whose every partial sum is exact the scores EQUAL it.
 
 Bounds.  TOL = 1e-4: the fp32-arithmetic bound of tests/test_gpu_eval.py.  2^-8: one rounding to bf16 (8 significand bits, half an ulp
 is 2^-9 of the element, bounded by 2^-8 of the largest under the max-norm), the bound of tests/test_gpu_bf16.py."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -228,11 +230,12 @@ def test_distmult_bf16_exact_sums_that_need_the_rounding(monkeypatch, bwd, d):
     distmult_bf16_exact(monkeypatch, bwd, d, (), gmax=16)
 
 
-def distmult_bf16_exact(monkeypatch, bwd, d, frozen, gmax):
+def distmult_bf16_exact(monkeypatch, bwd, d, frozen, gmax, guard=None):
     """the construction of test_gpu_exact.py's distmult_exact on bf16 nodes: integer embeddings in [-2, 2], repeated triples, a 700-triple hub
     that is subject and object.  Every sum is an integer inside the fp32 significand: scores, drel and the bias gradients EQUAL the oracle,
     dnodes EQUALS the oracle's sum rounded once to bf16.  d = 50: element loads; d = 300: quarter-row loads, two passes of 256 features.  Both relation tables fit the LDS, so csr is
-    the one-walk kernel and split the predicate-sorted kernel plus the entity walk."""
+    the one-walk kernel and split the predicate-sorted kernel plus the entity walk.  guard: a guard_bands.Guard, not yet entered -- parameters,
+    embeddings, triples and the score gradient move into guarded allocations, forward and backward run under it, its findings are asserted"""
     from torch_rgcn import _native
     from torch_rgcn.layers import DistMult
     frozen = frozenset(frozen)
@@ -267,19 +270,26 @@ def distmult_bf16_exact(monkeypatch, bwd, d, frozen, gmax):
     dm.relations.requires_grad_("relations" not in frozen)
     for b in (dm.sbias, dm.pbias, dm.obias):
         b.requires_grad_("biases" not in frozen)
-    nd = dev(nodes, BF).requires_grad_("nodes" not in frozen)
     any_grad = frozen != {"nodes", "relations", "biases"}
     asked = []                                                  # ranks= of every call of the scoring kernel's wrapper
     inner = _native.distmult_fwd_bf16
     monkeypatch.setattr(_native, "distmult_fwd_bf16", lambda *a, ranks=False: (asked.append(ranks), inner(*a, ranks=ranks))[1])
-    _native.profile_start()
-    sc = dm(dev(tr), nd)
-    if any_grad:
-        sc.backward(dev(gs))
-    tags = set(_native.profile_stop())
+    home = (lambda t: t) if guard is None else guard.home
+    with contextlib.nullcontext() if guard is None else guard:
+        if guard is not None:
+            for p in dm.parameters():
+                p.data = home(p.data)
+        nd = home(dev(nodes, BF)).requires_grad_("nodes" not in frozen)
+        _native.profile_start()
+        sc = dm(home(dev(tr)), nd)
+        if any_grad:
+            sc.backward(home(dev(gs)))
+        tags = set(_native.profile_stop())
+        guard_problems = [] if guard is None else guard.problems()
     print(f"[exact] distmult bf16 {bwd} d={d} frozen {sorted(frozen)}: tags {sorted(tags)} | proof bits "
           + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
     assert asked == [any_grad and bwd != "atomic"], asked       # no CSR ranks counted when nothing needs a gradient
+    assert not guard_problems, "\n".join(guard_problems)
     split = {"distmult_bwd_rel_bf16", "distmult_bwd_nodes_bf16"}
     want = {"atomic": {"distmult_bwd"}, "split": split,
             "csr": {"distmult_bwd_all_bf16"} if _native.distmult_bwd_all_supported(R0, d) else split}[bwd] if any_grad else set()

@@ -18,6 +18,7 @@ relation-owner / block-tile kernels.
 
 EXCEPTED (case, tensor) pairs -- a gradient that sums over all relations in a hub case, compared under the 1e-4 max-norm because no hub size
 that still splits passes the proof bound: none."""
+import contextlib
 import functools
 
 import numpy as np
@@ -169,12 +170,15 @@ def make_layer(fx, params, bias, d_in, d_out, mode, featureless, vertical, num_b
 
 def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, relu=False, dtype=torch.float32, pdtype=torch.float32,
               num_bases=3, num_blocks=2, vmax=2, density=0.5, expect=(), forbid=(), split=None, seed=0, param_dtypes=None, lp=False,
-              frozen=(), counts=None):
+              frozen=(), counts=None, guard=None):
     """one layer, forward and backward, on the fixture `fix`; every result equal to the oracle.  lp: the link-prediction layer in eval mode
     (no dropout), the graph handed over per call.  frozen: names out of "X", the layer's parameter names and "bias" that get no gradient
     (requires_grad False before the forward) -- their .grad must stay None, and everything else is compared with the SAME reference: the
     gradient of a tensor does not depend on which other tensors are frozen.  counts: {profile tag: launches} that must match exactly (the
-    forward and the feature gradient share a tag: only the count tells them apart).  -> (profile tags, the layer)"""
+    forward and the feature gradient share a tag: only the count tells them apart).  guard: a guard_bands.Guard, not yet entered -- the
+    parameters, X, the upstream gradient and the LP triples move into guarded allocations, the first call (graph and plans), forward and
+    backward run under it, and what it finds (damaged bands, written buffers that no band protects) joins the problems of the case; every
+    other assertion is unchanged, so a guard that moved the case to another route fails it.  -> (profile tags, the layer)"""
     from torch_rgcn import _native
     frozen = frozenset(frozen)
     fx = lp_fixture(fix) if lp else fixture(fix)
@@ -189,16 +193,22 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
     assert frozen <= names and frozen != names, (sorted(frozen), sorted(names))
     for n in frozen - {"X"}:
         getattr(layer, n).requires_grad_(False)
-    Xd = None if featureless else _dev(X, dtype).requires_grad_("X" not in frozen)
-    _native.profile_start()
-    if lp:
-        out = layer(torch.from_numpy(fx["T"]).to(DEV), Xd)
-    elif relu:
-        out = layer.forward_activated(Xd, "relu", private=True)
-    else:
-        out = layer(Xd) if Xd is not None else layer()
-    out.backward(_dev(g, out.dtype))
-    launches = {k: len(v) for k, v in _native.profile_stop().items()}
+    home = (lambda t: t) if guard is None else guard.home
+    with contextlib.nullcontext() if guard is None else guard:
+        if guard is not None:
+            for p in layer.parameters():
+                p.data = home(p.data)
+        Xd = None if featureless else home(_dev(X, dtype)).requires_grad_("X" not in frozen)
+        _native.profile_start()
+        if lp:
+            out = layer(home(torch.from_numpy(fx["T"]).to(DEV)), Xd)
+        elif relu:
+            out = layer.forward_activated(Xd, "relu", private=True)
+        else:
+            out = layer(Xd) if Xd is not None else layer()
+        out.backward(home(_dev(g, out.dtype)))
+        launches = {k: len(v) for k, v in _native.profile_stop().items()}
+        guard_problems = [] if guard is None else guard.problems()
     tags = set(launches)
     ind = None if split is None else int(_split(layer._graph, split, d_in, d_out))
     case = f"{fx['name']} {d_in}x{d_out} {mode}{' featureless' if featureless else ''}{' vertical' if vertical else ''}{' relu' if relu else ''}" \
@@ -206,7 +216,7 @@ def run_exact(fix, d_in, d_out, mode="none", featureless=False, vertical=False, 
            f"{' frozen {' + ', '.join(sorted(frozen)) + '}' if frozen else ''}"
     print(f"[exact] {case}: tags {sorted(tags)} | split {ind} | proof bits " + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
 
-    problems = []
+    problems = list(guard_problems)
 
     def check(got, want, name, degree=None):
         try:
@@ -552,10 +562,11 @@ def test_distmult(monkeypatch, bwd, d, with_bias):
     distmult_exact(monkeypatch, bwd, d, with_bias)
 
 
-def distmult_exact(monkeypatch, bwd, d, with_bias, frozen=()):
+def distmult_exact(monkeypatch, bwd, d, with_bias, frozen=(), guard=None):
     """the body of test_distmult.  frozen: names out of "nodes", "relations", "biases" (the three bias vectors together) that get no
     gradient: theirs must stay None, the others equal the same oracle gradients.  All of them frozen: forward only -- the scores exact and
-    no CSR ranks counted by the scoring kernel"""
+    no CSR ranks counted by the scoring kernel.  guard: as in run_exact -- parameters, embeddings, triples and the score gradient in guarded
+    allocations, forward and backward under the guard, its findings asserted with the rest"""
     from torch_rgcn import _native
     frozen = frozenset(frozen)
     assert frozen <= {"nodes", "relations", "biases"} and (with_bias or "biases" not in frozen)
@@ -591,20 +602,27 @@ def distmult_exact(monkeypatch, bwd, d, with_bias, frozen=()):
     if with_bias:
         for b in (dm.sbias, dm.pbias, dm.obias):
             b.requires_grad_("biases" not in frozen)
-    nd = torch.from_numpy(nodes).to(DEV).requires_grad_("nodes" not in frozen)
     any_grad = frozen != ({"nodes", "relations", "biases"} if with_bias else {"nodes", "relations"})
     asked = []                                                  # ranks= of every call of the scoring kernel's wrapper
     inner = _native.distmult_fwd
     monkeypatch.setattr(_native, "distmult_fwd", lambda *a, ranks=False: (asked.append(ranks), inner(*a, ranks=ranks))[1])
-    _native.profile_start()
-    sc = dm(torch.from_numpy(tr).to(DEV), nd)
-    if any_grad:
-        sc.backward(torch.from_numpy(gs).to(DEV))
-    tags = set(_native.profile_stop())
+    home = (lambda t: t) if guard is None else guard.home
+    with contextlib.nullcontext() if guard is None else guard:
+        if guard is not None:
+            for p in dm.parameters():
+                p.data = home(p.data)
+        nd = home(torch.from_numpy(nodes).to(DEV)).requires_grad_("nodes" not in frozen)
+        _native.profile_start()
+        sc = dm(home(torch.from_numpy(tr).to(DEV)), nd)
+        if any_grad:
+            sc.backward(home(torch.from_numpy(gs).to(DEV)))
+        tags = set(_native.profile_stop())
+        guard_problems = [] if guard is None else guard.problems()
     print(f"[exact] distmult {bwd} d={d} bias={with_bias}{' frozen {' + ', '.join(sorted(frozen)) + '}' if frozen else ''}: tags {sorted(tags)} "
           f"| proof bits " + " ".join(f"{k} {v:.1f}" for k, v in bits.items()))
     # the scoring kernel counts the CSR ranks when anything needs a gradient and the backward will walk the CSRs
     assert asked == [any_grad and bwd != "atomic"], asked
+    assert not guard_problems, "\n".join(guard_problems)
     # csr: every gradient from the two CSR walks where the relation table fits (distmult_bwd_all_supported), else the split form; split:
     # predicate-sorted kernel + entity gradients from the CSRs; atomic: the scatter kernel alone.  (The backward computes every gradient
     # whatever is frozen: autograd drops what nobody asked for.)
