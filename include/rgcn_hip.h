@@ -807,6 +807,29 @@ RGCN_API int rgcn_rank_filter_f32(float *scores, int64_t Q, int64_t n_nodes, con
  * batch[q,2].  rank = greater + (ties - 1) / 2 + 1 is left to the caller (misc.py:99-101). */
 RGCN_API int rgcn_rank_count_f32(const float *scores, const int64_t *batch, int64_t Q, int32_t head,
                                  int64_t n_nodes, int64_t *greater, int64_t *ties, void *stream);
+/* Fused ranking evaluator (utils/misc.py:40-58, 71-99): greater [Q] and ties [Q] (int64, what rgcn_rank_count_f32 returns after
+ * rgcn_distmult_score_all_* and rgcn_rank_filter_f32) straight from the entity table -- no [Q, n_nodes] score buffer exists.  Three
+ * passes on `stream`, no host synchronisation, no memset: the query pass of the score-all entries; tscore [Q] (float, always written) =
+ * the score of every query's own target, bit for bit the cell the score-all kernel computes (the same product and bias epilogue, one
+ * 128 x 128 tile per 128 queries on the rows nodes[target_q]); the count pass = that product again, tile by tile, with an epilogue that
+ * compares with tscore instead of storing.  A workgroup owns 128 queries and one of `strips` runs of consecutive candidate tiles
+ * (strips = 0: the library's choice, two workgroups per compute unit; a strip may own no tile), keeps its counters in registers and
+ * writes one (greater, ties) pair per strip and query; a last kernel sums the strips.  filt_q / filt_n [F] (int32, device; F = 0 with
+ * NULL lists = raw ranks) set bits in a mask [Q][ceil(n_nodes / 32)] inside the workspace with integer atomic OR (duplicates are
+ * harmless) and a masked cell compares as -inf.  An entry on a query's own target -- a caller error in both routes -- is IGNORED here.
+ * Entries are NOT range-checked on the device (the Python wrapper checks 0 <= filt_q < Q, 0 <= filt_n < n_nodes).
+ * workspace: rgcn_distmult_rank_fused_workspace_bytes(Q, n_nodes, d, strips, bf16) bytes (the same `strips` as the call; no device is
+ * asked: strips = 0 sizes for the largest default), 16-byte aligned.  Errors as the score-all entries: RGCN_EINVAL for bad, NULL or
+ * misaligned arguments, strips < 0 and biases partly set; RGCN_EUNSUPPORTED beyond INT32_MAX workgroups; Q == 0 launches nothing. */
+RGCN_API int64_t rgcn_distmult_rank_fused_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
+RGCN_API int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                          const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                          int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                           const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                           int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

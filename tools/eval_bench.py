@@ -4,10 +4,15 @@ tail queries), filtered against ~150k known triples.  Prints one JSON line: whol
 kernel's MFMA roofline, and the CPU oracle (reference algorithm, numpy) on a bounded sample.
     python tools/eval_bench.py [--test 5000] [--cpu-sample 48] [--no-cpu] [--bf16]
 --bf16: the entity table is rounded to bf16 and, in the same process, the fp32 evaluator on the widened table is measured against the bf16
-evaluator on the bf16 table (launches alternate): "bf16" in the result."""
+evaluator on the bf16 table (launches alternate): "bf16" in the result.
+    python tools/eval_bench.py --fused [--test 5000] [--steps 20 --warmup 5 --out DIR]   -> DIR/rank_fused_bench_<csrc_sha>.json (DIR: profiles/)
+--fused: nothing of the above; in one process, for fp32 and bf16 tables, the materialised route (score-all, filter, count) against the fused
+route, taking turns: whole evaluate() calls by the host clock (they end in a synchronising download of the counts), and
+single launches of the full head batch by HIP events.  The counts of the two routes are compared before anything is timed."""
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -42,7 +47,18 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=48)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
+    if a.fused:
+        res = fused_against_materialised(a.test, a.steps, a.warmup)
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, f"rank_fused_bench_{_native.csrc_sha()}.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res), flush=True)
+        return
     print(json.dumps(run(a.test, 0 if a.no_cpu else a.cpu_sample, a.bf16)), flush=True)
 
 
@@ -66,6 +82,88 @@ def bf16_against_fp32(batch, x, rel, out, launches=10):
     return {"fp32_on_widened_ms": round(ks["score_all"], 4), "bf16_ms": round(ks["distmult_score_all_bf16"], 4),
             "bf16_speedup": round(ks["score_all"] / ks["distmult_score_all_bf16"], 3),
             "max_abs_difference_over_max_score": float((a - b).abs().max() / a.abs().max())}
+
+
+def _quartiles(t, unit="ms"):
+    q = statistics.quantiles(t, n=4)
+    return {f"{unit}_median": round(statistics.median(t), 4), f"{unit}_min": round(min(t), 4), f"{unit}_q1": round(q[0], 4),
+            f"{unit}_q3": round(q[2], 4)}
+
+
+def fused_against_materialised(Q=5000, steps=20, warmup=5, evaluations=5):
+    """-> the dict of profiles/rank_fused_bench_<csrc_sha>.json"""
+    N, R0, d = 40_943, 18, 200
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    x32 = torch.randn(N, d, device=dev)
+    dm = DistMult(R0, d, N, R0).to(dev)
+    rel = dm.relations.detach()
+    test = _native.synthetic_triples_host(N, R0, Q, 5)
+    known = _native.synthetic_triples_host(N, R0, 146_442, 6)
+    true_triples = misc.generate_true_dict(np.concatenate([known, test]))
+    batch = torch.from_numpy(test).to(dev)
+    rows, cols = misc._filter_index(true_triples, N).lists(test, True)
+    fq, fn = torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)
+    scores = torch.empty(Q, N, device=dev)
+    res = {"tool": "tools/eval_bench.py --fused", "csrc_sha": _native.csrc_sha(), "steps": steps, "warmup": warmup,
+           "evaluations": evaluations, "device": torch.cuda.get_device_name(0),
+           "shape": {"N": N, "d": d, "Q": Q, "filter_entries_head": int(len(rows))},
+           "score_matrix_bytes": 4 * Q * N}
+    for storage, x in (("fp32", x32), ("bf16", x32.to(torch.bfloat16))):
+        score_all = _native.distmult_score_all_bf16 if storage == "bf16" else _native.distmult_score_all
+        model = Model(dm, x)
+
+        def materialised():
+            score_all(batch, True, x, rel, out=scores)
+            _native.rank_filter(scores, fq, fn)
+            return _native.rank_count(scores, batch, True)
+
+        def fused():
+            return _native.distmult_rank_fused(batch, True, x, rel, filt_q=fq, filt_n=fn)[:2]
+
+        a, b = materialised(), fused()
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), "the routes count differently"
+        variants = {"materialised": materialised, "fused": fused}
+        for run_ in variants.values():
+            for _ in range(warmup):
+                run_()
+        torch.cuda.synchronize()
+        times = {k: [] for k in variants}
+        for _ in range(steps):
+            for k, run_ in variants.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run_()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1))
+        launch = {k: _quartiles(t) for k, t in times.items()}
+        launch["fused_speedup"] = round(launch["materialised"]["ms_median"] / launch["fused"]["ms_median"], 3)
+        flops = 2.0 * Q * N * d
+        launch["fused_useful_tflops"] = round(flops / (launch["fused"]["ms_median"] * 1e-3) / 1e12, 2)
+        # whole evaluate() calls: both directions, host filter lists, uploads, the download of the counts
+        ranks, walls = {}, {False: [], True: []}
+        for f in (False, True):
+            ranks[f] = misc.evaluate(model, None, test, true_triples, N, verbose=False, fused=f)[2]        # warm-up
+        assert ranks[False] == ranks[True], "the routes rank differently"
+        for _ in range(evaluations):
+            for f in (False, True):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                misc.evaluate(model, None, test, true_triples, N, verbose=False, fused=f)
+                torch.cuda.synchronize()
+                walls[f].append(time.perf_counter() - t0)
+        ev = {"materialised": _quartiles(walls[False], "s"), "fused": _quartiles(walls[True], "s")}
+        ev["fused_speedup"] = round(ev["materialised"]["s_median"] / ev["fused"]["s_median"], 3)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fused()
+        peak = torch.cuda.max_memory_allocated() - base
+        res[storage] = {"per_launch_head_batch": launch, "evaluate_both_directions": ev,
+                        "fused_workspace_bytes": _native.rank_fused_workspace_bytes(Q, N, d, 0, storage == "bf16"),
+                        "fused_peak_memory_rise_bytes": int(peak)}
+    return res
 
 
 def run(test=5000, cpu_sample=48, bf16=False):

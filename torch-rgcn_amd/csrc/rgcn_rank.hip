@@ -12,6 +12,8 @@
 // feeding four MFMAs of each tile that shares it) is kept selectable for comparison (RGCN_RANK_TILE=44).
 // The K index is permuted -- lane group kq carries k = 16t + 4kq + c at MFMA c of step t -- which is legal
 // because both operands use the same permutation and the sum over k does not care.
+// Second route (rgcn_distmult_rank_fused_*, utils/misc.py:40-58, 71-99): the same tile product with an epilogue that compares every score
+// with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.
 #include <cmath>
 #include <cstdlib>
 
@@ -59,26 +61,18 @@ __device__ __forceinline__ f32x4 mask_k4(f32x4 v, int k, int d) {
 // LDS tile (row stride 20 floats: the ds_read_b128 of 16 rows x 4 column groups is conflict-free) and read back as MFMA
 // operands.  The loads of step t+1 are issued before the 64 MFMAs of step t and land in LDS after them.
 constexpr int LDS_LD = 20;
+
+// The product loop of one 128 x 128 tile, shared by score_all_lds_kernel and the fused evaluator's target and count kernels
+// (rank_target_kernel, rank_count_fused_kernel): whoever instantiates it gets the same K permutation and the same MFMA chain per
+// accumulator, hence the same bits for the same pair of rows wherever the pair sits in a tile.  ga / gb: this thread's two staging rows
+// (tid >> 2 and + 64) of the query and the candidate slab.  Ends on a barrier: the LDS slabs may be refilled right away.
 template <bool VEC>
-__global__ __launch_bounds__(WG) void score_all_lds_kernel(
-    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes,
-    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int head, int q_blocks) {
-  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
+__device__ __forceinline__ void tile_product_f32(const float *const (&ga)[2], const float *const (&gb)[2], int d,
+                                                 float (&sA)[2][128 * LDS_LD], float (&sB)[2][128 * LDS_LD], f32x4 (&acc)[4][4]) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, kq = lane >> 4;
-  const int qt = (blockIdx.x % q_blocks) * 128;
-  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
-  const int q0 = qt + (wave >> 1) * 64;
-  const long long c0 = ct + (wave & 1) * 64;
   // staging: thread -> rows (tid >> 2) and (tid >> 2) + 64 of both slabs, 16-byte column group tid & 3
   const int sr = tid >> 2, sc = 4 * (tid & 3);
-  const float *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
-    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-  }
-  f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -125,6 +119,15 @@ __global__ __launch_bounds__(WG) void score_all_lds_kernel(
     if (t + 1 < steps) stash(cur ^ 1, t + 1);
     __syncthreads();
   }
+}
+
+// The epilogue of a wave's 64 x 64 block, shared like the product (fp32 and bf16 tiles hold their accumulators alike): the parenthesised
+// bias sum on every cell with qrow < Q and col < n_cols.  row(a * 4 + r, qrow) opens a query row and returns its state; cb_of(col) is the
+// candidate-side bias of a column; cell(state, a * 4 + r, b, col, score) takes the finished score.
+template <class Row, class CB, class Cell>
+__device__ __forceinline__ void tile_epilogue(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long n_cols,
+                                              const float *__restrict__ qb, int head, Row row, CB cb_of, Cell cell) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -133,18 +136,155 @@ __global__ __launch_bounds__(WG) void score_all_lds_kernel(
       if (qrow >= Q) continue;
       float s1 = 0.f, s2 = 0.f;
       if (qb) { s1 = qb[2 * qrow]; s2 = qb[2 * qrow + 1]; }
+      auto st = row(a * 4 + r, qrow);
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const long long col = c0 + 16 * b + i;
-        if (col >= N) continue;
+        if (col >= n_cols) continue;
         float sc_ = acc[a][b][r];
         if (qb) {
-          const float cb = cbias[col];
+          const float cb = cb_of(col);
           sc_ += head ? ((cb + s1) + s2) : ((s2 + s1) + cb);
         }
-        scores[(size_t)qrow * N + col] = sc_;
+        cell(st, a * 4 + r, b, col, sc_);
       }
     }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void score_all_lds_kernel(
+    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes,
+    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128;
+  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
+  const int sr = tid >> 2;
+  const float *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
+    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+  }
+  f32x4 acc[4][4];
+  tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, ct + (wave & 1) * 64, Q, N, qb, head,
+                [&](int, int qrow) { return scores + (size_t)qrow * N; },
+                [&](long long col) { return cbias[col]; },
+                [&](float *out, int, int, long long col, float sc_) { out[col] = sc_; });
+}
+
+// ------------------------------------------------------------------ fused evaluator: ranks without the score matrix
+// Pass 2: tscore[q] = the score of query q's own target, from the SAME product and epilogue as score_all -- one 128 x 128 tile per
+// block of 128 queries whose "candidate" row j is nodes[target of query qt + j]; the diagonal cells are kept.
+__device__ __forceinline__ long long rank_target(const long long *__restrict__ batch, int q, int head) { return batch[3 * q + (head ? 0 : 2)]; }
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void rank_target_kernel(
+    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
+    const long long *__restrict__ batch, float *__restrict__ tscore, int Q, int d, int head) {
+  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = blockIdx.x * 128;
+  const int sr = tid >> 2;
+  const float *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int q = min(qt + sr + 64 * h, Q - 1);
+    ga[h] = qvec + (size_t)q * d;
+    gb[h] = nodes + (size_t)rank_target(batch, q, head) * d;
+  }
+  f32x4 acc[4][4];
+  tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, (long long)qt + (wave & 1) * 64, Q, (long long)Q, qb, head,
+                [&](int, int qrow) { return qrow; },
+                [&](long long col) { return cbias[rank_target(batch, (int)col, head)]; },
+                [&](int qrow, int, int, long long col, float sc_) { if (col == qrow) tscore[qrow] = sc_; });
+}
+
+// Pass 3's epilogue: the cells of one tile compared with their query's target score instead of stored.  mask: the filter bits
+// [Q][mask_w] (NULL = raw ranks), one word per 32 candidates -- the lane's four columns c0 + 16 b + i (c0 a multiple of 64) sit in words
+// c0 / 32 and c0 / 32 + 1.  A filtered cell compares as -inf, which is what rank_filter_kernel writes into the score matrix of the
+// materialised route.  Counters: a lane's 16 rows would cost 32 registers across the product loop; instead every row's (greater, equal)
+// of this tile -- at most 64 each, packed in one word -- is summed over the 16 lanes that share the row (four DPP steps) and kept by
+// lane i = row: g / e hold the counts of row 16 (i >> 2) + 4 kq + (i & 3) of the wave's 64.
+struct RankRow { float t; unsigned w[2]; };
+
+__device__ __forceinline__ void tile_count(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long N, const float *__restrict__ qb,
+                                           const float *__restrict__ cbias, int head, const float *__restrict__ tscore,
+                                           const unsigned *__restrict__ mask, long long mask_w, int &g, int &e) {
+  const int i = threadIdx.x & 15;
+  int c[16];
+#pragma unroll
+  for (int row = 0; row < 16; ++row) c[row] = 0;
+  tile_epilogue(acc, q0, c0, Q, N, qb, head,
+                [&](int, int qrow) {
+                  RankRow st{tscore[qrow], {0u, 0u}};
+                  if (mask) {
+                    const long long w0 = c0 >> 5;
+                    const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                    if (w0 < mask_w) st.w[0] = mrow[w0];                  // (the right half of a ragged last tile may start past N)
+                    if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  }
+                  return st;
+                },
+                [&](long long col) { return cbias[col]; },
+                [&](const RankRow &st, int row, int b, long long, float sc_) {
+                  const float s = (st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u ? -INFINITY : sc_;
+                  c[row] += (s > st.t) + ((s == st.t) << 16);
+                });
+#pragma unroll
+  for (int row = 0; row < 16; ++row) {
+    int v = c[row];
+    v += dpp_i<0xB1>(v, v);        // quad_perm [1,0,3,2]
+    v += dpp_i<0x4E>(v, v);        // quad_perm [2,3,0,1]
+    v += dpp_i<0x141>(v, v);       // row_half_mirror
+    v += dpp_i<0x140>(v, v);       // row_mirror: every lane of the 16 holds the row's sum
+    g += i == row ? v & 0xFFFF : 0;
+    e += i == row ? v >> 16 : 0;
+  }
+}
+
+// strip s of `strips` owns the candidate tiles [s n_tiles / strips, (s + 1) n_tiles / strips): sizes differ by one at most, and a strip
+// beyond the tiles owns none
+__device__ __forceinline__ long long strip_first(long long s, long long n_tiles, int strips) { return s * n_tiles / strips; }
+
+// a wave's counters -> partial[2 strip + candidate half of the wave][q] = (greater, equal)
+__device__ __forceinline__ void strip_store(int g, int e, int q0, int Q, uint2 *__restrict__ part) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
+  const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
+  if (qrow < Q) part[qrow] = uint2{(unsigned)g, (unsigned)e};
+}
+
+// Pass 3: a workgroup owns one block of 128 queries and a strip of candidate tiles; counters stay in registers over the strip.
+template <bool VEC>
+__global__ __launch_bounds__(WG) void rank_count_fused_kernel(
+    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
+    const float *__restrict__ tscore, const unsigned *__restrict__ mask, long long mask_w, uint2 *__restrict__ partial,
+    int Q, long long N, int d, int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
+  const long long n_tiles = (N + 127) / 128;
+  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
+  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
+  const float *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
+  int g = 0, e = 0;
+  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
+    const long long ct = tile * 128;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+    f32x4 acc[4][4];
+    tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
+    // the rows' target scores, bias terms and addresses are formed again for every tile: hoisted out of this loop they would sit in
+    // ~100 registers through the product, and the kernel would drop to one workgroup per compute unit
+    int q0t = q0;
+    asm volatile("" : "+v"(q0t));
+    tile_count(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, tscore, mask, mask_w, g, e);
+  }
+  strip_store(g, e, q0, Q, partial + (size_t)(2 * strip + (wave & 1)) * Q);
 }
 
 // ------------------------------------------------------------------ bf16 entity table
@@ -220,27 +360,16 @@ __device__ __forceinline__ u32x4 mask_k8(u32x4 v, int k, int d) {
 constexpr int SLAB = 128 * 32;          // bf16 elements of one 128-row slab
 __device__ __forceinline__ int slab_at(int row, int piece) { return row * 32 + 8 * (piece ^ ((row >> 2) & 2)); }
 
+// The bf16 product loop of one tile, shared by score_all_bf16_kernel, rank_target_bf16_kernel and rank_count_fused_bf16_kernel (as
+// tile_product_f32: same lo-mid-hi order and MFMA chain per accumulator for whoever instantiates it).  ga: this thread's two staging rows
+// of the hi term (mid and lo `term` elements further on), gb: of the candidate slab.  Ends on a barrier.
 template <bool VEC>
-__global__ __launch_bounds__(WG) void score_all_bf16_kernel(
-    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes,
-    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int dpad, int head, int q_blocks) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
+__device__ __forceinline__ void tile_product_bf16(const uint16_t *const (&ga)[2], const uint16_t *const (&gb)[2], size_t term, int d, int dpad,
+                                                  uint16_t (&sA)[2][3][SLAB], uint16_t (&sB)[2][SLAB], f32x4 (&acc)[4][4]) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, kq = lane >> 4;
-  const int qt = (blockIdx.x % q_blocks) * 128;
-  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
-  const int q0 = qt + (wave >> 1) * 64;
-  const long long c0 = ct + (wave & 1) * 64;
   // staging: thread -> rows (tid >> 2) and (tid >> 2) + 64 of the four slabs, 16-byte piece tid & 3
   const int sr = tid >> 2, sc = tid & 3;
-  const size_t term = (size_t)Q * dpad;
-  const uint16_t *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
-    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-  }
-  f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -292,26 +421,108 @@ __global__ __launch_bounds__(WG) void score_all_bf16_kernel(
     if (t + 1 < steps) stash(cur ^ 1, t + 1);
     __syncthreads();
   }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void score_all_bf16_kernel(
+    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes,
+    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int dpad, int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128;
+  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
+  const int sr = tid >> 2;
+  const uint16_t *ga[2], *gb[2];
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+  for (int h = 0; h < 2; ++h) {
+    ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
+    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+  }
+  f32x4 acc[4][4];
+  tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, ct + (wave & 1) * 64, Q, N, qb, head,
+                [&](int, int qrow) { return scores + (size_t)qrow * N; },
+                [&](long long col) { return cbias[col]; },
+                [&](float *out, int, int, long long col, float sc_) { out[col] = sc_; });
+}
+
+// the fused evaluator's passes 2 and 3 on the bf16 table (see rank_target_kernel, rank_count_fused_kernel)
+template <bool VEC>
+__global__ __launch_bounds__(WG) void rank_target_bf16_kernel(
+    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
+    const long long *__restrict__ batch, float *__restrict__ tscore, int Q, int d, int dpad, int head) {
+  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = blockIdx.x * 128;
+  const int sr = tid >> 2;
+  const uint16_t *ga[2], *gb[2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow = q0 + 16 * a + 4 * kq + r;
-      if (qrow >= Q) continue;
-      float s1 = 0.f, s2 = 0.f;
-      if (qb) { s1 = qb[2 * qrow]; s2 = qb[2 * qrow + 1]; }
+  for (int h = 0; h < 2; ++h) {
+    const int q = min(qt + sr + 64 * h, Q - 1);
+    ga[h] = qs + (size_t)q * dpad;
+    gb[h] = nodes + (size_t)rank_target(batch, q, head) * d;
+  }
+  f32x4 acc[4][4];
+  tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, (long long)qt + (wave & 1) * 64, Q, (long long)Q, qb, head,
+                [&](int, int qrow) { return qrow; },
+                [&](long long col) { return cbias[rank_target(batch, (int)col, head)]; },
+                [&](int qrow, int, int, long long col, float sc_) { if (col == qrow) tscore[qrow] = sc_; });
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void rank_count_fused_bf16_kernel(
+    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
+    const float *__restrict__ tscore, const unsigned *__restrict__ mask, long long mask_w, uint2 *__restrict__ partial,
+    int Q, long long N, int d, int dpad, int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
+  const long long n_tiles = (N + 127) / 128;
+  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
+  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
+  const uint16_t *ga[2], *gb[2];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const long long col = c0 + 16 * b + i;
-        if (col >= N) continue;
-        float sc_ = acc[a][b][r];
-        if (qb) {
-          const float cb = cbias[col];
-          sc_ += head ? ((cb + s1) + s2) : ((s2 + s1) + cb);
-        }
-        scores[(size_t)qrow * N + col] = sc_;
-      }
-    }
+  for (int h = 0; h < 2; ++h) ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
+  int g = 0, e = 0;
+  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
+    const long long ct = tile * 128;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+    f32x4 acc[4][4];
+    tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
+    // the rows' target scores, bias terms and addresses are formed again for every tile: hoisted out of this loop they would sit in
+    // ~100 registers through the product, and the kernel would drop to one workgroup per compute unit
+    int q0t = q0;
+    asm volatile("" : "+v"(q0t));
+    tile_count(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, tscore, mask, mask_w, g, e);
+  }
+  strip_store(g, e, q0, Q, partial + (size_t)(2 * strip + (wave & 1)) * Q);
+}
+
+// filter bits: mask[fq][fn / 32] |= 1 << (fn % 32).  Integer OR: duplicates are harmless.  An entry on a query's own target is dropped
+// (a caller error in both routes; the materialised route would rank that query against -inf)
+__global__ void rank_mask_kernel(unsigned *__restrict__ mask, long long mask_w, const int *__restrict__ fq, const int *__restrict__ fn,
+                                 long long F, const long long *__restrict__ batch, int head) {
+  for (long long e = (long long)blockIdx.x * WG + threadIdx.x; e < F; e += (long long)gridDim.x * WG) {
+    const int q = fq[e], n = fn[e];
+    if (n != rank_target(batch, q, head)) atomicOr(mask + (size_t)q * mask_w + (n >> 5), 1u << (n & 31));
+  }
+}
+
+// the strips' partials [n_part][Q] summed into the int64 outputs (integers: any order is exact)
+__global__ __launch_bounds__(WG) void rank_reduce_kernel(const uint2 *__restrict__ partial, int n_part, int Q,
+                                                         long long *__restrict__ greater, long long *__restrict__ ties) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= Q) return;
+  long long gs = 0, es = 0;
+  for (int p = 0; p < n_part; ++p) {
+    const uint2 v = partial[(size_t)p * Q + q];
+    gs += v.x;
+    es += v.y;
+  }
+  greater[q] = gs;
+  ties[q] = es;
 }
 
 __global__ void rank_filter_kernel(float *__restrict__ scores, long long N, const int *__restrict__ fq,
@@ -451,4 +662,125 @@ extern "C" int rgcn_rank_count_f32(const float *scores, const int64_t *batch, in
                      reinterpret_cast<long long *>(greater), reinterpret_cast<long long *>(ties));
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
+}
+
+// ------------------------------------------------------------------ fused evaluator: entry points
+namespace {
+
+constexpr int64_t FUSED_CU_CAP = 512;          // the workspace of strips = 0 is sized for up to this many compute units
+inline int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+// the library's choice of strips: two workgroups per compute unit (what the LDS slabs and the registers of the count kernels allow)
+inline int64_t fused_default_strips(int64_t Q, int64_t n_nodes, int64_t n_cu) {
+  const int64_t qbl = (Q + 127) / 128, n_tiles = (n_nodes + 127) / 128;
+  return std::max<int64_t>(1, std::min(n_tiles, (2 * std::min(n_cu, FUSED_CU_CAP) + qbl - 1) / qbl));
+}
+
+struct FusedLayout { int64_t qv, qb, part, mask, total, mask_w; };
+
+// strips = 0: room for the default of any device up to FUSED_CU_CAP units, by a bound that grows with Q and with N:
+// strips * Q <= min(n_tiles * Q, 2 * CAP * 128 + Q)
+inline FusedLayout fused_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t strips, bool bf16) {
+  FusedLayout L;
+  L.mask_w = (n_nodes + 31) / 32;
+  const int64_t n_tiles = (n_nodes + 127) / 128;
+  const int64_t cells = strips > 0 ? strips * Q : std::min(n_tiles * Q, 2 * FUSED_CU_CAP * 128 + Q);
+  L.qv = 0;
+  L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
+  L.part = L.qb + align16(2 * Q * (int64_t)sizeof(float));
+  L.mask = L.part + align16(2 * cells * (int64_t)sizeof(uint2));
+  L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
+  return L;
+}
+
+template <bool BF16, class T>
+int rank_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, const T *nodes, const float *rel, const float *sbias,
+               const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F, int32_t strips,
+               void *workspace, int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t d, void *stream) {
+  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || F < 0 || strips < 0 || (F && (!filt_q || !filt_n)) ||
+      (Q && (!batch || !nodes || !rel || !workspace || !greater || !ties || !tscore)) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+    rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; strips >= 0; F > 0 needs both filter lists)", name);
+    return RGCN_EINVAL;
+  }
+  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) {
+    rgcn_set_error("%s: biases must be all set or all NULL", name);
+    return RGCN_EINVAL;
+  }
+  if (Q == 0) return RGCN_OK;
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const int64_t qbl = (Q + 127) / 128, n_tiles = (n_nodes + 127) / 128;
+  const int64_t n_strips = strips > 0 ? strips : fused_default_strips(Q, n_nodes, n_cu);
+  // a strip's counters are 32-bit: (tiles of the longest strip) * 128 cells per query
+  if (n_strips * qbl > INT32_MAX || n_tiles > INT32_MAX || ((n_tiles + n_strips - 1) / n_strips + 1) * 128 > INT32_MAX) {
+    rgcn_set_error("%s: too many scores in one call; split the batch", name);
+    return RGCN_EUNSUPPORTED;
+  }
+  const FusedLayout L = fused_layout(Q, n_nodes, d, strips, BF16);
+  char *ws = static_cast<char *>(workspace);
+  float *qb = reinterpret_cast<float *>(ws + L.qb);
+  uint2 *part = reinterpret_cast<uint2 *>(ws + L.part);
+  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const long long *b = reinterpret_cast<const long long *>(batch);
+  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
+  if (F) {
+    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
+    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
+                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head);
+  }
+  const dim3 gq((unsigned)((Q + 3) / 4)), gt((unsigned)qbl), gc((unsigned)(n_strips * qbl));
+  if constexpr (BF16) {
+    uint16_t *qs = reinterpret_cast<uint16_t *>(ws + L.qv);
+    const int dpad = (int)k_pad32(d);
+    hipLaunchKernelGGL(rank_query_bf16_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qs, qb, d, dpad);
+    // 16-byte loads of the entity rows as in rgcn_distmult_score_all_bf16: the same instantiation, the same bits
+    auto run = [&](auto vec) {
+      constexpr bool V = decltype(vec)::value;
+      hipLaunchKernelGGL(rank_target_bf16_kernel<V>, gt, dim3(WG), 0, st, qs, qb1, nodes, cb1, b, tscore, (int)Q, d, dpad, head);
+      hipLaunchKernelGGL(rank_count_fused_bf16_kernel<V>, gc, dim3(WG), 0, st, qs, qb1, nodes, cb1, tscore, mask, (long long)L.mask_w,
+                         part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips);
+    };
+    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(nodes) & 15) == 0) run(std::true_type{});
+    else run(std::false_type{});
+  } else {
+    float *qvec = reinterpret_cast<float *>(ws + L.qv);
+    hipLaunchKernelGGL(rank_query_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qvec, qb, d);
+    auto run = [&](auto vec) {
+      constexpr bool V = decltype(vec)::value;
+      hipLaunchKernelGGL(rank_target_kernel<V>, gt, dim3(WG), 0, st, qvec, qb1, nodes, cb1, b, tscore, (int)Q, d, head);
+      hipLaunchKernelGGL(rank_count_fused_kernel<V>, gc, dim3(WG), 0, st, qvec, qb1, nodes, cb1, tscore, mask, (long long)L.mask_w,
+                         part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips);
+    };
+    if (d % 4 == 0) run(std::true_type{});
+    else run(std::false_type{});
+  }
+  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((Q + WG - 1) / WG)), dim3(WG), 0, st, part, (int)(2 * n_strips), (int)Q,
+                     reinterpret_cast<long long *>(greater), reinterpret_cast<long long *>(ties));
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rgcn_distmult_rank_fused_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : fused_layout(Q, n_nodes, d, strips, bf16 != 0).total;
+}
+
+extern "C" int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                            int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return rank_fused<false>("distmult_rank_fused", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                           greater, ties, tscore, n_nodes, d, stream);
+}
+
+extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                             const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                             int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return rank_fused<true>("distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                          greater, ties, tscore, n_nodes, d, stream);
 }

@@ -28,12 +28,13 @@ from utils.misc import evaluate, generate_true_dict, negative_sampling, select_s
 OPTIMISERS = {"adam": torch.optim.Adam, "adamw": torch.optim.AdamW, "adagrad": torch.optim.Adagrad, "sgd": torch.optim.SGD}
 
 
-def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=None, hipgraph=None):
+def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=None, hipgraph=None, fused_eval=None):
     """-> (loss per epoch, {"mrr", "hits@1", "hits@3", "hits@10"} of the final evaluation).
     The training step (per-step graph build, encoder, decoder, loss, backward, optimiser) is captured once in a hipGraph and replayed
     every epoch on freshly sampled inputs copied into static buffers -- BY DEFAULT (hipgraph=None: unless route `capture` is "0";
     falls back to the eager loop, with a warning, if the capture fails; True insists, False is the reference's loop literally).
-    The capture runs under the sync-free plan builder (route deferred_checks = 1, scoped to the warm-up and the capture)."""
+    The capture runs under the sync-free plan builder (route deferred_checks = 1, scoped to the warm-up and the capture).
+    fused_eval: utils.misc.evaluate's `fused` (True: rank without the score matrix; None: only where that matrix would need chunks)."""
     dataset, training, encoder = cfg["dataset"], cfg["training"], cfg["encoder"]
     decoder, evaluation = cfg.get("decoder", {}), cfg.get("evaluation", {})
     max_epochs = epochs or training.get("epochs", 5000)
@@ -46,7 +47,7 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     filtered = evaluation.get("filtered", False)
     eval_every = evaluation.get("check_every", 2000)
     eval_kw = dict(batch_size=evaluation.get("batch_size", 16), verbose=evaluation.get("verbose", False) and not quiet,
-                   filter_candidates=filtered)
+                   filter_candidates=filtered, fused=fused_eval)
 
     (n2i, nodes), (r2i, relations), train, test, all_triples = load_link_prediction_data(
         dataset["name"], use_test_set=evaluation.get("final_run", False), directory=data_dir, synthetic=synthetic)
@@ -220,6 +221,8 @@ if __name__ == "__main__":
     ap.add_argument("--max-test", type=int, default=None)
     ap.add_argument("--hipgraph", action="store_true", help="insist on the captured training step (the default tries it and falls back to eager)")
     ap.add_argument("--eager", action="store_true", help="the reference's loop literally: no hipGraph capture")
+    ap.add_argument("--fused-eval", action="store_true", help="rank with the fused evaluator (no score matrix) whatever the size; "
+                    "the default takes it only where the score matrix of the test set exceeds the 1 GiB chunk budget")
     a = ap.parse_args()
     run(yaml.safe_load(open(a.config)), a.data, a.epochs, max_test=a.max_test, synthetic=True if a.synthetic else None,
-        hipgraph=False if a.eager else (True if a.hipgraph else None))
+        hipgraph=False if a.eager else (True if a.hipgraph else None), fused_eval=True if a.fused_eval else None)

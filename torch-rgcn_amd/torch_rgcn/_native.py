@@ -2255,3 +2255,56 @@ def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obi
                                                   _dp(pbias), _dp(obias), _dp(qsplit), _dp(qb), _dp(scores), N,
                                                   rel.shape[0], d, _stream(nodes.device)), "distmult_score_all_bf16")
     return scores
+
+
+def rank_fused_workspace_bytes(Q, N, d, strips=0, bf16=False):
+    """bytes of the fused evaluator's workspace (query vectors, strip partials, the [Q][ceil(N / 32)] filter mask); needs no device"""
+    return int(lib().rgcn_distmult_rank_fused_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
+
+
+def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0):
+    """(greater, ties, tscore) of every query of `batch` (int64 [Q, 3], device) without the [Q, N] score matrix: what rank_count returns
+    after distmult_score_all[_bf16] and rank_filter on (filt_q, filt_n) (int32 device lists, None = raw ranks), plus the target's own
+    score -- utils/misc.py:40-58, 71-99.  fp32 or bf16 nodes (rel and biases fp32).  strips: candidate strips per block of 128 queries
+    (0 = the library's choice).  A filter entry on a query's own target is ignored."""
+    bf16 = nodes.dtype == torch.bfloat16
+    if bf16:
+        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
+    else:
+        _req(nodes, "nodes"); _req(rel, "relations")
+        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
+            _req(b, n)
+    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
+    Q, (N, d) = batch.shape[0], nodes.shape
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    assert rel.shape[1] == d, "relation and node embeddings differ in width"
+    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
+        "filt_q and filt_n: two int32 lists of one length, or neither"
+    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
+    F = 0 if filt_q is None else filt_q.shape[0]
+    if Q:
+        lo, hi = batch.amin(0), batch.amax(0)
+        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
+            if bf16:
+                raise IndexError("triple index out of range")
+            raise AssertionError("triple index out of range")
+    if F:       # an entry out of range would set a bit outside the mask
+        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
+            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    dev = nodes.device
+    greater = torch.empty(Q, device=dev, dtype=torch.int64)
+    ties = torch.empty(Q, device=dev, dtype=torch.int64)
+    tscore = torch.empty(Q, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    with _on(dev), _timed("rank_fused_bf16" if bf16 else "rank_fused"):
+        if bf16:
+            _check(lib().rgcn_distmult_rank_fused_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                       _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips,
+                                                       _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, rel.shape[0], d,
+                                                       _stream(dev)), "distmult_rank_fused_bf16")
+        else:
+            _check(lib().rgcn_distmult_rank_fused_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                      _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips,
+                                                      _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, rel.shape[0], d,
+                                                      _stream(dev)), "distmult_rank_fused")
+    return greater, ties, tscore

@@ -1244,6 +1244,21 @@ def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, ob
     return _native.distmult_score_all(batch, head, nodes, relations, sbias, pbias, obias, out=out)
 
 
+def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0):
+    """(greater, ties, tscore) [Q]: for each triple of `batch` the number of entities that score above its target as the head (head=True)
+    or the tail, the number that score the same (the target included) and the target's score -- the counts `_native.rank_count` takes from
+    the score matrix of distmult_score_all after `_native.rank_filter` on the int32 device lists (filt_q, filt_n), without that matrix
+    (utils/misc.py:40-58, 71-99).  No autograd.  fp32 or bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16
+    (widened here), as in distmult_score_all."""
+    if nodes.dtype == torch.bfloat16:
+        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+        widen = lambda t: None if t is None else t.float()     # noqa: E731
+        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+    return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips)
+
+
 _UNIT = {}
 
 
