@@ -133,3 +133,13 @@ def test_product_never_imports_the_oracle():
             if f.endswith((".py", ".hip", ".cpp", ".h")):
                 src = open(os.path.join(dirpath, f)).read()
                 assert "oracle" not in src.replace("no oracle", ""), os.path.join(dirpath, f)
+
+
+def test_block_tile_backward_takes_with_diag4_what_it_takes_without():
+    """functional._backward_route asks _bwd_blk_plan once, with the caller's diag4: a tall plan the kernel takes for the dense dW it takes
+    for dW's diagonal 4 x 4 blocks too (they need less of the LDS), for every relation count"""
+    lib = ctypes.CDLL(_native._LIB_PATH)
+    for R in list(range(1, 700)) + [4095, 65534, 65535]:
+        dense, diag = lib.rgcn_bwd_blk_max_rows(R, 0), lib.rgcn_bwd_blk_max_rows(R, _native.F_DIAG4)
+        assert diag >= dense, (R, dense, diag)
+        assert not lib.rgcn_bwd_blk_supported(dense, R, 0) or lib.rgcn_bwd_blk_supported(dense, R, _native.F_DIAG4), R

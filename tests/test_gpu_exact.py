@@ -341,10 +341,12 @@ def test_soft_window_forward_and_relation_owner_backward(fix, split, relu, verti
 def test_relation_owner_backward_on_and_off(own, vertical):
     """bwd_own=1: rgcn_bwd_own_f32 (dW in the registers of the relation's owner wave); 0: the block-tile backward on the same graph"""
     from torch_rgcn import _native
+    from torch_rgcn import functional as F_
     with routes.override(bwd_own=own):
         _, layer = run_exact("big", 16, 16, vertical=vertical, expect=("spmm_blk", "bwd_fused"), seed=1)
-    graph = layer._graph
-    assert (graph._plans.get(("win", "bwd_own", _native.bwd_own_rows(graph.num_nodes))) is not None) == (own == "1")
+        graph = layer._graph
+        assert (graph._plans.get(("win", "bwd_own", _native.bwd_own_rows(graph.num_nodes))) is not None) == (own == "1")
+        assert F_._backward_route(graph, 16, 16)[0] == ("own" if own == "1" else "blk")
 
 
 @BOTH
@@ -363,13 +365,61 @@ def test_block_tile_backward(monkeypatch, fix, kernel, relu, vertical):
     """bwd_kernel=blk: the block-tile backward (dX tile in LDS doubles, dW of all relations resident; a hub tile walked in pieces);
     lean: the wave-owned window kernel (hub-split plans fall back to the two-pass backward)"""
     from torch_rgcn import _native
+    from torch_rgcn import functional as F_
     routes.patch(monkeypatch, "bwd_kernel", kernel)
     routes.patch(monkeypatch, "sparse_path", "0")
     routes.patch(monkeypatch, "bwd_own", "0")
     hub = fix == "big_r9hub"
-    run_exact(fix, 16, 16, vertical=vertical, relu=relu, expect=("spmm", "wgrad") if (hub and kernel == "lean") else ("bwd_fused",),
-              forbid=("bwd_fused",) if (hub and kernel == "lean") else ("wgrad",), split="bwd_blk" if (hub and kernel == "blk") else None)
+    _, layer = run_exact(fix, 16, 16, vertical=vertical, relu=relu, expect=("spmm", "wgrad") if (hub and kernel == "lean") else ("bwd_fused",),
+                         forbid=("bwd_fused",) if (hub and kernel == "lean") else ("wgrad",), split="bwd_blk" if (hub and kernel == "blk") else None)
     assert (_native.bwd_blk_rows(40_009, 19) > 64) == (kernel == "blk")
+    assert F_._backward_route(layer._graph, 16, 16)[0] == ("blk" if kernel == "blk" else "split" if hub else "lean")
+
+
+# ----------------------------------------------------------------------------- the dense-weight featured layer's routes, by name
+S0 = dict(sparse_path="0")
+R9 = dict(S0, bwd_own="0")
+ROUTES = [
+    # (fixture, route switches, relu, 4 x 4 blocks) -> (forward, backward) of functional._forward_route / _backward_route, read off their conditions
+    # (DESIGN.md section 7) and the fixtures' sizes; the tests above expect the tags of the same kernels for the same rows
+    ("plain", S0, False, False, "tiles", "lean"),                    # N = 2000: no tall tiles; spmm + bwd_fused (test_wave_owned_tile_plan)
+    ("plain", dict(S0, bwd="split"), False, False, "tiles", "split"),
+    ("plain", dict(S0, deterministic="1"), False, False, "tiles", "lean"),      # (test_backward_variants: bwd_fused in this mode too)
+    ("hub12", S0, False, False, "tiles", "split"),                   # hub-split wave-owned plan: spmm + wgrad
+    ("plain", dict(sparse_path="1", spmm_csr="1"), False, False, "csr", "scatter"),     # R = 7 <= 120; N < 4096: no block-tile backward
+    ("plain", dict(sparse_path="1", spmm_csr="0"), False, False, "two_pass", "scatter"),
+    ("big_r70", dict(sparse_path="1"), False, False, "blk", "scatter"),         # R = 141 > 120; dW of 141 relations leaves the LDS no 64 rows
+    ("big", {}, False, False, "win", "own"),
+    ("big", dict(bwd_own="0"), False, False, "win", "blk"),
+    ("bighub", {}, False, False, "win", "blk"),                      # hub pieces in the owner plan too (the inverse relations): block-tile kernel
+    ("bighub", {}, True, False, "tiles", "blk"),                     # the ReLU epilogue leaves a forward plan with hub pieces
+    ("big_r9", dict(R9, bwd_kernel="blk"), False, False, "win", "blk"),
+    ("big_r9", dict(R9, bwd_kernel="lean"), False, False, "win", "lean"),
+    ("big_r9hub", dict(R9, bwd_kernel="lean"), False, False, "win", "split"),
+    ("plain", dict(sparse_path="1"), False, True, "block_csr", "scatter"),
+]
+
+
+@pytest.mark.parametrize("fix,switches,relu,blocks,fwd,bwd", ROUTES,
+                         ids=[f"{r[0]}-{'-'.join(f'{k}={v}' for k, v in r[1].items()) or 'defaults'}{'-relu' * r[2]}{'-blocks' * r[3]}" for r in ROUTES])
+def test_route_names(fix, switches, relu, blocks, fwd, bwd):
+    """the two decisions of _RelationalMP, asked with the layer's graph and the shapes alone: the names, and "split" -- which asks the graph
+    for no fused-backward plan -- whenever X or W is frozen.  No tensors, no oracle: one forward on zeros builds the graph"""
+    from torch_rgcn import functional as F_
+    fx = fixture(fix)
+    mode = "block" if blocks else "none"
+    shapes = _param_shapes(fx["R"], fx["N"], 16, 16, mode, False, 3, 4, False)
+    params = {n: np.zeros(shape, np.float32) for n, shape in shapes.items()}
+    layer = make_layer(fx, params, params.pop("bias"), 16, 16, mode, False, False, 3, 4, False)
+    with routes.override(**switches), torch.no_grad():
+        layer(torch.zeros(fx["N"], 16, device=DEV))
+        graph = layer._graph
+        before = set(graph._plans)
+        assert F_._backward_route(graph, 16, 16, need_x=False, diag4=blocks)[0] == "split"
+        assert F_._backward_route(graph, 16, 16, need_w=False, diag4=blocks)[0] == "split"
+        assert set(graph._plans) == before, "a frozen input: no plan is asked for"
+        got = F_._forward_route(graph, fx["R"], 16, 16, relu=relu, blocks4=blocks)[0], F_._backward_route(graph, 16, 16, diag4=blocks)[0]
+    assert got == (fwd, bwd), got
 
 
 # ----------------------------------------------------------------------------- fp32, other widths

@@ -380,7 +380,7 @@ def test_distmult_all_frozen_scores_only(monkeypatch, bwd, d):
 # ----------------------------------------------------------------------------- wrapper flags no layer reaches
 @pytest.mark.parametrize("kernel", ["bwd_own", "bwd_own_bf16", "bwd_fused-blk", "bwd_fused-lean"])
 def test_wrappers_without_bias_gradient(monkeypatch, kernel):
-    """_fused_backward always asks the fp32 kernels for db; want_db=False (a null db pointer in the relation-owner and block-tile kernels) is
+    """_RelationalMP._backward always asks the fp32 kernels for db; want_db=False (a null db pointer in the relation-owner and block-tile kernels) is
     reached only by calling the wrappers: on the layer's own plan, dX and dW equal to the oracle and no db returned"""
     from torch_rgcn import _native
     fix = {"bwd_own": "big", "bwd_own_bf16": "big", "bwd_fused-blk": "big_r9", "bwd_fused-lean": "plain"}[kernel]

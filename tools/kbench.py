@@ -126,11 +126,10 @@ if "bwd" in a.what:
         balg = M * (4 * d + 8) + 2 * N * 4 * d
         print(f"[{tag} K={os.environ.get('RGCN_BWD_KERNEL', 'blk')} NW={os.environ.get('RGCN_BWD_NW', '-')} BP={os.environ.get('RGCN_BWD_BPERM', '-')}] bwd_fused {'atomic' if atomic else 'partial'} tile={bp.tile_rows} relerr dX {e1:.2e} dW {e2:.2e} "
               f"med {med:.3f} ms min {mn:.3f} ms -> {balg / med / 1e6:.0f} GB/s algorithmic (backward bytes)", flush=True)
-    if _native.bwd_fused_relu_ok(bp):        # ReLU mask fused into the dX epilogue (window kernel)
-        Xr = torch.relu(X)
-        dxr, dwr = _native.bwd_fused(G, Xr, W, bp, atomic=True, relu=True)
-        dx0, dw0 = _native.bwd_fused(G, Xr, W, bp, atomic=True)
-        print("relu-masked dX == mask(dX):", bool(torch.allclose(dxr, dx0 * (Xr > 0), rtol=1e-5, atol=1e-6 * dx0.abs().max().item())), "dW relerr", ((dwr - dw0).abs().max() / dw0.abs().max()).item(), flush=True)
+    Xr = torch.relu(X)          # ReLU mask fused into the dX epilogue (both fused kernels have it)
+    dxr, dwr = _native.bwd_fused(G, Xr, W, bp, atomic=True, relu=True)
+    dx0, dw0 = _native.bwd_fused(G, Xr, W, bp, atomic=True)
+    print("relu-masked dX == mask(dX):", bool(torch.allclose(dxr, dx0 * (Xr > 0), rtol=1e-5, atol=1e-6 * dx0.abs().max().item())), "dW relerr", ((dwr - dw0).abs().max() / dw0.abs().max()).item(), flush=True)
     d2 = _native.bwd_fused(G, X, W, bp64)
     d3 = _native.bwd_fused(G, X, W, bp64)
     print("bwd_fused (partial) bitwise reproducible:", bool(torch.equal(d2[0], d3[0]) and torch.equal(d2[1], d3[1])), flush=True)

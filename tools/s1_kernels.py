@@ -46,8 +46,16 @@ def timeit(fn):
 
 
 if "fwd" in a.what:
-    plan = functional._fwd_win(g, True)
+    route, plan = functional._forward_route(g, R, 16, 16, relu=True)
+    plan = plan if route == "win" else None
     fn = (lambda: _native.spmm_blk(X, W, b, plan, relu=True)) if plan is not None else (lambda: _native.spmm(X, W, b, g.fwd_plan(16), relu=True))
     print("forward", "spmm_blk on the soft-window plan" if plan is not None else "spmm_d16", f"{timeit(fn):.3f} ms", flush=True)
 if "bwd" in a.what:
-    print("backward", f"{timeit(lambda: functional._fused_backward(X, W, G, g, relu_in=True, want_db=True)):.3f} ms", flush=True)
+    route, bp = functional._backward_route(g, 16, 16)
+    if route == "own":
+        print("backward own", f"{timeit(lambda: _native.bwd_own(G, X, W, bp, relu=True, want_db=True)):.3f} ms", flush=True)
+    elif route in ("blk", "blk_forced", "lean"):
+        atomic = not functional.deterministic()
+        print("backward", route, f"{timeit(lambda: _native.bwd_fused(G, X, W, bp, atomic=atomic, relu=True, want_db=True)):.3f} ms", flush=True)
+    else:
+        print(f"backward: route {route!r} is not one fused launch on this graph (too small, hub-split, RGCN_BWD=split): nothing to time", flush=True)

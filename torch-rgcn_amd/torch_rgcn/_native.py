@@ -1416,8 +1416,7 @@ def bwd_blk_rows(n_nodes, num_rels, deterministic=False, device=None, diag4=Fals
     diag4: the weights are block_diag() of 4 x 4 blocks (only the diagonal blocks of dW are kept: AM's 267 relations leave 406 rows)"""
     if bwd_route() != "blk" or deterministic or n_nodes < (_BLK_MIN_NODES_SPARSE if sparse else _BLK_MIN_NODES):
         return 0
-    cap = int(lib().rgcn_bwd_blk_max_rows(num_rels, F_DIAG4 if diag4 else 0))
-    cap = min(cap, int(routes.get("bwd_blk_cap", "512")))
+    cap = int(lib().rgcn_bwd_blk_max_rows(num_rels, F_DIAG4 if diag4 else 0))      # (at most 512)
     if cap < 64:
         return 0
     return max(_even_tile_rows(n_nodes, cap, device), min(cap, 128))      # small graphs: fewer, taller tiles (fuller buckets, fewer dW flushes) rather than one per CU
@@ -1435,7 +1434,7 @@ def spmm_blk_rows(n_nodes, device=None):
     every CU the same number of tiles; 0 for graphs too small to fill the chip with one tile per workgroup"""
     if n_nodes < _BLK_MIN_NODES or routes.get("spmm_csr", "1") == "0":
         return 0
-    cap = min(1000, int(lib().rgcn_spmm_blk_max_rows()), int(routes.get("fwd_rows_cap", "1000")))
+    cap = min(1000, int(lib().rgcn_spmm_blk_max_rows()))
     return _even_tile_rows(n_nodes, cap, device)
 
 
@@ -1521,13 +1520,15 @@ def _bwd_blk_plan(plan, diag4=False):
         bool(lib().rgcn_bwd_blk_supported(plan.tile_rows, plan.num_rels, F_DIAG4 if diag4 else 0))
 
 
-def bwd_fused_ok(plan, diag4=False):
+def bwd_fused_ok(plan, diag4=False, blk=None):
     """the fused backward kernels walk the transposed plan tile by tile: packed slots and run pointers.  The wave-owned forms
     take a whole tile per wave (no hub-split work units, at most 160 rows: dX tiles + scratch + staging within the LDS); the
-    block-tile form deals a tile's chunks to 16 waves itself and ignores the work units"""
+    block-tile form deals a tile's chunks to 16 waves itself and ignores the work units.  blk: _bwd_blk_plan(plan, diag4)'s answer, where the
+    caller has it (diag4 is then not looked at)"""
+    assert blk is None or not diag4
     if plan.run_ptr is None or plan.n_tiles <= 0 or plan.n_src >= (1 << 24):
         return False
-    if _bwd_blk_plan(plan, diag4):
+    if _bwd_blk_plan(plan, diag4) if blk is None else blk:
         return True             # (tiles above 255 rows have no packed slots: the lean slots are made from the unpacked arrays)
     # (the lean window kernel: its LDS holds the dX tile + X tile + scratch of at least 8 waves; round 2's staging kernel, which took the
     # taller wave-owned tiles up to 160 rows, is gone -- such plans only come from experimental routes and take the two-pass backward)
@@ -1642,11 +1643,6 @@ def bwd_own_bf16(G, X, W, plan, relu=False, want_db=False):
                                        plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(db) if want_db else None, plan.n_src,
                                        _stream(dev)), "bwd_own_bf16")
     return (dX, dW, db if want_db else None)
-
-
-def bwd_fused_relu_ok(plan, diag4=False):
-    """RGCN_F_RELU (dX masked with X > 0 in the epilogue): both fused kernels have it"""
-    return bool(_bwd_blk_plan(plan, diag4)) or bwd_fused_ok(plan, diag4)
 
 
 def bwd_fused(G, X, W, plan, atomic=False, relu=False, want_db=False, diag4=False):

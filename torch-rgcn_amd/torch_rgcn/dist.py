@@ -142,7 +142,7 @@ def gather_owned_parameters(layer):
     its owner (sum all-reduce of the rows masked by ownership).  Collective: call it on every rank."""
     group = layer._shard_group
     graph = layer._graph
-    assert graph is not None and getattr(graph, "owned_relations", None) is not None, \
+    assert graph is not None and graph.owned_relations is not None, \
         "run one forward (the shard's graph is built lazily) before gathering parameters"
     out = {}
     for name in _PER_RELATION_PARAMS:
@@ -169,7 +169,7 @@ def sync_owned_parameters(layer):
 def filter_graph_for_rank(graph, group):
     """Drop the messages of relations owned by other ranks (in place, before any plan is built)."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
-    if getattr(graph, "_dev", None) is not None:   # message list lives on the GPU: shard through the alive mask
+    if graph._dev is not None:   # message list lives on the GPU: shard through the alive mask
         s, p, o, val, alive = graph._dev
         live = torch.ones_like(p, dtype=torch.bool) if alive is None else alive != 0
         counts = torch.bincount(p[live].long(), minlength=graph.num_rels).cpu().numpy()

@@ -8,13 +8,9 @@ Both are the custom-Function form of what the reference leaves to autograd
 autograd engine's thread and launches on that thread's current HIP stream; it uses
 nothing but the tensors saved on ctx and the immutable RelGraph.
 """
-import os
-
 import torch
 
-from . import routes
-
-from . import _native
+from . import _native, routes
 
 
 def _wgrad_tiles(plan):
@@ -24,10 +20,9 @@ def _wgrad_tiles(plan):
     return int(env) if env else (8 if plan.n_tiles >= 4096 else 4)
 
 
-def _sparse_buckets(graph, W):
+def _sparse_buckets(graph, d_in, d_out):
     """hidden 16 and (tile, relation) buckets so small that the 16-slot chunks are mostly padding"""
-    if W.shape[1] != 16 or W.shape[2] != 16 or getattr(graph, "_dev", None) is None or getattr(graph, "sync_free", False) or \
-            getattr(graph, "per_call", False):
+    if d_in != 16 or d_out != 16 or graph._dev is None or graph.sync_free or graph.per_call:
         return False            # (the two-pass path sizes its scratch by a message count read back from the device)
     mode = routes.get("sparse_path", "auto")
     if mode != "auto":
@@ -39,24 +34,45 @@ def _sparse_buckets(graph, W):
     return graph.max_degree() <= 4096
 
 
-def _fwd_blk(graph, relu):
-    """the forward plan of tall tiles for rgcn_spmm_blk_f32, or None (graph too small, route off, ReLU epilogue on a plan with hub pieces,
-    deterministic mode: the tile is summed in arrival order)"""
-    if deterministic():
-        return None
-    plan = graph.fwd_blk_plan()
-    if plan is None or (relu and _native._blk_units(plan)[2]):
-        return None
-    return plan
+def _hub_free(plan):
+    """a plan of tall tiles, none of them cut into hub pieces (what the relation-owner backward and a ReLU epilogue need)"""
+    return plan is not None and not _native._blk_units(plan)[2]
 
 
-def _fwd_win(graph, relu):
-    """the forward plan in soft-window order (graph.win_plan) for rgcn_spmm_blk_f32, or None; the ReLU epilogue needs tiles that are not cut
-    into hub pieces (as _fwd_blk)"""
-    plan = graph.win_plan("fwd") if hasattr(graph, "win_plan") else None
-    if plan is None or (relu and _native._blk_units(plan)[2]):
-        return None
-    return plan
+def _tall_plan(plan, relu):
+    """a forward plan of tall tiles for rgcn_spmm_blk_f32 / _bf16 as it is, or None: no such plan, or the ReLU epilogue on tiles cut into hub pieces"""
+    return plan if plan is not None and (not relu or _hub_free(plan)) else None
+
+
+def _forward_route(graph, R, d_in, d_out, relu=False, blocks4=False):
+    """(name, plan) of the forward of _RelationalMP at the padded shape [R, d_in, d_out]; relu: the ReLU epilogue is
+    wanted; blocks4: W = block_diag(4 x 4 blocks) at width 16 and the caller holds the blocks.  Builds forward plans only."""
+    # spmm_csr=0 asks for the two-pass forward: it turns every one-launch kernel of width 16 off -- the CSR kernel, and with it both plans of
+    # tall tiles (_native.spmm_blk_rows gives them no rows then: graph.fwd_blk_plan() and graph.win_plan("fwd") are None)
+    one_launch = routes.get("spmm_csr", "1") != "0"
+    if _sparse_buckets(graph, d_in, d_out):
+        csr = graph.csr("fwd")
+        if blocks4 and routes.get("block_fwd", "1") != "0":
+            # W = block_diag(blocks), 4 x 4 blocks, sparse buckets (AM): the forward reads the blocks themselves on the CSR
+            # kernel (block table in LDS; one gather per message, no transformed-row buffer): 0.46 ms against 0.65 ms for the
+            # two passes below.  The backward stays on the dense W (dX rows + dW from one relation-major walk; autograd
+            # through block_diag() picks the blocks' gradient out of dW).
+            return "block_csr", csr
+        if one_launch and _native.spmm_csr_d16_ok(csr, R):
+            # sparse buckets, up to 120 relations: ONE pass over the destination-major CSR, messages of mixed relations, W in LDS
+            return "csr", csr
+        # sparse buckets, more relations than the CSR kernel's LDS holds (AM as shipped, layer 2: R = 267): the forward plan cut into
+        # tall workgroup-owned tiles (31 messages per (tile, relation) bucket instead of ~2), one launch, no [M, 16] intermediate
+        # (not in deterministic mode: the tile is summed in arrival order)
+        plan = _tall_plan(graph.fwd_blk_plan(), relu) if one_launch and not deterministic() else None
+        return ("blk", plan) if plan is not None else ("two_pass", None)
+    if d_in == 16 and d_out == 16 and one_launch:
+        # dense buckets on a large static graph (S1): tall workgroup-owned tiles walked in soft-window order -- the whole chip gathers
+        # from a few MB of X at any time (0.33 ms against 0.42 on the wave-owned tiles, tools/softwin_probe.py)
+        plan = _tall_plan(graph.win_plan("fwd"), relu)
+        if plan is not None:
+            return "win", plan
+    return "tiles", None
 
 
 def _pad_blocks(X, W, bias, graph=None):
@@ -67,7 +83,7 @@ def _pad_blocks(X, W, bias, graph=None):
     -> (X', W', bias', (d_in, d_out)) or the inputs unchanged and None."""
     d_in, d_out = W.shape[1], W.shape[2]
     pi, po = -d_in % 16, -d_out % 16
-    if max(d_in, d_out) > _BLOCKED_MAX or (pi == 0 and po == 0) or routes.get("pad16", "1") == "0" or \
+    if max(d_in, d_out) > _BLOCKED_MAX or (pi == 0 and po == 0) or \
             (graph is not None and _wide_gemm_path(graph, d_in, d_out)):       # (the gather-GEMM takes ragged widths as they are)
         return X, W, bias, None
     # one launch for W and the bias together (torch.nn.functional.pad: a fill and a copy each)
@@ -88,7 +104,7 @@ _BLOCKED_MAX = 512     # widest layer that is cut into 64-wide blocks of the MFM
 def _wide_gemm_path(graph, d_in, d_out):
     """undecomposed weights above width 64: relation-grouped gather-GEMM on the matrix cores + per-destination row sum
     (csrc/rgcn_gemm.hip); needs the device-side graph and host-known message counts (not the sync-free per-call build)"""
-    return max(d_in, d_out) > 64 and getattr(graph, "_dev", None) is not None and not getattr(graph, "sync_free", False)
+    return max(d_in, d_out) > 64 and graph._dev is not None and not graph.sync_free
 
 
 def _spmm_blocked(X, W, bias, plan_of, relu=False, graph=None, kind="fwd"):
@@ -98,8 +114,7 @@ def _spmm_blocked(X, W, bias, plan_of, relu=False, graph=None, kind="fwd"):
     d_in, d_out = W.shape[1], W.shape[2]
     if graph is not None and _wide_gemm_path(graph, d_in, d_out):
         return _native.spmm_wide_two_pass(X, W, bias, graph.scatter_plan(kind, 8), graph.csr(kind), relu=relu)
-    if max(d_in, d_out) <= 64 or d_in % 16 or d_out % 16 or max(d_in, d_out) > _BLOCKED_MAX or \
-            routes.get("pad16", "1") == "0":
+    if max(d_in, d_out) <= 64 or d_in % 16 or d_out % 16 or max(d_in, d_out) > _BLOCKED_MAX:
         return _native.spmm(X, W, bias, plan_of(d_out), relu=relu and max(d_in, d_out) <= 64)
     xs = [X[:, i:i + 64].contiguous() for i in range(0, d_in, 64)]
     cols = []
@@ -120,6 +135,17 @@ def _zero_padded_rows(t, wide):
         return False
     # the mark is a Python attribute: it survives set_() / resize_() / .data swaps of the tensor object -- the storage must still hold the rows
     return t.untyped_storage().nbytes() >= (t.storage_offset() + t.shape[0] * wide) * t.element_size()
+
+
+def _padded_grad(g, dims):
+    """the upstream gradient of a layer whose widths _pad_blocks padded (dims), dense, at the padded output width"""
+    if dims is not None and dims[1] % 16:
+        wide = dims[1] + (-dims[1] % 16)
+        if _zero_padded_rows(g, wide):
+            g = torch.as_strided(g, (g.shape[0], wide), (wide, 1))       # MaskedCrossEntropy wrote the zero-padded rows already
+        else:
+            g = _native.resize3(dense(g), (g.shape[0], wide))
+    return dense(g)
 
 
 def _unpad_blocks(dims, dX, dW, db, dx_view=False):
@@ -196,29 +222,40 @@ class _ReluToken:
         return self.ref is not None and self.ref() is g and g._version == self.version
 
 
-def _fused_backward(X, W, g, graph, relu_in=False, want_db=False, diag4=False, sparse=False):
-    """hidden 16, both gradients wanted: ONE walk of the transposed plan gathers G[s] once per message and produces dX
-    and dW together (csrc/rgcn_bwd.hip).  None when the plan does not qualify (hub-split tiles, unpacked slots) or
-    RGCN_BWD=split asks for round 1's two-pass backward.  relu_in: X is the output of a ReLU and dX is wanted before it
-    (masked with X > 0 in the kernel's epilogue); returns (dX, dW, masked, db) -- db: the bias gradient when want_db and the kernel
-    sums G's columns on the side (block-tile kernel), else None."""
-    if W.shape[1] != 16 or W.shape[2] != 16 or routes.get("bwd", "fused") == "split":
-        return None
-    if not diag4 and not sparse and routes.get("bwd_own", "1") != "0" and _native.bwd_route() == "blk" and hasattr(graph, "win_plan"):
+def _backward_route(graph, d_in, d_out, need_x=True, need_w=True, diag4=False, sparse=None):
+    """(name, plan) of the backward of _RelationalMP at the padded widths, from the routes table as it is NOW.
+    own / blk / lean: hidden 16, both gradients wanted -- ONE walk of a transposed plan gathers G[s] once per message and produces dX and dW
+    together (blk_forced: the block-tile kernel on the wave-owned plan of a forced tile height, RGCN_TILE_ROWS, never with diag4); scatter: the same on the relation-major plan of sparse buckets; split: a kernel per gradient (X or W frozen, other widths,
+    RGCN_BWD=split, plans no fused kernel takes: hub-split tiles, unpacked slots) -- and then no fused-backward plan is asked for.
+    diag4: W = block_diag(4 x 4 blocks) and only dW's diagonal blocks are wanted (block-tile kernel only).  sparse: the sparse-bucket test
+    where the caller has its answer (the relation-sharded layer: never)."""
+    if not (need_x and need_w) or d_in != 16 or d_out != 16 or routes.get("bwd", "fused") == "split":
+        return "split", None
+    if sparse is None:
+        sparse = _sparse_buckets(graph, d_in, d_out)
+    if not diag4 and not sparse and routes.get("bwd_own", "1") != "0" and _native.bwd_route() == "blk":
         # large static graph with dense buckets (S1): tall tiles in soft-window order, every relation's dW in the registers of its owner wave
         op = graph.win_plan("bwd_own")
-        if op is not None and not _native._blk_units(op)[2]:
-            dX, dW, db = _native.bwd_own(g, X, W, op, relu=relu_in, want_db=True)
-            return dX, dW, relu_in, (db if want_db else None)
-    bp = graph.bwd_blk_plan(diag4, sparse)                  # tall tiles, one per workgroup -- or the wave-owned 64-row plan
-    diag4 = diag4 and bp is not None and _native._bwd_blk_plan(bp, True)   # block-diagonal W (4 x 4 blocks): only on the block-tile kernel
-    if bp is None or not _native._bwd_blk_plan(bp, diag4):
-        bp = graph.bwd_plan(16)
-    if not _native.bwd_fused_ok(bp, diag4):
-        return None
-    masked = relu_in and _native.bwd_fused_relu_ok(bp, diag4)
-    dX, dW, db = _native.bwd_fused(g, X, W, bp, atomic=not deterministic(), relu=masked, want_db=True, diag4=diag4)
-    return dX, dW, masked, (db if want_db else None)
+        if _hub_free(op):
+            return "own", op
+    # sparse (tile, relation) buckets normally leave the tile plan -- except on a graph the block-tile kernel takes: its tall tiles
+    # (128 .. 512 rows) hold several messages per bucket where a 64-row tile holds one or two, and dW of all relations (block-diagonal
+    # weights: its diagonal blocks) fits the workgroup's LDS.  One launch instead of the two-pass backward's three.
+    rows = _native.bwd_blk_rows(graph.num_nodes, graph.num_rels, deterministic(), graph.device, diag4, sparse)
+    if rows or not sparse:
+        bp = graph.bwd_blk_plan(rows=rows)                  # tall tiles, one per workgroup -- or the wave-owned 64-row plan
+        # (a plan the kernel takes without diag4 it takes with it -- the diagonal blocks need less LDS --, so one question settles both)
+        name = "blk" if bp is not None and _native._bwd_blk_plan(bp, diag4) else "lean"
+        if name == "lean":
+            bp = graph.bwd_plan(16)
+            if _native._bwd_blk_plan(bp):                   # (64 rows: no; a forced tile height, RGCN_TILE_ROWS, may be taller)
+                name = "blk_forced"
+        if _native.bwd_fused_ok(bp, blk=name != "lean"):
+            return name, bp
+    if sparse and routes.get("twopass", "gather") == "gather" and not deterministic():
+        # sparse buckets: relation-major walk, G[s] and X[o] gathered once each for dX's rows and dW together
+        return "scatter", graph.scatter_plan("bwd")
+    return "split", None
 
 
 def _weight_gradient(X, W, g, graph):
@@ -254,28 +291,18 @@ class _RelationalMP(torch.autograd.Function):
         W = dense(W)
         b = None if bias is None else dense(bias)
         fused_relu = relu and (max(W.shape[1], W.shape[2]) <= 64 or _wide_gemm_path(graph, W.shape[1], W.shape[2]))   # kernel epilogues
+        # W = block_diag(4 x 4 blocks) at width 16: the backward may keep only dW's diagonal blocks (block-tile kernel, R <= 447)
+        ctx.diag4 = blocks is not None and ctx.dims is None and tuple(blocks.shape[2:]) == (4, 4) and W.shape[1] == 16 and W.shape[2] == 16
+        route, plan = _forward_route(graph, *W.shape, relu=fused_relu, blocks4=ctx.diag4)
         with _native.w16_scope() as w16:        # [R,16,16] weights: both fragment orders packed once, handed to the backward below
-            if _sparse_buckets(graph, W) and blocks is not None and ctx.dims is None and tuple(blocks.shape[2:]) == (4, 4) and \
-                    routes.get("block_fwd", "1") != "0":
-                # W = block_diag(blocks), 4 x 4 blocks, sparse buckets (AM): the forward reads the blocks themselves on the CSR
-                # kernel (block table in LDS; one gather per message, no transformed-row buffer): 0.46 ms against 0.65 ms for the
-                # two passes below.  The backward stays on the dense W (dX rows + dW from one relation-major walk; autograd
-                # through block_diag() picks the blocks' gradient out of dW).
-                out = _native.block_spmm(X, blocks.detach().contiguous(), b, graph.csr("fwd"), relu=fused_relu)
-            elif _sparse_buckets(graph, W) and routes.get("spmm_csr", "1") != "0" and \
-                    _native.spmm_csr_d16_ok(graph.csr("fwd"), W.shape[0]):
-                # sparse buckets, up to 120 relations: ONE pass over the destination-major CSR, messages of mixed relations, W in LDS
-                out = _native.spmm_csr_d16(X, W, b, graph.csr("fwd"), relu=fused_relu)
-            elif _sparse_buckets(graph, W) and _fwd_blk(graph, fused_relu) is not None:
-                # sparse buckets, more relations than the CSR kernel's LDS holds (AM as shipped, layer 2: R = 267): the forward plan cut into
-                # tall workgroup-owned tiles (31 messages per (tile, relation) bucket instead of ~2), one launch, no [M, 16] intermediate
-                out = _native.spmm_blk(X, W, b, _fwd_blk(graph, fused_relu), relu=fused_relu)
-            elif _sparse_buckets(graph, W):
+            if route == "block_csr":
+                out = _native.block_spmm(X, blocks.detach().contiguous(), b, plan, relu=fused_relu)
+            elif route == "csr":
+                out = _native.spmm_csr_d16(X, W, b, plan, relu=fused_relu)
+            elif route in ("blk", "win"):
+                out = _native.spmm_blk(X, W, b, plan, relu=fused_relu)
+            elif route == "two_pass":
                 out = _native.spmm_two_pass(X, W, b, graph.scatter_plan("fwd"), graph.csr("fwd"), relu=fused_relu)
-            elif W.shape[1] == 16 and W.shape[2] == 16 and _fwd_win(graph, fused_relu) is not None:
-                # dense buckets on a large static graph (S1): tall workgroup-owned tiles walked in soft-window order -- the whole chip gathers
-                # from a few MB of X at any time (0.33 ms against 0.42 on the wave-owned tiles, tools/softwin_probe.py)
-                out = _native.spmm_blk(X, W, b, _fwd_win(graph, fused_relu), relu=fused_relu)
             else:
                 out = _spmm_blocked(X, W, b, graph.fwd_plan, relu=fused_relu, graph=graph, kind="fwd")
         ctx.w16 = w16.pair(W)
@@ -284,8 +311,6 @@ class _RelationalMP(torch.autograd.Function):
         ctx.graph = graph
         ctx.has_bias = bias is not None
         ctx.relu = relu
-        # W = block_diag(4 x 4 blocks) at width 16: the backward may keep only dW's diagonal blocks (block-tile kernel, R <= 447)
-        ctx.diag4 = blocks is not None and ctx.dims is None and tuple(blocks.shape[2:]) == (4, 4) and W.shape[1] == 16 and W.shape[2] == 16
         if relu:
             ctx.save_for_backward(X, W, out)
         else:
@@ -305,37 +330,22 @@ class _RelationalMP(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, g, X, W):
         graph = ctx.graph
-        if ctx.dims is not None and ctx.dims[1] % 16:
-            wide = ctx.dims[1] + (-ctx.dims[1] % 16)
-            if _zero_padded_rows(g, wide):
-                g = torch.as_strided(g, (g.shape[0], wide), (wide, 1))       # MaskedCrossEntropy wrote the zero-padded rows already
-            else:
-                g = _native.resize3(dense(g), (g.shape[0], wide))
-        g = dense(g)
+        g = _padded_grad(g, ctx.dims)
         if ctx.relu and not ctx.out_token.premasked(g):     # out = relu(pre): the gradient passes where the stored output is positive
             g = torch.ops.aten.threshold_backward(g, ctx.saved_tensors[2], 0.0)
         dX = dW = db = None
-        sparse = _sparse_buckets(graph, W)
-        both = None
-        masked = False
-        # sparse (tile, relation) buckets normally leave the tile plan -- except on a graph the block-tile kernel takes: its tall tiles
-        # (128 .. 512 rows) hold several messages per bucket where a 64-row tile holds one or two, and dW of all relations (block-diagonal
-        # weights: its diagonal blocks) fits the workgroup's LDS.  One launch instead of the two-pass backward's three.
-        blk_sparse = sparse and routes.get("bwd", "fused") != "split" and \
-            _native.bwd_blk_rows(graph.num_nodes, graph.num_rels, deterministic(), graph.device, ctx.diag4, True) > 0
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and (not sparse or blk_sparse):
-            both = _fused_backward(X, W, g, graph, relu_in=ctx.in_token is not None and ctx.in_token.private and (ctx.dims is None or ctx.dims[0] % 16 == 0) and not ctx.in_token.observed(),
-                                   want_db=ctx.has_bias and ctx.needs_input_grad[2], diag4=ctx.diag4, sparse=sparse)
-            if both is not None:
-                both, masked, db = both[:2], both[2], both[3]
-        if both is None and sparse and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and routes.get("bwd", "fused") != "split" \
-                and routes.get("twopass", "gather") == "gather" and not deterministic():
-            # sparse buckets: relation-major walk, G[s] and X[o] gathered once each for dX's rows and dW together
-            # (the producer's ReLU mask rides on the transformed rows: same condition as for the fused kernels above)
-            masked = ctx.in_token is not None and ctx.in_token.private and not ctx.in_token.observed()
-            both = _native.bwd_two_pass_fused(g, X, W, graph.scatter_plan("bwd"), graph.csr("bwd"), relu=masked)
-        if both is not None:
-            dX, dW = both
+        sparse = _sparse_buckets(graph, W.shape[1], W.shape[2])
+        route, plan = _backward_route(graph, W.shape[1], W.shape[2], ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.diag4, sparse)
+        # X is the output of a ReLU whose producer left the masking to this layer (_ReluToken): dX is wanted BEFORE it, masked with X > 0 in
+        # the fused kernel's epilogue (scatter: the mask rides on the transformed rows, at any input width)
+        masked = route != "split" and ctx.in_token is not None and ctx.in_token.private and not ctx.in_token.observed() and \
+            (route == "scatter" or ctx.dims is None or ctx.dims[0] % 16 == 0)
+        if route == "own":
+            dX, dW, db = _native.bwd_own(g, X, W, plan, relu=masked, want_db=True)
+        elif route in ("blk", "blk_forced", "lean"):
+            dX, dW, db = _native.bwd_fused(g, X, W, plan, atomic=not deterministic(), relu=masked, want_db=True, diag4=route == "blk" and ctx.diag4)
+        elif route == "scatter":
+            dX, dW = _native.bwd_two_pass_fused(g, X, W, plan, graph.csr("bwd"), relu=masked)
         else:
             if ctx.needs_input_grad[0]:
                 Wt = W.transpose(1, 2).contiguous()
@@ -345,8 +355,8 @@ class _RelationalMP(torch.autograd.Function):
                     dX = _spmm_blocked(g, Wt, None, graph.bwd_plan, graph=graph, kind="bwd")
             if ctx.needs_input_grad[1]:
                 dW = _weight_gradient(X, W, g, graph)
-        if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
-            db = _native.colsum(g)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        db = (db if db is not None else _native.colsum(g)) if want_db else None      # (the relation-owner and block-tile kernels sum G's columns on the side)
         res = _unpad_blocks(ctx.dims, dX, dW, db, getattr(ctx, "dx_view", False))
         if masked:
             ctx.in_token.mark(res[0])                 # the tensor autograd is handed (a view or a crop of dX for padded widths) already is the
@@ -366,10 +376,10 @@ def _bf16_native_plans(graph, d_in, d_out, relu):
     rgcn_wgrad_bf16 on the relation-major plan, rgcn_colsum_bf16."""
     if max(d_in, d_out) > 64 or deterministic():
         return None
-    if d_in == 16 and d_out == 16 and routes.get("bwd_own", "1") != "0" and hasattr(graph, "win_plan"):
-        fp = _fwd_win(graph, relu)
+    if d_in == 16 and d_out == 16 and routes.get("bwd_own", "1") != "0":
+        fp = _tall_plan(graph.win_plan("fwd"), relu)
         op = graph.win_plan("bwd_own") if fp is not None else None
-        if op is not None and not _native._blk_units(op)[2]:
+        if _hub_free(op):
             return "win", fp, op
     fp, bp = graph.fwd_plan(d_out), graph.bwd_plan(d_in)
     if fp.pack is None or bp.pack is None or fp.n_src >= (1 << 24) or bp.n_src >= (1 << 24):
@@ -532,13 +542,7 @@ class _ShardedRelationalMP(torch.autograd.Function):
     def _backward(ctx, g, X, W):
         import torch.distributed as dist
         graph = ctx.graph
-        if ctx.dims is not None and ctx.dims[1] % 16:
-            wide = ctx.dims[1] + (-ctx.dims[1] % 16)
-            if _zero_padded_rows(g, wide):
-                g = torch.as_strided(g, (g.shape[0], wide), (wide, 1))       # MaskedCrossEntropy wrote the zero-padded rows already
-            else:
-                g = _native.resize3(dense(g), (g.shape[0], wide))
-        g = dense(g)
+        g = _padded_grad(g, ctx.dims)
         dX = dW = db = None
         works = []
         slabbed = ctx.n_slabs > 0 and ctx.comm == "allreduce"
@@ -553,8 +557,11 @@ class _ShardedRelationalMP(torch.autograd.Function):
                 dX, dW, _ = _native.bwd_fused_slabs(g, X, W, bp, ctx.n_slabs,
                                                     lambda o, r0, r1: works.append(dist.all_reduce(o[r0:r1], group=ctx.group, async_op=True)))
                 both, joined = (dX, dW), True
-        if both is None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not slabbed:
-            both = _fused_backward(X, W, g, graph)
+        if not slabbed:         # (a rank's share of the relations never takes the sparse-bucket routes)
+            route, plan = _backward_route(graph, W.shape[1], W.shape[2], ctx.needs_input_grad[0], ctx.needs_input_grad[1], sparse=False)
+            if route != "split":
+                both = _native.bwd_own(g, X, W, plan, want_db=True) if route == "own" else \
+                    _native.bwd_fused(g, X, W, plan, atomic=not deterministic(), want_db=True)
         if both is not None:
             dX, dW = both[:2]
         else:
@@ -583,8 +590,7 @@ def sharded_relational_mp(features, weights, bias, graph, group, n_slabs=0, comm
 def _featureless_csr(graph, width):
     """the featureless layer's route: destination-major CSR kernels (one lane group per message) when the (tile, relation) buckets
     of the tile plan are mostly padding (AIFB: 91 relations on 8-row tiles, 23 slots per message) and the graph is static"""
-    if getattr(graph, "_dev", None) is None or getattr(graph, "sync_free", False) or getattr(graph, "per_call", False) or \
-            routes.get("featureless_csr", "auto") == "0":
+    if graph._dev is None or graph.sync_free or graph.per_call or routes.get("featureless_csr", "auto") == "0":
         return False
     if routes.get("featureless_csr", "auto") == "1":
         return True
@@ -689,7 +695,7 @@ def use_block_path(graph, blocks):
     forward + backward against 2.43 -- every message re-reads its blocks from L2, 4x the bytes of its feature row), so
     RGCN_BLOCK_PATH=1 (default) takes the block kernels only above width 16; 2 = whenever supported; 0 = never."""
     mode = routes.get("block_path", "1")
-    if mode == "0" or getattr(graph, "_dev", None) is None or not _native.block_supported(blocks.shape[2], blocks.shape[3]):
+    if mode == "0" or graph._dev is None or not _native.block_supported(blocks.shape[2], blocks.shape[3]):
         return False
     wide = blocks.shape[1] * blocks.shape[2] > 16 or blocks.shape[1] * blocks.shape[3] > 16
     return wide or mode == "2"
@@ -731,7 +737,7 @@ def diag_mp(features, w, bias, graph):
 
 def use_diag_path(graph, d):
     """the diagonal kernels need the device-side graph build (CSR + relation-major plan)"""
-    return getattr(graph, "_dev", None) is not None and routes.get("diag_path") != "0"
+    return graph._dev is not None and routes.get("diag_path") != "0"
 
 
 # bf16 storage of the two structured decompositions (DESIGN.md 4.6): storage twins of _BlockMP / _DiagMP.  X and the upstream gradient
@@ -931,7 +937,7 @@ class _BasisMP(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dX = _native.basis_aggregate(d_ag, comps, ctx.graph.csr("bwd"), B, d_in, B)
         if ctx.needs_input_grad[2]:
-            if getattr(ctx.graph, "per_call", False) and not deterministic() and _native.basis_dcomps_csr_ok(comps.shape[0], B, d_in):
+            if ctx.graph.per_call and not deterministic() and _native.basis_dcomps_csr_ok(comps.shape[0], B, d_in):
                 # per-step (LP) graphs: on the CSR the forward walked -- building a relation-major plan for this one kernel costs a dozen launches
                 dC = _native.basis_dcomps_csr(X, d_ag, ctx.graph.csr("fwd"), comps.shape[0], B, d_in)
             else:
@@ -1117,9 +1123,7 @@ def basis_mp(features, bases, comps, bias, graph):
 
 def use_basis_path(num_bases, d_in, d_out, graph):
     """aggregate-then-contract pays when the per-message d_in x d_out product is large and B is small"""
-    if routes.get("basis_path") == "0" or getattr(graph, "_dev", None) is None:
-        return False
-    return d_in * d_out >= 64 * 64 and num_bases <= 8
+    return graph._dev is not None and d_in * d_out >= 64 * 64 and num_bases <= 8
 
 
 def relational_mp(features, weights, bias, graph, relu=False, blocks=None):

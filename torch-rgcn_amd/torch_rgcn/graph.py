@@ -11,14 +11,10 @@ Three plans, all produced by the same host routine (csrc/rgcn_host.cpp):
   bwd    destination = object  o, tiles over o      -> dX  = sum val G[s] W_p^T
   wgt    one tile (relation-major)                  -> dW_p = sum val X[o]^T G[s]
 """
-import os
-
 import numpy as np
 import torch
 
-from . import routes
-
-from . import _native
+from . import _native, routes
 
 _LDS_WAVE_FLOATS = 2048  # 8 KiB of LDS per wave-owned destination tile (4 waves per workgroup)
 
@@ -59,6 +55,8 @@ class RelGraph:
         self._plans = {}
         self.perm = self.inv = None   # locality relabelling of the nodes (graph_from_nc_triples(relabel=...)): perm[old] = new, inv[new] = old
         self.sync_free = False      # True: plans are sized by upper bounds and finished on the device (no host read-back)
+        self.per_call = False       # True: the graph of ONE step (graph_from_lp_triples): plans finished on the device, no soft windows
+        self.owned_relations = None  # relation-sharded layers (dist.filter_graph_for_rank): the relations whose messages this rank kept
         if triples_plus is None:
             return
         tp = np.ascontiguousarray(triples_plus, dtype=np.int64).reshape(-1, 3)
@@ -91,7 +89,7 @@ class RelGraph:
             # plans of per-call (LP) graphs are always finished on the device: 4 read-backs per plan cost more than they buy on
             # graphs that live for one step (upper-bound sizes: at most 16 slots per message; one work unit per tile, no hub
             # splitting -- a sampled graph's hub is a few thousand messages).  Static (NC) graphs keep the exact path.
-            nosync = self.sync_free or getattr(self, "per_call", False)
+            nosync = self.sync_free or self.per_call
             self._plans[key] = _native.build_plan_device(dst, src, p, val, alive, N, N, R, tile_rows, self.num_messages,
                                                          max_item_chunks, want_runs=True, want_pack=True, sync_free=nosync,
                                                          **({"max_unit_chunks": 1 << 30} if whole else {}))
@@ -117,20 +115,19 @@ class RelGraph:
         if d_in == 16 and not routes.is_set("tile_rows"):
             # hidden 16: the fused backward kernels (dX + dW in one walk) keep a dX tile, an X tile, a transposition scratch and
             # the dW hand-over slots in LDS: 64-row tiles (measured in round 2: 0.71 ms at 64 rows, 0.80 at 128)
-            rows = int(routes.get("bwd_tile_rows")) if routes.is_set("bwd_tile_rows") else min(rows, 64)
+            rows = min(rows, 64)
         return self._plan("bwd", rows)
 
-    def bwd_blk_plan(self, diag4=False, sparse=False):
+    def bwd_blk_plan(self, diag4=False, sparse=False, rows=None):
         """transposed plan of TALL tiles (one per workgroup, up to 255 / 512 rows) for the block-tile backward kernel, or None
         when that kernel does not apply (small graph, too many relations, RGCN_DETERMINISTIC=1, RGCN_BWD_KERNEL != blk).
-        Only rgcn_bwd_blk_f32 can walk it -- every other kernel gets bwd_plan()."""
+        Only rgcn_bwd_blk_f32 can walk it -- every other kernel gets bwd_plan().  rows: _native.bwd_blk_rows' answer, where the caller has it
+        (diag4 and sparse, its arguments, are then not looked at)."""
         if routes.is_set("tile_rows"):
             return None
-        if routes.is_set("bwd_tile_rows") and _native.bwd_route() == "blk":
-            rows = int(routes.get("bwd_tile_rows"))         # experiments (tools/r3_blk.sh)
-            return self._plan("bwd", rows) if rows > 64 else None
-        rows = _native.bwd_blk_rows(self.num_nodes, self.num_rels, routes.get("deterministic", "0") == "1", self.device, diag4,
-                                    sparse)
+        if rows is None:
+            rows = _native.bwd_blk_rows(self.num_nodes, self.num_rels, routes.get("deterministic", "0") == "1", self.device, diag4,
+                                        sparse)
         return self._plan("bwd", rows) if rows else None
 
     def fwd_blk_plan(self):
@@ -151,7 +148,7 @@ class RelGraph:
         (tile, relation) bucket on average -- the span of a chunk's sources is 1 / that of the table -- and without forced tile heights,
         RGCN_SOFTWIN=0 or RGCN_DETERMINISTIC=1 (the tile is summed in arrival order)."""
         if routes.get("softwin", "auto") == "0" or routes.get("deterministic", "0") == "1" or routes.is_set("tile_rows") or \
-                self._dev is None or self.sync_free or getattr(self, "per_call", False):
+                self._dev is None or self.sync_free or self.per_call:
             return None
         if rows is None:
             rows = _native.bwd_own_rows(self.num_nodes, self.device) if kind == "bwd_own" else _native.spmm_blk_rows(self.num_nodes, self.device)
@@ -193,7 +190,7 @@ class RelGraph:
             if self._dev is None:
                 raise RuntimeError("the basis-aggregation path needs the device-side graph build")
             s, p, o, val, alive = self._dev
-            if getattr(self, "per_call", False) and not need_slot and ("csr", "fwd") not in self._plans \
+            if self.per_call and not need_slot and ("csr", "fwd") not in self._plans \
                     and ("csr", "bwd") not in self._plans:
                 # per-call graphs: both directions at once (a training step walks both), five launches for the pair
                 self._plans[("csr", "fwd")], self._plans[("csr", "bwd")] = \
@@ -201,8 +198,8 @@ class RelGraph:
                 return self._plans[key]
             dst, src = (s, o) if kind == "fwd" else (o, s)
             self._plans[key] = _native.build_csr_device(dst, src, p, val, alive, self.num_nodes, sync_free=self.sync_free,
-                                                        want_slot=need_slot or not getattr(self, "per_call", False))
-            self._plans[key].per_call = getattr(self, "per_call", False)
+                                                        want_slot=need_slot or not self.per_call)
+            self._plans[key].per_call = self.per_call
             self._plans[key].num_rels = self.num_rels
         return self._plans[key]
 

@@ -291,8 +291,7 @@ class RelationalGraphConvolutionNC(_RGCBase):
                 raise NotImplementedError("RGCN_RELABEL with a featureless layer (the R x N x d weight table is indexed by node id)")
             features = features.index_select(0, graph.inv)
 
-        fl_basis = (self.in_features is None and self.weight_decomp == 'basis' and not self.vertical_stacking and
-                    getattr(graph, "_dev", None) is not None and routes.get("basis_path") != "0")
+        fl_basis = self.in_features is None and self.weight_decomp == 'basis' and not self.vertical_stacking and graph._dev is not None
         # block-diagonal weights: the blocks are applied as they are (csrc/rgcn_block.hip); blocks above 8 x 8, or a host-built
         # graph, are expanded to dense R x d x d weights and multiplied per message by the relation-grouped gather-GEMM of
         # csrc/rgcn_gemm.hip (hand-written MFMA).  Round 1-2 had a third route for small graphs -- einsum('nbi,rbio->rnbo') on
@@ -401,7 +400,7 @@ class RelationalGraphConvolutionNC(_RGCBase):
 
     def _forward_featureless_bf16(self, activation, private):
         """featureless layer with basis decomposition and bf16 bases: the tile kernels on the bf16 table
-        (F_.featureless_basis_mp_bf16); relation-sharded layers, host-built graphs and basis_path=0 run the fp32 route on the widened
+        (F_.featureless_basis_mp_bf16); relation-sharded layers and host-built graphs run the fp32 route on the widened
         parameters and round the output once"""
         N, R, out_dim = self.num_nodes, self.num_relations, self.out_features
         _require_gpu(self.bases, "RelationalGraphConvolutionNC parameters")
@@ -414,7 +413,7 @@ class RelationalGraphConvolutionNC(_RGCBase):
                                f"(mat1 and mat2 shapes cannot be multiplied: {R * N}x{N} and {R * N}x{out_dim})")
         relu = activation == "relu"
         group = getattr(self, "_shard_group", None)
-        fl_basis = getattr(graph, "_dev", None) is not None and routes.get("basis_path") != "0"
+        fl_basis = graph._dev is not None
         if group is None and fl_basis:
             return F_.featureless_basis_mp_bf16(self.bases, self.comps, self.bias, graph, relu=relu)
         # upcast: the fp32 routes of _forward_impl on the widened parameters, one rounding at the end
