@@ -9,8 +9,9 @@
 // rows, and the block-tile kernel (rgcn_bwd_blk.hip) holds 218: its LDS keeps every relation's dW (R KiB) next to the X and dX tiles.
 // Here dW sits in REGISTERS.  Every relation -- every part of a large one -- belongs to one of the workgroup's NW waves (LPT over the
 // message counts, made with the plan); a wave walks only the chunks of its units and keeps their K accumulators (the MFMA's 16 x 16 D
-// fragment: 4 registers each) in a <32 x float> register vector indexed by the chunk's local number (wave-uniform: s_set_gpr_idx_on +
-// v_mov), the dW products accumulate in them directly.  No LDS table, no compare-and-swap adds, no dirty flags; the registers leave the
+// fragment: 4 registers each) as K separate register quads; wave-uniform tests of the chunk's local number pick the case whose four
+// MFMAs name that quad, so the dW products accumulate in place under compile-time register numbers (no s_set_gpr_idx_on / indexed
+// v_mov: -0.009 ms per launch at S1).  No LDS table, no compare-and-swap adds, no dirty flags; the registers leave the
 // CU once, at the end of the kernel (the same R KiB of global atomics per workgroup as the block-tile kernel's one flush).
 // LDS = the dX tile in doubles (128 bytes per row, ds_add_f64 as in the block-tile kernel) + the X tile (64 bytes per row: A operand of
 // the dW products, ReLU mask of the epilogue) + 1 KiB of transposition scratch per wave: tiles of up to 767 rows (S1: 652 rows, 1534
@@ -19,6 +20,7 @@
 // average): 12 waves x 9 units x 4 chunks (152 VGPRs, the first shipped form) 0.460 ms; 16 x 7 x 4 (128 VGPRs, 11 spilled) 0.454;
 // 16 x 8 x 3 0.437 -- the loads in flight per CU are the same 48 chunks, the fourth wave per SIMD hides the LDS and MFMA phases;
 // 16 x 8 x 2 **0.432**, 16 x 8 x 1 0.447 (fewer chunks in flight narrow the span of sources the chip reads at one time).
+// (Those forms kept the accumulators in one <32 x float> under a dynamic index; the ninth of the 12 x 9 form sat behind a select.)
 // Measured and dropped on the way (tools/r6_own_abl.sh, profiles/r06_own_ablation.txt): the X rows read from global memory instead of an
 // LDS tile (tiles of 977 rows fit then): 16 more loads per four chunks, +0.09 ms; accumulators updated by indexed adds: +0.03 ms.
 //
@@ -48,15 +50,23 @@ constexpr int OWN_K = RGCN_OWN_K;    // relations per wave (accumulators in regi
 constexpr int OWN_U = RGCN_OWN_U;    // chunks per loop trip
 constexpr int OWN_MAX_ROWS = (OWN_LDS_MAX - OWN_NW * BW_SCR2 * 4 - 64) / 192;      // 767: dX tile (doubles) + X tile + the waves' scratch
 
-// the first 8 accumulators of a wave: ONE register vector indexed by the chunk's local relation number (a <32 x float> is the largest
-// the compiler keeps in registers under a dynamic index: s_set_gpr_idx_on + v_mov; <36 x float> goes to scratch); the ninth is a
-// vector of its own, fed through a wave-uniform select
-typedef float own_acc32 __attribute__((ext_vector_type(32)));
+// One case of the accumulator selection: the chunk's four dW MFMAs on accumulator I, in place.  The cases are separate wave-uniform
+// ifs, not the arms of one switch: the compiler structurizes a multiway branch into a chain of merge blocks that copy every
+// accumulator of the other arms (v_mov blocks the size of the register vector); an if of its own names only its own four registers
+// and its merge moves nothing.  (The empty asm keeps the optimizer from threading the ifs back into one multiway branch.)  Measured and
+// not kept: the cases in groups of four behind a test of lr >> 2 (fewer branches per chunk, +0.002 ms per launch).
+#define OWN_DW_CASE(I)                                                                                             \
+  if constexpr (I < K) {                                                                                           \
+    if (lr == I) {                                                                                                 \
+      _Pragma("unroll") for (int t4 = 0; t4 < 4; ++t4)                                                             \
+        accw[I] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t4], b[t4], accw[I], 0, 0, 0);                            \
+    }                                                                                                              \
+    asm volatile("" : "+s"(lr));                                                                                   \
+  }
 
 size_t bwd_own_lds(int rows) { return (size_t)rows * 192 + (size_t)OWN_NW * BW_SCR2 * 4 + 64; }
 
-// Timing experiments (ablation library only, make abl; wrong results): ABL bits 2 no dW part, 4 the accumulator index is always 0,
-// 8 no dX tile update, 16 loads only
+// Timing experiments (ablation library only, make abl; wrong results): ABL bits 2 no dW part, 8 no dX tile update, 16 loads only
 // BF (rgcn_bwd_own_bf16): G, X and dX hold bf16 rows (32 bytes); G is gathered 8 bytes per lane (the record's byte offset
 // src << 6 halved) and widened, the X tile in LDS stays fp32, dX is rounded once on the way out; dW and the bias gradient stay fp32.
 // BF = false is the fp32 kernel as it was.
@@ -67,8 +77,7 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     float *__restrict__ dbias, int n_src, const int *__restrict__ unit_rel) {
   constexpr int U = OWN_U, NT = 64 * NW;
   constexpr int TQ = (OWN_MAX_ROWS * 4 + NT - 1) / NT;            // float4 of a tile a thread carries / converts per tile, at most
-  static_assert(K <= 9, "8 indexed accumulators + 1");
-  constexpr bool EXT = K == 9;
+  static_assert(K <= 9, "dw_add lists nine accumulator cases");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -114,10 +123,13 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
   const unsigned rows_lane = (unsigned)OWN_REC_ROWS + (unsigned)k * 8u;
   const unsigned w_lane = (unsigned)lane * 16u;
 
-  own_acc32 accs;
+  f32x4 accw[K];
 #pragma unroll
-  for (int i = 0; i < 32; ++i) accs[i] = 0.f;
-  f32x4 acc8 = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < K; ++i) accw[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // dW_unit += A^T B on the accumulator of local unit lr (wave-uniform, < K by the plan: own_relations gives a wave at most K units)
+  auto dw_add = [&](int lr, const float (&a)[4], const float (&b)[4]) {
+    OWN_DW_CASE(0) OWN_DW_CASE(1) OWN_DW_CASE(2) OWN_DW_CASE(3) OWN_DW_CASE(4) OWN_DW_CASE(5) OWN_DW_CASE(6) OWN_DW_CASE(7) OWN_DW_CASE(8)
+  };
 
   uint2 sl_n[U], rw_n[U];
   int hd_n[U];
@@ -212,22 +224,11 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
           for (int t4 = 0; t4 < 4; ++t4) av[jj][t4] = *reinterpret_cast<const float *>(lds + (xrd + ro[j][t4]));
           asm volatile("" ::: "memory");
         }
-        // (two chunks of one pair may share their relation: the second reads what the first wrote)
+        // (two chunks of one pair may share their unit: the second dw_add runs after the first and reads what it wrote)
 #pragma unroll
         for (int jj = 0; jj < P; ++jj) {
           if (h + jj >= U) break;
-          const int lr = (ABL & 4) ? 0 : (int)((unsigned)hd_[h + jj] >> 16);
-          const bool ext = EXT && lr >= 8;           // (wave-uniform selects, not multiplications by 0 / 1: an Inf stays in ITS relation)
-          const int li = 4 * (lr & 7);
-          const f32x4 in0 = f32x4{accs[li], accs[li + 1], accs[li + 2], accs[li + 3]};
-          f32x4 aw = EXT ? f32x4{ext ? acc8[0] : in0[0], ext ? acc8[1] : in0[1], ext ? acc8[2] : in0[2], ext ? acc8[3] : in0[3]} : in0;
-#pragma unroll
-          for (int t4 = 0; t4 < 4; ++t4) aw = __builtin_amdgcn_mfma_f32_16x16x4f32(av[jj][t4], bv[jj][t4], aw, 0, 0, 0);
-          accs[li] = ext ? in0[0] : aw[0];
-          accs[li + 1] = ext ? in0[1] : aw[1];
-          accs[li + 2] = ext ? in0[2] : aw[2];
-          accs[li + 3] = ext ? in0[3] : aw[3];
-          if (EXT) acc8 = f32x4{ext ? aw[0] : acc8[0], ext ? aw[1] : acc8[1], ext ? aw[2] : acc8[2], ext ? aw[3] : acc8[3]};
+          dw_add((int)((unsigned)hd_[h + jj] >> 16), av[jj], bv[jj]);
         }
       }
       // ---- phase 3: the tile update, one ds_add_f64 per slot quarter: the 16 lanes of a quarter wave add to the 16 features of one row
@@ -329,13 +330,15 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     const int r = __builtin_amdgcn_readfirstlane(unit_rel[wave * K + li]);
     if (r >= 0) {
       float *o = dWout + (size_t)r * 256 + (4 * k) * 16 + m;
-      atomicAdd(o, li < 8 ? accs[(4 * li) & 31] : acc8[0]);
-      atomicAdd(o + 16, li < 8 ? accs[(4 * li + 1) & 31] : acc8[1]);
-      atomicAdd(o + 32, li < 8 ? accs[(4 * li + 2) & 31] : acc8[2]);
-      atomicAdd(o + 48, li < 8 ? accs[(4 * li + 3) & 31] : acc8[3]);
+      atomicAdd(o, accw[li][0]);
+      atomicAdd(o + 16, accw[li][1]);
+      atomicAdd(o + 32, accw[li][2]);
+      atomicAdd(o + 48, accw[li][3]);
     }
   }
 }
+
+#undef OWN_DW_CASE
 
 }  // namespace
 
@@ -374,10 +377,8 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
   {
     const int ABLV = rgcn_option_value(RGCN_OPT_BWD_ABL);
     if (ABLV == 2) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 2>>));
-    else if (ABLV == 4) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 4>>));
     else if (ABLV == 8) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 8>>));
     else if (ABLV == 16) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 16>>));
-    else if (ABLV == 6) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 6>>));
     else HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0>>));
     return RGCN_OK;
   }
