@@ -830,6 +830,32 @@ RGCN_API int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int3
                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
                                            int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* Top-k link prediction: for each of the Q queries of `batch` the k entities that complete it best as its head (head != 0) or its tail,
+ * ids [Q, k] (int64) and scores [Q, k] (float) -- without a [Q, n_nodes] score buffer.  The scores are bit for bit the cells of
+ * rgcn_distmult_score_all_f32 / _bf16 (the same product and bias epilogue); the column of `batch` that is predicted is ignored.
+ * Order within a row: score descending, equal scores (==: +0 and -0 are one value, returned as +0) by ascending id -- one answer,
+ * whatever `strips` is.  filt_q / filt_n [F] (int32, device; F = 0 with NULL lists = no filter) exclude cells through the bit mask of
+ * the fused evaluator; prediction has no target, so EVERY listed cell is excluded (the ranking entries ignore an entry on the target).
+ * A score of -inf -- what an excluded cell holds on the materialised route -- is excluded as well.  With fewer than k candidates left
+ * (k > n_nodes, heavy filtering) the tail of a row is id -1, score -inf.  NaN scores are outside the contract.
+ * Passes on `stream`, no host synchronisation: the query pass; the strip pass = the grid of the fused evaluator's count pass (a
+ * workgroup owns 128 queries and one of `strips` runs of candidate tiles; strips = 0: the library's choice), each wave keeping k 64-bit
+ * keys (score image, ~id) and their minimum per query row in LDS, sized by k; the merge pass, one wave per query over the 2 strips lists.
+ * Limits: 1 <= k <= 32 (RGCN_EUNSUPPORTED with a message above: select from the materialised scores), n_nodes < 2^31
+ * (RGCN_EUNSUPPORTED), RGCN_EUNSUPPORTED beyond INT32_MAX workgroups or merge keys.  workspace:
+ * rgcn_distmult_topk_workspace_bytes(Q, n_nodes, d, k, strips, bf16) bytes (query vectors, 2 Q bias terms, 2 strips Q k keys, the
+ * mask; the same `strips` and k as the call; no device is asked; 0 for arguments the call refuses), 16-byte aligned.  RGCN_EINVAL for
+ * bad, NULL or misaligned arguments, k < 1, strips < 0 and biases partly set; Q == 0 launches nothing.  Filter entries and triples are
+ * NOT range-checked on the device (the Python wrapper checks). */
+RGCN_API int64_t rgcn_distmult_topk_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t k, int32_t strips, int32_t bf16);
+RGCN_API int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                    const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                    const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
+                                    float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                     const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                     const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
+                                     float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -500,13 +500,243 @@ __global__ __launch_bounds__(WG) void rank_count_fused_bf16_kernel(
   strip_store(g, e, q0, Q, partial + (size_t)(2 * strip + (wave & 1)) * Q);
 }
 
-// filter bits: mask[fq][fn / 32] |= 1 << (fn % 32).  Integer OR: duplicates are harmless.  An entry on a query's own target is dropped
-// (a caller error in both routes; the materialised route would rank that query against -inf)
+// ------------------------------------------------------------------ top-k prediction: the k best candidates per query
+// The product and epilogue of score_all again, with an epilogue that SELECTS.  Selection is integer max-selection on 64-bit keys:
+//   high word = the score's order-preserving unsigned image (-0 canonicalised to +0, then: negative -> all bits flipped, else sign set),
+//   low word  = ~id, so that among equal scores the lower id is the larger key.
+// Keys of one query are distinct (ids are) and never 0 (id < 2^31 sets the low word's top bit): 0 marks an empty slot, and "score
+// descending, id ascending" is "key descending" -- one answer whatever the strips, the tile a candidate sits in or the insertion order.
+// A filtered cell, a cell out of range and a score of -inf (what a filtered cell holds on the materialised route) produce no key.
+// NaN scores are outside the contract (a NaN lands wherever its bit pattern puts it).
+constexpr int TOPK_MAX = 32;
+
+__device__ __forceinline__ unsigned long long topk_key(float s, unsigned id) {
+  unsigned b = __float_as_uint(s);
+  b = b == 0x80000000u ? 0u : b;
+  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ((unsigned long long)b << 32) | (unsigned)~id;
+}
+
+// LDS words of a wave's lists: other lanes of the wave write them between one lane's reads, so every access is a relaxed atomic (a plain
+// load may be kept in a register across the insertion loop); the wave's LDS operations execute in program order
+__device__ __forceinline__ unsigned long long lds_ld64(const unsigned long long *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void lds_st64(unsigned long long *p, unsigned long long v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// 64-bit values over the 16 lanes of a DPP row (all of them active): after the four exchanges every lane holds the row's result
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+  const unsigned lo = (unsigned)dpp_i<CTRL>((int)(unsigned)v, (int)(unsigned)v);
+  const unsigned hi = (unsigned)dpp_i<CTRL>((int)(unsigned)(v >> 32), (int)(unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long row16_max(unsigned long long v) {
+  unsigned long long o;
+  o = dpp_u64<0xB1>(v); v = o > v ? o : v;         // quad_perm [1,0,3,2]
+  o = dpp_u64<0x4E>(v); v = o > v ? o : v;         // quad_perm [2,3,0,1]
+  o = dpp_u64<0x141>(v); v = o > v ? o : v;        // row_half_mirror
+  o = dpp_u64<0x140>(v); v = o > v ? o : v;        // row_mirror
+  return v;
+}
+__device__ __forceinline__ unsigned long long row16_min(unsigned long long v) {
+  unsigned long long o;
+  o = dpp_u64<0xB1>(v); v = o < v ? o : v;
+  o = dpp_u64<0x4E>(v); v = o < v ? o : v;
+  o = dpp_u64<0x141>(v); v = o < v ? o : v;
+  o = dpp_u64<0x140>(v); v = o < v ? o : v;
+  return v;
+}
+__device__ __forceinline__ int row16_min_i(int v) {
+  v = min(v, dpp_i<0xB1>(v, v));
+  v = min(v, dpp_i<0x4E>(v, v));
+  v = min(v, dpp_i<0x141>(v, v));
+  v = min(v, dpp_i<0x140>(v, v));
+  return v;
+}
+
+// One query row of a tile: the 16 lanes that share it (one DPP row, all of them active) hold up to four keys each that beat the row's
+// threshold `thr` = the smallest of the row's k kept keys (an empty slot is 0, the smallest; 0 = no key).  They are inserted one per turn,
+// the row's LARGEST pending key first -- the threshold rises as fast as it can, and after k turns at most nothing is left that beats it.
+// A turn is cooperative: lane i holds slots i and i + 16 of the list, the first slot equal to thr is replaced, and the new threshold is
+// the minimum over the lanes' slots -- no lane walks the list.  The four rows of a wave instruction take their turns side by side, every
+// step is predicated (no DPP under a branch), and the loop ends when no row of the wave has a key left.
+__device__ __forceinline__ void topk_insert(unsigned long long (&pend)[4], unsigned long long *list, unsigned long long *thr_p, int k,
+                                            unsigned long long thr) {
+  const int i = threadIdx.x & 15;
+  for (;;) {
+    unsigned long long m = pend[0] > pend[1] ? pend[0] : pend[1];
+    const unsigned long long m2 = pend[2] > pend[3] ? pend[2] : pend[3];
+    m = m > m2 ? m : m2;
+    m = m > thr ? m : 0ull;
+    if (!__builtin_amdgcn_ballot_w64(m != 0ull)) break;
+    const unsigned long long gm = row16_max(m);
+    const bool go = gm != 0ull;                                  // the same for the 16 lanes of the row
+    unsigned long long e0 = i < k ? lds_ld64(list + i) : ~0ull;
+    unsigned long long e1 = i + 16 < k ? lds_ld64(list + (i + 16)) : ~0ull;
+    const int at = row16_min_i(e0 == thr ? i : (e1 == thr ? i + 16 : 64));
+    if (go && at == i) { e0 = gm; lds_st64(list + i, gm); }
+    if (go && at == i + 16) { e1 = gm; lds_st64(list + (i + 16), gm); }
+    const unsigned long long low = row16_min(e0 < e1 ? e0 : e1);
+    thr = go ? low : thr;
+    if (go && i == 0) lds_st64(thr_p, thr);
+    pend[0] = pend[0] == gm ? 0ull : pend[0];
+    pend[1] = pend[1] == gm ? 0ull : pend[1];
+    pend[2] = pend[2] == gm ? 0ull : pend[2];
+    pend[3] = pend[3] == gm ? 0ull : pend[3];
+  }
+}
+
+// The selecting epilogue of one tile: tile_epilogue over the wave's whole 64 x 64 block (n_cols = c0 + 64, so that no lane leaves the
+// cell loop and the 16 lanes of a row stay together; a column past N is clamped for its bias and produces no key).  Thresholds, lists and
+// mask words are read again for every tile: nothing of a row lives in registers across the product loop.
+struct TopkRow { unsigned long long thr; unsigned w[2]; int lr; };
+
+__device__ __forceinline__ void tile_select(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long N, const float *__restrict__ qb,
+                                            const float *__restrict__ cbias, int head, const unsigned *__restrict__ mask, long long mask_w,
+                                            unsigned long long *lists, unsigned long long *thr, int k) {
+  const int i = threadIdx.x & 15;
+  unsigned long long pend[4] = {0ull, 0ull, 0ull, 0ull};
+  tile_epilogue(acc, q0, c0, Q, c0 + 64, qb, head,
+                [&](int, int qrow) {
+                  TopkRow st{0ull, {0u, 0u}, qrow - q0};
+                  st.thr = lds_ld64(thr + st.lr);
+                  if (mask) {
+                    const long long w0 = c0 >> 5;
+                    const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                    if (w0 < mask_w) st.w[0] = mrow[w0];                  // (the right half of a ragged last tile may start past N)
+                    if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  }
+                  return st;
+                },
+                [&](long long col) { return cbias[col < N ? col : N - 1]; },
+                [&](const TopkRow &st, int, int b, long long col, float sc_) {
+                  const bool out = col >= N || ((st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u) || sc_ == -INFINITY;
+                  const unsigned long long key = topk_key(sc_, (unsigned)col);
+                  pend[b] = (!out && key > st.thr) ? key : 0ull;
+                  if (b == 3) topk_insert(pend, lists + (size_t)st.lr * k, thr + st.lr, k, st.thr);
+                });
+}
+
+// dynamic LDS of the strip kernels: [4 waves][64 rows][k] keys, then [4][64] thresholds
+__device__ __forceinline__ void topk_lds(unsigned long long *dyn, int k, unsigned long long *&lists, unsigned long long *&thr) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  lists = dyn + (size_t)wave * 64 * k;
+  thr = dyn + (size_t)4 * 64 * k + wave * 64;
+  for (int e = lane; e < 64 * k; e += 64) lds_st64(lists + e, 0ull);
+  lds_st64(thr + lane, 0ull);
+}
+
+// a wave's lists -> partial[2 strip + candidate half of the wave][q][k]; empty slots go out as key 0
+__device__ __forceinline__ void topk_store(const unsigned long long *lists, int q0, int Q, int k, unsigned long long *__restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int n = min(64, Q - q0) * k;
+  for (int e = lane; e < n; e += 64) part[(size_t)q0 * k + e] = lds_ld64(lists + e);
+}
+
+// Strip pass: the grid and ownership of rank_count_fused_kernel -- a workgroup owns one block of 128 queries and a strip of candidate
+// tiles, a wave 64 rows x its 64-column half of every tile -- and the tile product of score_all_lds_kernel, so the scores are its bits.
+template <bool VEC>
+__global__ __launch_bounds__(WG) void topk_strip_kernel(
+    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
+    const unsigned *__restrict__ mask, long long mask_w, unsigned long long *__restrict__ partial,
+    int Q, long long N, int d, int head, int q_blocks, int strips, int k) {
+  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
+  extern __shared__ __attribute__((aligned(16))) unsigned long long topk_dyn[];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
+  const long long n_tiles = (N + 127) / 128;
+  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
+  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
+  unsigned long long *lists, *thr;
+  topk_lds(topk_dyn, k, lists, thr);
+  const float *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
+  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
+    const long long ct = tile * 128;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+    f32x4 acc[4][4];
+    tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
+    int q0t = q0;                     // as in rank_count_fused_kernel: the rows' addresses are formed again for every tile
+    asm volatile("" : "+v"(q0t));
+    tile_select(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
+  }
+  if (q0 < Q) topk_store(lists, q0, Q, k, partial + (size_t)(2 * strip + (wave & 1)) * Q * k);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void topk_strip_bf16_kernel(
+    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
+    const unsigned *__restrict__ mask, long long mask_w, unsigned long long *__restrict__ partial,
+    int Q, long long N, int d, int dpad, int head, int q_blocks, int strips, int k) {
+  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
+  extern __shared__ __attribute__((aligned(16))) unsigned long long topk_dyn[];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
+  const long long n_tiles = (N + 127) / 128;
+  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
+  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
+  unsigned long long *lists, *thr;
+  topk_lds(topk_dyn, k, lists, thr);
+  const uint16_t *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
+  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
+    const long long ct = tile * 128;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+    f32x4 acc[4][4];
+    tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
+    int q0t = q0;
+    asm volatile("" : "+v"(q0t));
+    tile_select(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
+  }
+  if (q0 < Q) topk_store(lists, q0, Q, k, partial + (size_t)(2 * strip + (wave & 1)) * Q * k);
+}
+
+// Merge pass, one wave per query: of the n_part lists of k keys the k largest, in k rounds -- round j takes the largest key below the
+// one round j - 1 took (keys of a query are distinct).  Integers only: any order of the lists gives the same answer.  Key 0 = no
+// candidate left: id -1, score -inf.
+__global__ __launch_bounds__(WG) void topk_merge_kernel(const unsigned long long *__restrict__ partial, int n_part, int Q, int k,
+                                                        long long *__restrict__ ids, float *__restrict__ scores) {
+  const int q = blockIdx.x * (WG / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (q >= Q) return;
+  const int m = n_part * k;
+  unsigned long long prev = ~0ull;
+  for (int j = 0; j < k; ++j) {
+    unsigned long long best = 0ull;
+    for (int e = lane; e < m; e += 64) {
+      const int p = e / k;
+      const unsigned long long v = partial[((size_t)p * Q + q) * k + (e - p * k)];
+      best = (v < prev && v > best) ? v : best;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long o = __shfl_xor(best, off);
+      best = o > best ? o : best;
+    }
+    if (lane == 0) {
+      const unsigned hi = (unsigned)(best >> 32);
+      const unsigned bits = (hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi;
+      ids[(size_t)q * k + j] = best ? (long long)(unsigned)~(unsigned)best : -1ll;
+      scores[(size_t)q * k + j] = best ? __uint_as_float(bits) : -INFINITY;
+    }
+    prev = best;
+  }
+}
+
+// filter bits: mask[fq][fn / 32] |= 1 << (fn % 32).  Integer OR: duplicates are harmless.  Ranking (keep_target = 0): an entry on a
+// query's own target is dropped (a caller error in both routes; the materialised route would rank that query against -inf).  Prediction
+// (keep_target != 0) has no target: every listed cell is set.
 __global__ void rank_mask_kernel(unsigned *__restrict__ mask, long long mask_w, const int *__restrict__ fq, const int *__restrict__ fn,
-                                 long long F, const long long *__restrict__ batch, int head) {
+                                 long long F, const long long *__restrict__ batch, int head, int keep_target) {
   for (long long e = (long long)blockIdx.x * WG + threadIdx.x; e < F; e += (long long)gridDim.x * WG) {
     const int q = fq[e], n = fn[e];
-    if (n != rank_target(batch, q, head)) atomicOr(mask + (size_t)q * mask_w + (n >> 5), 1u << (n & 31));
+    if (keep_target || n != rank_target(batch, q, head)) atomicOr(mask + (size_t)q * mask_w + (n >> 5), 1u << (n & 31));
   }
 }
 
@@ -727,7 +957,7 @@ int rank_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, 
   if (F) {
     HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
     hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
-                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head);
+                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, 0);
   }
   const dim3 gq((unsigned)((Q + 3) / 4)), gt((unsigned)qbl), gc((unsigned)(n_strips * qbl));
   if constexpr (BF16) {
@@ -783,4 +1013,130 @@ extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, in
   (void)n_rel;
   return rank_fused<true>("distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
                           greater, ties, tscore, n_nodes, d, stream);
+}
+
+// ------------------------------------------------------------------ top-k prediction: entry points
+namespace {
+
+constexpr int TOPK_LDS_CU = 160 * 1024;        // LDS of a compute unit: the static operand slabs and the lists share it
+
+struct TopkLayout { int64_t qv, qb, part, mask, total, mask_w; };
+
+// FusedLayout with k keys of 8 bytes per (strip half, query) in place of the (greater, equal) pair; the same `cells` bound
+inline TopkLayout topk_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t k, int64_t strips, bool bf16) {
+  TopkLayout L;
+  L.mask_w = (n_nodes + 31) / 32;
+  const int64_t n_tiles = (n_nodes + 127) / 128;
+  const int64_t cells = strips > 0 ? strips * Q : std::min(n_tiles * Q, 2 * FUSED_CU_CAP * 128 + Q);
+  L.qv = 0;
+  L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
+  L.part = L.qb + align16(2 * Q * (int64_t)sizeof(float));
+  L.mask = L.part + align16(2 * cells * k * (int64_t)sizeof(unsigned long long));
+  L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
+  return L;
+}
+
+template <bool BF16, class T>
+int topk_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, const T *nodes, const float *rel, const float *sbias,
+               const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F, int32_t k, int32_t strips,
+               void *workspace, int64_t *ids, float *scores, int64_t n_nodes, int32_t d, void *stream) {
+  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || F < 0 || k < 1 || strips < 0 || (F && (!filt_q || !filt_n)) ||
+      (Q && (!batch || !nodes || !rel || !workspace || !ids || !scores)) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+    rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; k >= 1; strips >= 0; F > 0 needs both filter lists)", name);
+    return RGCN_EINVAL;
+  }
+  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) {
+    rgcn_set_error("%s: biases must be all set or all NULL", name);
+    return RGCN_EINVAL;
+  }
+  if (k > TOPK_MAX) {
+    rgcn_set_error("%s: k = %d is above the native limit of %d; select from the materialised scores instead", name, (int)k, TOPK_MAX);
+    return RGCN_EUNSUPPORTED;
+  }
+  if (n_nodes > INT32_MAX) {
+    rgcn_set_error("%s: entity ids must fit 31 bits", name);
+    return RGCN_EUNSUPPORTED;
+  }
+  if (Q == 0) return RGCN_OK;
+  int dev = 0, n_cu = 0;
+  HIP_TRY(launch_device(&dev, &n_cu));
+  const int64_t qbl = (Q + 127) / 128;
+  const int64_t n_strips = strips > 0 ? strips : fused_default_strips(Q, n_nodes, n_cu);
+  if (n_strips * qbl > INT32_MAX || 2 * n_strips * k > INT32_MAX) {
+    rgcn_set_error("%s: too many strips in one call; split the batch", name);
+    return RGCN_EUNSUPPORTED;
+  }
+  const TopkLayout L = topk_layout(Q, n_nodes, d, k, strips, BF16);
+  char *ws = static_cast<char *>(workspace);
+  float *qb = reinterpret_cast<float *>(ws + L.qb);
+  unsigned long long *part = reinterpret_cast<unsigned long long *>(ws + L.part);
+  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const long long *b = reinterpret_cast<const long long *>(batch);
+  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
+  if (F) {
+    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
+    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
+                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, 1);
+  }
+  const dim3 gq((unsigned)((Q + 3) / 4)), gc((unsigned)(n_strips * qbl));
+  const size_t lds = (size_t)4 * 64 * (k + 1) * sizeof(unsigned long long);       // the lists and thresholds, sized by this call's k
+  // the slabs are static LDS: the lists may take what they leave of the compute unit
+  constexpr size_t slabs = BF16 ? sizeof(uint16_t) * (2 * 3 * SLAB + 2 * SLAB) : sizeof(float) * (4 * 128 * LDS_LD);
+  auto strip_pass = [&](auto kc, auto... args) -> hipError_t {
+    constexpr auto kern = decltype(kc)::value;
+    hipError_t e = allow_lds<kern>(dev, slabs + lds, (int)(TOPK_LDS_CU - slabs));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, gc, dim3(WG), lds, st, args...);
+    return hipSuccess;
+  };
+  if constexpr (BF16) {
+    uint16_t *qs = reinterpret_cast<uint16_t *>(ws + L.qv);
+    const int dpad = (int)k_pad32(d);
+    hipLaunchKernelGGL(rank_query_bf16_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qs, qb, d, dpad);
+    // 16-byte loads of the entity rows as in rgcn_distmult_score_all_bf16: the same instantiation, the same bits
+    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(nodes) & 15) == 0)
+      HIP_TRY(strip_pass(kern_c<topk_strip_bf16_kernel<true>>, (const uint16_t *)qs, qb1, nodes, cb1, (const unsigned *)mask,
+                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips, (int)k));
+    else
+      HIP_TRY(strip_pass(kern_c<topk_strip_bf16_kernel<false>>, (const uint16_t *)qs, qb1, nodes, cb1, (const unsigned *)mask,
+                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips, (int)k));
+  } else {
+    float *qvec = reinterpret_cast<float *>(ws + L.qv);
+    hipLaunchKernelGGL(rank_query_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qvec, qb, d);
+    if (d % 4 == 0)
+      HIP_TRY(strip_pass(kern_c<topk_strip_kernel<true>>, (const float *)qvec, qb1, nodes, cb1, (const unsigned *)mask,
+                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips, (int)k));
+    else
+      HIP_TRY(strip_pass(kern_c<topk_strip_kernel<false>>, (const float *)qvec, qb1, nodes, cb1, (const unsigned *)mask,
+                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips, (int)k));
+  }
+  hipLaunchKernelGGL(topk_merge_kernel, gq, dim3(WG), 0, st, (const unsigned long long *)part, (int)(2 * n_strips), (int)Q, (int)k,
+                     reinterpret_cast<long long *>(ids), scores);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rgcn_distmult_topk_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t k, int32_t strips, int32_t bf16) {
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || k < 1 || k > TOPK_MAX || strips < 0) ? 0 : topk_layout(Q, n_nodes, d, k, strips, bf16 != 0).total;
+}
+
+extern "C" int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                      const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
+                                      float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return topk_fused<false>("distmult_topk", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, k, strips, workspace, ids,
+                           scores, n_nodes, d, stream);
+}
+
+extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                       const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                       const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
+                                       float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return topk_fused<true>("distmult_topk_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, k, strips, workspace, ids,
+                          scores, n_nodes, d, stream);
 }

@@ -2304,3 +2304,60 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
                                                       _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, rel.shape[0], d,
                                                       _stream(dev)), "distmult_rank_fused")
     return greater, ties, tscore
+
+
+TOPK_MAX = 32       # the native limit of k (rgcn_distmult_topk_*: the lists of k keys per query row live in LDS)
+
+
+def topk_workspace_bytes(Q, N, d, k, strips=0, bf16=False):
+    """bytes of the top-k route's workspace (query vectors, 2 strips Q k keys, the [Q][ceil(N / 32)] filter mask); needs no device; 0 for
+    arguments the call refuses (k outside 1..TOPK_MAX among them)"""
+    return int(lib().rgcn_distmult_topk_workspace_bytes(Q, N, d, k, strips, 1 if bf16 else 0))
+
+
+def distmult_topk(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k=10, filt_q=None, filt_n=None, strips=0):
+    """(ids int64 [Q, k], scores fp32 [Q, k]): the k entities that complete each query of `batch` (int64 [Q, 3], device; the predicted
+    column is ignored) best as its head (head=True) or tail, without the [Q, N] score matrix.  Scores are the cells of
+    distmult_score_all[_bf16], bit for bit; rows are ordered by score descending, equal scores by ascending id; every cell on the int32
+    device lists (filt_q, filt_n) is excluded; rows with fewer than k candidates end in id -1, score -inf.  fp32 or bf16 nodes (rel and
+    biases fp32).  1 <= k <= TOPK_MAX (the library refuses a larger k).  strips: as in distmult_rank_fused.  NaN scores are outside the
+    contract."""
+    bf16 = nodes.dtype == torch.bfloat16
+    if bf16:
+        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
+    else:
+        _req(nodes, "nodes"); _req(rel, "relations")
+        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
+            _req(b, n)
+    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
+    Q, (N, d) = batch.shape[0], nodes.shape
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    assert rel.shape[1] == d, "relation and node embeddings differ in width"
+    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
+        "filt_q and filt_n: two int32 lists of one length, or neither"
+    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
+    assert isinstance(k, int) and k >= 1, "k must be a positive int"
+    F = 0 if filt_q is None else filt_q.shape[0]
+    if Q:
+        lo, hi = batch.amin(0), batch.amax(0)
+        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
+            if bf16:
+                raise IndexError("triple index out of range")
+            raise AssertionError("triple index out of range")
+    if F:       # an entry out of range would set a bit outside the mask
+        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
+            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    dev = nodes.device
+    ids = torch.empty(Q, k, device=dev, dtype=torch.int64)
+    scores = torch.empty(Q, k, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    with _on(dev), _timed("topk_fused_bf16" if bf16 else "topk_fused"):
+        if bf16:
+            _check(lib().rgcn_distmult_topk_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                 _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, k, strips,
+                                                 _dp(ws), _dp(ids), _dp(scores), N, rel.shape[0], d, _stream(dev)), "distmult_topk_bf16")
+        else:
+            _check(lib().rgcn_distmult_topk_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, k, strips,
+                                                _dp(ws), _dp(ids), _dp(scores), N, rel.shape[0], d, _stream(dev)), "distmult_topk")
+    return ids, scores

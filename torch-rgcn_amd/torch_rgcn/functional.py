@@ -1263,6 +1263,21 @@ def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obi
     return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips)
 
 
+def distmult_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt_q=None, filt_n=None, strips=0):
+    """(ids int64 [Q, k], scores fp32 [Q, k]): for each triple of `batch` the k entities that score best as its head (head=True) or its
+    tail -- the rows of distmult_score_all after `_native.rank_filter` on the int32 device lists (filt_q, filt_n), sorted by score
+    descending and id ascending and cut at k, without that matrix.  The predicted column of `batch` is ignored and every
+    listed cell is excluded; rows with fewer than k candidates end in id -1, score -inf.  No autograd.  k <= _native.TOPK_MAX.  fp32 or
+    bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16 (widened here), as in distmult_rank_all."""
+    if nodes.dtype == torch.bfloat16:
+        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+        widen = lambda t: None if t is None else t.float()     # noqa: E731
+        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+    return _native.distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips)
+
+
 _UNIT = {}
 
 

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from torch_rgcn import _native
-from torch_rgcn.functional import distmult_rank_all, distmult_score_all
+from torch_rgcn.functional import distmult_rank_all, distmult_score_all, distmult_topk_all
 from torch_rgcn.layers import DistMult
 
 _SCORE_BYTES = 1 << 30     # score-matrix budget per chunk of queries
@@ -66,8 +66,9 @@ class _FilterIndex:
             gather = np.repeat(starts - ptr[:-1], lens[order]) + np.arange(int(lens.sum()))
             self.tables.append((keys[order], ptr, vals[gather]))
 
-    def lists(self, batch, head):
-        """-> (rows, cols) int32 arrays: for query i every known completion except its own target"""
+    def lists(self, batch, head, keep_target=False):
+        """-> (rows, cols) int32 arrays: for query i every known completion except its own target; keep_target=True (prediction: the
+        query has no target) keeps that one too"""
         b = np.asarray(batch, np.int64)
         keys, ptr, vals = self.tables[0 if head else 1]
         q = b[:, 1] * self.n + (b[:, 2] if head else b[:, 0])
@@ -78,6 +79,8 @@ class _FilterIndex:
         cnt = np.where(hit, ptr[pos_c + 1] - ptr[pos_c], 0) if len(keys) else np.zeros(len(q), np.int64)
         rows = np.repeat(np.arange(len(q)), cnt)
         cols = vals[np.repeat(lo - np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt) + np.arange(int(cnt.sum()))]
+        if keep_target:
+            return rows.astype(np.int32), cols.astype(np.int32)
         keep = cols != (b[:, 0] if head else b[:, 2])[rows]
         return rows[keep].astype(np.int32), cols[keep].astype(np.int32)
 
@@ -177,6 +180,75 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
     mrr = sum(1.0 / r for r in ranks) / len(ranks)
     hits = tuple(sum(1.0 if r <= k else 0.0 for r in ranks) / len(ranks) for k in hits_at_k)
     return mrr, hits, ranks
+
+
+def _topk_batch(num_queries, num_nodes, dim, k):
+    """queries per launch of the top-k route: _fused_batch with the strips' lists counted -- 2 strips k keys of 8 bytes per query, and
+    strips * queries is at most 128 K + queries (the workspace bound of strips = 0)"""
+    per_query = 4 * ((num_nodes + 31) // 32) + 6 * (dim + 31) + 64 + 16 * k
+    return min(num_queries, max(64, (_FUSED_BYTES - 16 * k * (128 << 10)) // per_query))
+
+
+def _topk_of_scores(scores, k):
+    """(ids, scores) [Q, k] of a score matrix [Q, N] whose excluded cells hold -inf: score descending, equal scores (+0 == -0) by
+    ascending id -- a stable descending sort keeps equal scores in column order --, cells of -inf dropped, rows padded with -1 / -inf"""
+    n = scores.shape[1]
+    s, idx = torch.sort(scores + 0.0, dim=1, descending=True, stable=True)        # (+ 0.0: -0 becomes +0, one value for any sort)
+    s, idx = s[:, :k], idx[:, :k]
+    idx = torch.where(s == float("-inf"), torch.full_like(idx, -1), idx)
+    if k > n:
+        idx = torch.cat([idx, idx.new_full((idx.shape[0], k - n), -1)], 1)
+        s = torch.cat([s, s.new_full((s.shape[0], k - n), float("-inf"))], 1)
+    return idx.contiguous(), s.contiguous()
+
+
+@torch.no_grad()
+def predict(model, graph, queries, num_nodes, k=10, head=False, true_triples=None, fused=None):
+    """(ids int64 [Q, k], scores fp32 [Q, k]) on the model's device: for each query (s, p, o) of `queries` the k entities that complete
+    it best as the head of (?, p, o) (head=True) or the tail of (s, p, ?) -- the predicted column of `queries` is ignored.  Rows are
+    ordered by score descending, equal scores by ascending id.  `true_triples` (the pair generate_true_dict returns): every known
+    completion of a query is excluded from its row.  Rows with fewer than k candidates end in id -1, score -inf.
+
+    The graph is encoded once.  fused=None takes the product kernel's selecting epilogue (`functional.distmult_topk_all`; DESIGN.md 4.5:
+    no score matrix) whenever k <= _native.TOPK_MAX; fused=False, or a larger k, sorts chunks of the materialised scores -- the same
+    answer.  An extension: the reference has no counterpart."""
+    decoder = getattr(model, "scoring_function", None)
+    if not (hasattr(model, "encode") and isinstance(decoder, DistMult)):
+        raise TypeError("predict needs a model with an `encode` method and a DistMult `scoring_function`")
+    if not (isinstance(k, int) and k >= 1):
+        raise ValueError("k must be a positive int")
+    device = next(model.parameters()).device
+    queries = torch.as_tensor(queries, dtype=torch.long).reshape(-1, 3)
+    x = model.encode(graph).contiguous()
+    assert x.shape[0] == num_nodes, "num_nodes differs from the encoder output"
+    params = (decoder.relations.detach(), *((decoder.sbias.detach(), decoder.pbias.detach(), decoder.obias.detach())
+                                            if decoder.b_init else ()))
+    fuse = k <= _native.TOPK_MAX and (fused is None or bool(fused))      # (a larger k takes the fallback whatever `fused` says)
+    if fuse:
+        batch_size = _topk_batch(len(queries), num_nodes, x.shape[1], k)
+    else:       # the scores, the sorted scores and their int64 columns
+        batch_size = min(len(queries), max(1, _SCORE_BYTES // (16 * num_nodes)))
+    ids, scores = [], []
+    for fr in range(0, len(queries), max(batch_size, 1)):
+        host = queries[fr:fr + batch_size]
+        batch = host.to(device).contiguous()
+        rows = cols = None
+        if true_triples is not None:
+            r, c = _filter_index(true_triples, num_nodes).lists(host.cpu().numpy(), head, keep_target=True)
+            if len(r):
+                rows, cols = torch.from_numpy(r).to(device), torch.from_numpy(c).to(device)
+        if fuse:
+            i, s = distmult_topk_all(batch, head, x, *params, k=k, filt_q=rows, filt_n=cols)
+        else:
+            sc = distmult_score_all(batch, head, x, *params)
+            if rows is not None:
+                _native.rank_filter(sc, rows, cols)
+            i, s = _topk_of_scores(sc, k)
+        ids.append(i)
+        scores.append(s)
+    if not ids:
+        return (torch.empty(0, k, dtype=torch.long, device=device), torch.empty(0, k, dtype=torch.float32, device=device))
+    return torch.cat(ids), torch.cat(scores)
 
 
 def select_sampling(method):
