@@ -8,7 +8,7 @@ one process, filtered, fp32 and bf16 entity tables, k in {1, 10, 32}.
 
 WN18 size (N = 40,943, d = 200, Q = 5,000), and a shape whose score matrix is 20 GB (N = 1,000,000, Q = 5,000), where only the two fused
 routes run.  The variants ALTERNATE launch by launch; HIP events; median, minimum and quartiles of --steps after --warmup.  No figure is a
-threshold.  The strip kernels' registers and occupancy are read from the compiler's resource-usage remarks (--remarks FILE: the output of
+threshold.  The registers and occupancy of the four kernel roles (every storage and load path) are read from the compiler's resource-usage remarks (--remarks FILE: the output of
 hipcc -Rpass-analysis=kernel-resource-usage on csrc/rgcn_rank.hip; without it the tool compiles the device code of that file once).
 
     python tools/topk_bench.py [--steps 20 --warmup 5 --out DIR --remarks FILE --skip-large]   -> DIR/topk_bench_<csrc_sha>.json (DIR: profiles/)
@@ -56,7 +56,8 @@ def alternate(variants, steps, warmup):
 
 
 def resource_usage(remarks):
-    """{kernel: {vgprs, agprs, occupancy_waves_per_simd, static_lds_bytes, scratch_bytes}} of the strip kernels, from the compiler's remarks"""
+    """{kernel: {vgprs, agprs, occupancy_waves_per_simd, static_lds_bytes, scratch_bytes}} of the four kernel roles of csrc/rgcn_rank.hip
+    (score-all, target score, strip count, strip select) in both storages and on both load paths, from the compiler's remarks"""
     if remarks is None:
         csrc = os.path.join(ROOT, "torch-rgcn_amd", "csrc")
         cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-mllvm",
@@ -71,11 +72,13 @@ def resource_usage(remarks):
     for line in text.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
+            # a mangled instantiation of a role: ...<role>_kernelINS_<Tile>ELb<VEC>EEE...
             name = m.group(1)
             cur = None
-            for kern in ("topk_strip_bf16_kernel", "topk_strip_kernel"):
-                if kern in name:
-                    cur = kern + ("<VEC>" if "ILb1E" in name else "<scalar loads>")
+            for kern in ("score_all_kernel", "target_score_kernel", "strip_count_kernel", "strip_select_kernel"):
+                tile = re.search(kern + r"I\w*?(TileF32|TileBf16)ELb([01])E", name)
+                if tile:
+                    cur = f"{kern}<{tile.group(1)}, {'VEC' if tile.group(2) == '1' else 'scalar loads'}>"
                     out[cur] = {}
                     break
             continue
@@ -137,8 +140,8 @@ def main():
         raise SystemExit("topk_bench: needs the GPU (no CPU fallback)")
     from torch_rgcn import _native
     out = {"tool": "tools/topk_bench.py", "csrc_sha": _native.csrc_sha(), "steps": args.steps, "warmup": args.warmup,
-           "device": torch.cuda.get_device_name(0), "strip_kernel_resources": resource_usage(args.remarks)}
-    print(json.dumps({"strip_kernel_resources": out["strip_kernel_resources"]}), flush=True)
+           "device": torch.cuda.get_device_name(0), "kernel_resources": resource_usage(args.remarks)}
+    print(json.dumps({"kernel_resources": out["kernel_resources"]}), flush=True)
     out["wn18"] = shape(args.steps, args.warmup, 40_943, 5_000, 200, True)
     print(json.dumps({"wn18": out["wn18"]}), flush=True)
     if not args.skip_large:

@@ -7,13 +7,15 @@
 // Here the [bn, N, 3] index tensor is never built.  For a batch of Q queries
 //     scores[q, n] = sum_k (nodes[fixed_q, k] * rel[p_q, k]) * nodes[n, k]  (+ biases)
 // is an NT product of the Q x d query vectors with the N x d entity table: fp32 MFMA (v_mfma_f32_16x16x4_f32,
-// exact fp32 products and accumulation).  Default kernel: 128 x 128 scores per workgroup, operand slabs staged through
-// double-buffered LDS (score_all_lds_kernel); the register-only variant (operands straight from L2, each lane's float4
-// feeding four MFMAs of each tile that shares it) is kept selectable for comparison (RGCN_RANK_TILE=44).
-// The K index is permuted -- lane group kq carries k = 16t + 4kq + c at MFMA c of step t -- which is legal
+// exact fp32 products and accumulation): 128 x 128 scores per workgroup, operand slabs staged through double-buffered LDS
+// (score_all_kernel).  The K index is permuted -- lane group kq carries k = 16t + 4kq + c at MFMA c of step t -- which is legal
 // because both operands use the same permutation and the sum over k does not care.
 // Second route (rgcn_distmult_rank_fused_*, utils/misc.py:40-58, 71-99): the same tile product with an epilogue that compares every score
-// with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.
+// with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.  Third (rgcn_distmult_topk_*):
+// an epilogue that selects the k best.
+// Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select) first; then a tile-precision trait
+// (TileF32 / TileBf16) and the four kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel --
+// each written once over <Tile, VEC>; then the entry points.
 #include <cmath>
 #include <cstdlib>
 
@@ -62,8 +64,8 @@ __device__ __forceinline__ f32x4 mask_k4(f32x4 v, int k, int d) {
 // operands.  The loads of step t+1 are issued before the 64 MFMAs of step t and land in LDS after them.
 constexpr int LDS_LD = 20;
 
-// The product loop of one 128 x 128 tile, shared by score_all_lds_kernel and the fused evaluator's target and count kernels
-// (rank_target_kernel, rank_count_fused_kernel): whoever instantiates it gets the same K permutation and the same MFMA chain per
+// The product loop of one 128 x 128 tile, shared by the four kernel roles (TileF32::product): whoever instantiates it gets the same
+// K permutation and the same MFMA chain per
 // accumulator, hence the same bits for the same pair of rows wherever the pair sits in a tile.  ga / gb: this thread's two staging rows
 // (tid >> 2 and + 64) of the query and the candidate slab.  Ends on a barrier: the LDS slabs may be refilled right away.
 template <bool VEC>
@@ -151,56 +153,8 @@ __device__ __forceinline__ void tile_epilogue(const f32x4 (&acc)[4][4], int q0, 
     }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(WG) void score_all_lds_kernel(
-    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes,
-    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int head, int q_blocks) {
-  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = (blockIdx.x % q_blocks) * 128;
-  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
-  const int sr = tid >> 2;
-  const float *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
-    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-  }
-  f32x4 acc[4][4];
-  tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
-  tile_epilogue(acc, qt + (wave >> 1) * 64, ct + (wave & 1) * 64, Q, N, qb, head,
-                [&](int, int qrow) { return scores + (size_t)qrow * N; },
-                [&](long long col) { return cbias[col]; },
-                [&](float *out, int, int, long long col, float sc_) { out[col] = sc_; });
-}
-
 // ------------------------------------------------------------------ fused evaluator: ranks without the score matrix
-// Pass 2: tscore[q] = the score of query q's own target, from the SAME product and epilogue as score_all -- one 128 x 128 tile per
-// block of 128 queries whose "candidate" row j is nodes[target of query qt + j]; the diagonal cells are kept.
 __device__ __forceinline__ long long rank_target(const long long *__restrict__ batch, int q, int head) { return batch[3 * q + (head ? 0 : 2)]; }
-
-template <bool VEC>
-__global__ __launch_bounds__(WG) void rank_target_kernel(
-    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
-    const long long *__restrict__ batch, float *__restrict__ tscore, int Q, int d, int head) {
-  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = blockIdx.x * 128;
-  const int sr = tid >> 2;
-  const float *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int q = min(qt + sr + 64 * h, Q - 1);
-    ga[h] = qvec + (size_t)q * d;
-    gb[h] = nodes + (size_t)rank_target(batch, q, head) * d;
-  }
-  f32x4 acc[4][4];
-  tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
-  tile_epilogue(acc, qt + (wave >> 1) * 64, (long long)qt + (wave & 1) * 64, Q, (long long)Q, qb, head,
-                [&](int, int qrow) { return qrow; },
-                [&](long long col) { return cbias[rank_target(batch, (int)col, head)]; },
-                [&](int qrow, int, int, long long col, float sc_) { if (col == qrow) tscore[qrow] = sc_; });
-}
 
 // Pass 3's epilogue: the cells of one tile compared with their query's target score instead of stored.  mask: the filter bits
 // [Q][mask_w] (NULL = raw ranks), one word per 32 candidates -- the lane's four columns c0 + 16 b + i (c0 a multiple of 64) sit in words
@@ -254,37 +208,6 @@ __device__ __forceinline__ void strip_store(int g, int e, int q0, int Q, uint2 *
   const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
   const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
   if (qrow < Q) part[qrow] = uint2{(unsigned)g, (unsigned)e};
-}
-
-// Pass 3: a workgroup owns one block of 128 queries and a strip of candidate tiles; counters stay in registers over the strip.
-template <bool VEC>
-__global__ __launch_bounds__(WG) void rank_count_fused_kernel(
-    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
-    const float *__restrict__ tscore, const unsigned *__restrict__ mask, long long mask_w, uint2 *__restrict__ partial,
-    int Q, long long N, int d, int head, int q_blocks, int strips) {
-  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
-  const long long n_tiles = (N + 127) / 128;
-  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
-  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
-  const float *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
-  int g = 0, e = 0;
-  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
-    const long long ct = tile * 128;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-    f32x4 acc[4][4];
-    tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
-    // the rows' target scores, bias terms and addresses are formed again for every tile: hoisted out of this loop they would sit in
-    // ~100 registers through the product, and the kernel would drop to one workgroup per compute unit
-    int q0t = q0;
-    asm volatile("" : "+v"(q0t));
-    tile_count(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, tscore, mask, mask_w, g, e);
-  }
-  strip_store(g, e, q0, Q, partial + (size_t)(2 * strip + (wave & 1)) * Q);
 }
 
 // ------------------------------------------------------------------ bf16 entity table
@@ -350,7 +273,7 @@ __device__ __forceinline__ u32x4 mask_k8(u32x4 v, int k, int d) {
   return v;
 }
 
-// The shape of score_all_lds_kernel: 128 queries x 128 candidates per workgroup, 64 x 64 per wave, double-buffered LDS slabs, the loads
+// The shape of the fp32 tile: 128 queries x 128 candidates per workgroup, 64 x 64 per wave, double-buffered LDS slabs, the loads
 // of step t + 1 issued before the MFMAs of step t.  A K step is 32: a slab row is 32 bf16 = 64 bytes = four 16-byte pieces, lane
 // 16 kq + i reads piece kq of row i (the operand map of v_mfma_f32_16x16x32_bf16: A[row l & 15][k = 8 (l >> 4) + j], B likewise by column)
 // and uses each of its four B fragments against the hi, mid and lo A fragments: 48 MFMAs per step and wave behind 16 ds_read_b128.
@@ -360,7 +283,7 @@ __device__ __forceinline__ u32x4 mask_k8(u32x4 v, int k, int d) {
 constexpr int SLAB = 128 * 32;          // bf16 elements of one 128-row slab
 __device__ __forceinline__ int slab_at(int row, int piece) { return row * 32 + 8 * (piece ^ ((row >> 2) & 2)); }
 
-// The bf16 product loop of one tile, shared by score_all_bf16_kernel, rank_target_bf16_kernel and rank_count_fused_bf16_kernel (as
+// The bf16 product loop of one tile, shared by the four kernel roles (TileBf16::product; as
 // tile_product_f32: same lo-mid-hi order and MFMA chain per accumulator for whoever instantiates it).  ga: this thread's two staging rows
 // of the hi term (mid and lo `term` elements further on), gb: of the candidate slab.  Ends on a barrier.
 template <bool VEC>
@@ -421,83 +344,6 @@ __device__ __forceinline__ void tile_product_bf16(const uint16_t *const (&ga)[2]
     if (t + 1 < steps) stash(cur ^ 1, t + 1);
     __syncthreads();
   }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(WG) void score_all_bf16_kernel(
-    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes,
-    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int d, int dpad, int head, int q_blocks) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = (blockIdx.x % q_blocks) * 128;
-  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
-  const int sr = tid >> 2;
-  const uint16_t *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
-    gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-  }
-  f32x4 acc[4][4];
-  tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
-  tile_epilogue(acc, qt + (wave >> 1) * 64, ct + (wave & 1) * 64, Q, N, qb, head,
-                [&](int, int qrow) { return scores + (size_t)qrow * N; },
-                [&](long long col) { return cbias[col]; },
-                [&](float *out, int, int, long long col, float sc_) { out[col] = sc_; });
-}
-
-// the fused evaluator's passes 2 and 3 on the bf16 table (see rank_target_kernel, rank_count_fused_kernel)
-template <bool VEC>
-__global__ __launch_bounds__(WG) void rank_target_bf16_kernel(
-    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
-    const long long *__restrict__ batch, float *__restrict__ tscore, int Q, int d, int dpad, int head) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = blockIdx.x * 128;
-  const int sr = tid >> 2;
-  const uint16_t *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int q = min(qt + sr + 64 * h, Q - 1);
-    ga[h] = qs + (size_t)q * dpad;
-    gb[h] = nodes + (size_t)rank_target(batch, q, head) * d;
-  }
-  f32x4 acc[4][4];
-  tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
-  tile_epilogue(acc, qt + (wave >> 1) * 64, (long long)qt + (wave & 1) * 64, Q, (long long)Q, qb, head,
-                [&](int, int qrow) { return qrow; },
-                [&](long long col) { return cbias[rank_target(batch, (int)col, head)]; },
-                [&](int qrow, int, int, long long col, float sc_) { if (col == qrow) tscore[qrow] = sc_; });
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(WG) void rank_count_fused_bf16_kernel(
-    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
-    const float *__restrict__ tscore, const unsigned *__restrict__ mask, long long mask_w, uint2 *__restrict__ partial,
-    int Q, long long N, int d, int dpad, int head, int q_blocks, int strips) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
-  const long long n_tiles = (N + 127) / 128;
-  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
-  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
-  const uint16_t *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
-  int g = 0, e = 0;
-  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
-    const long long ct = tile * 128;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-    f32x4 acc[4][4];
-    tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
-    // the rows' target scores, bias terms and addresses are formed again for every tile: hoisted out of this loop they would sit in
-    // ~100 registers through the product, and the kernel would drop to one workgroup per compute unit
-    int q0t = q0;
-    asm volatile("" : "+v"(q0t));
-    tile_count(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, tscore, mask, mask_w, g, e);
-  }
-  strip_store(g, e, q0, Q, partial + (size_t)(2 * strip + (wave & 1)) * Q);
 }
 
 // ------------------------------------------------------------------ top-k prediction: the k best candidates per query
@@ -636,66 +482,152 @@ __device__ __forceinline__ void topk_store(const unsigned long long *lists, int 
   for (int e = lane; e < n; e += 64) part[(size_t)q0 * k + e] = lds_ld64(lists + e);
 }
 
-// Strip pass: the grid and ownership of rank_count_fused_kernel -- a workgroup owns one block of 128 queries and a strip of candidate
-// tiles, a wave 64 rows x its 64-column half of every tile -- and the tile product of score_all_lds_kernel, so the scores are its bits.
-template <bool VEC>
-__global__ __launch_bounds__(WG) void topk_strip_kernel(
-    const float *__restrict__ qvec, const float *__restrict__ qb, const float *__restrict__ nodes, const float *__restrict__ cbias,
-    const unsigned *__restrict__ mask, long long mask_w, unsigned long long *__restrict__ partial,
-    int Q, long long N, int d, int head, int q_blocks, int strips, int k) {
-  __shared__ __attribute__((aligned(16))) float sA[2][128 * LDS_LD], sB[2][128 * LDS_LD];
-  extern __shared__ __attribute__((aligned(16))) unsigned long long topk_dyn[];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
-  const long long n_tiles = (N + 127) / 128;
-  const long long tile_end = strip_first(strip + 1, n_tiles, strips);
-  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
-  unsigned long long *lists, *thr;
-  topk_lds(topk_dyn, k, lists, thr);
-  const float *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) ga[h] = qvec + (size_t)min(qt + sr + 64 * h, Q - 1) * d;
-  for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
-    const long long ct = tile * 128;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
-    f32x4 acc[4][4];
-    tile_product_f32<VEC>(ga, gb, d, sA, sB, acc);
-    int q0t = q0;                     // as in rank_count_fused_kernel: the rows' addresses are formed again for every tile
-    asm volatile("" : "+v"(q0t));
-    tile_select(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
+// ------------------------------------------------------------------ the tile precision and the four kernel roles
+// What a kernel has to know about the storage of the entity table: the operand element type, the static LDS slabs of a workgroup, the
+// stride of the query rows and which product loop runs.  Every role below is written once over <Tile, VEC> (VEC: 16-byte loads of the
+// entity rows); the roles of one <Tile, VEC> share one product and tile_epilogue, hence the same bits for the same pair of rows.
+
+// The operand facts of one call, the same shape for both storages.  The two operand pointers (q: the query rows, nodes: the entity table
+// [N][d]) travel beside it as kernel parameters of their own: `__restrict__` does not hold on a struct member, and without it the strip
+// kernels come out of the compiler differently (12 registers apart).
+struct TileDims {
+  int d, dpad;                // row length; d rounded up to the bf16 K step of 32 (fp32 does not read it)
+  size_t term;                // bf16: Q * dpad, from a query row's hi term to its mid and from mid to lo (fp32 does not read it)
+};
+
+struct TileF32 {
+  using elem = float;         // queries: fp32 [Q][d]
+  struct Slabs { float a[2][128 * LDS_LD], b[2][128 * LDS_LD]; };             // 40,960 bytes
+  static __device__ __forceinline__ int q_stride(const TileDims &dm) { return dm.d; }
+  template <bool VEC>
+  static __device__ __forceinline__ void product(const float *const (&ga)[2], const float *const (&gb)[2], const TileDims &dm, Slabs &s,
+                                                 f32x4 (&acc)[4][4]) {
+    tile_product_f32<VEC>(ga, gb, dm.d, s.a, s.b, acc);
   }
-  if (q0 < Q) topk_store(lists, q0, Q, k, partial + (size_t)(2 * strip + (wave & 1)) * Q * k);
+};
+
+struct TileBf16 {
+  using elem = uint16_t;      // queries: the hi term of bf16 [3][Q][dpad]
+  struct Slabs { uint16_t a[2][3][SLAB], b[2][SLAB]; };                       // 65,536 bytes
+  static __device__ __forceinline__ int q_stride(const TileDims &dm) { return dm.dpad; }
+  template <bool VEC>
+  static __device__ __forceinline__ void product(const uint16_t *const (&ga)[2], const uint16_t *const (&gb)[2], const TileDims &dm, Slabs &s,
+                                                 f32x4 (&acc)[4][4]) {
+    tile_product_bf16<VEC>(ga, gb, dm.term, dm.d, dm.dpad, s.a, s.b, acc);
+  }
+};
+
+// this thread's two staging rows (tid >> 2 and + 64) of a slab that holds rows first .. first + 127 of `base`, clamped into its n rows
+template <class E, class I>
+__device__ __forceinline__ void stage_rows(const E *base, I first, I n, int ld, const E *(&g)[2]) {
+  const int sr = threadIdx.x >> 2;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) g[h] = base + (size_t)min(first + sr + 64 * h, n - 1) * ld;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(WG) void topk_strip_bf16_kernel(
-    const uint16_t *__restrict__ qs, const float *__restrict__ qb, const uint16_t *__restrict__ nodes, const float *__restrict__ cbias,
-    const unsigned *__restrict__ mask, long long mask_w, unsigned long long *__restrict__ partial,
-    int Q, long long N, int d, int dpad, int head, int q_blocks, int strips, int k) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[2][3][SLAB], sB[2][SLAB];
-  extern __shared__ __attribute__((aligned(16))) unsigned long long topk_dyn[];
+// Score-all: one 128 x 128 tile per workgroup, every score stored.
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void score_all_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, float *__restrict__ scores, int Q, long long N, int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  const int wave = threadIdx.x >> 6;
+  const int qt = (blockIdx.x % q_blocks) * 128;
+  const long long ct = (long long)(blockIdx.x / q_blocks) * 128;
+  const typename Tile::elem *ga[2], *gb[2];
+  stage_rows(q, qt, Q, Tile::q_stride(dm), ga);
+  stage_rows(nodes, ct, N, dm.d, gb);
+  f32x4 acc[4][4];
+  Tile::template product<VEC>(ga, gb, dm, slabs, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, ct + (wave & 1) * 64, Q, N, qb, head,
+                [&](int, int qrow) { return scores + (size_t)qrow * N; },
+                [&](long long col) { return cbias[col]; },
+                [&](float *out, int, int, long long col, float sc_) { out[col] = sc_; });
+}
+
+// Target score (pass 2 of the fused evaluator): tscore[q] = the score of query q's own target, from the SAME product and epilogue as
+// score-all -- one 128 x 128 tile per block of 128 queries whose "candidate" row j is nodes[target of query qt + j]; the diagonal cells
+// are kept.
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void target_score_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const long long *__restrict__ batch, float *__restrict__ tscore, int Q, int head) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
   const int tid = threadIdx.x, wave = tid >> 6;
+  const int qt = blockIdx.x * 128;
+  const int sr = tid >> 2;
+  const typename Tile::elem *ga[2], *gb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int row = min(qt + sr + 64 * h, Q - 1);
+    ga[h] = q + (size_t)row * Tile::q_stride(dm);
+    gb[h] = nodes + (size_t)rank_target(batch, row, head) * dm.d;
+  }
+  f32x4 acc[4][4];
+  Tile::template product<VEC>(ga, gb, dm, slabs, acc);
+  tile_epilogue(acc, qt + (wave >> 1) * 64, (long long)qt + (wave & 1) * 64, Q, (long long)Q, qb, head,
+                [&](int, int qrow) { return qrow; },
+                [&](long long col) { return cbias[rank_target(batch, (int)col, head)]; },
+                [&](int qrow, int, int, long long col, float sc_) { if (col == qrow) tscore[qrow] = sc_; });
+}
+
+// The strip walk of the count and the select kernel: a workgroup owns one block of 128 queries and a strip of candidate tiles, a wave
+// 64 rows x its 64-column half of every tile; action(acc, q0, c0) takes the wave's finished 64 x 64 block.  What a wave keeps over its
+// strip (counters, lists) is the caller's.  Returns where the wave stands: its first query row and its row of the partials.
+struct StripWave { int q0, part; };
+
+template <class Tile, bool VEC, class Action>
+__device__ __forceinline__ StripWave strip_walk(const typename Tile::elem *q, const typename Tile::elem *nodes, const TileDims &dm,
+                                                typename Tile::Slabs &slabs, int Q, long long N, int q_blocks, int strips, Action action) {
+  const int wave = threadIdx.x >> 6;
   const int qt = (blockIdx.x % q_blocks) * 128, strip = blockIdx.x / q_blocks;
   const long long n_tiles = (N + 127) / 128;
   const long long tile_end = strip_first(strip + 1, n_tiles, strips);
-  const int sr = tid >> 2, q0 = qt + (wave >> 1) * 64;
-  unsigned long long *lists, *thr;
-  topk_lds(topk_dyn, k, lists, thr);
-  const uint16_t *ga[2], *gb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) ga[h] = qs + (size_t)min(qt + sr + 64 * h, Q - 1) * dpad;
+  const int q0 = qt + (wave >> 1) * 64;
+  const typename Tile::elem *ga[2], *gb[2];
+  stage_rows(q, qt, Q, Tile::q_stride(dm), ga);
   for (long long tile = strip_first(strip, n_tiles, strips); tile < tile_end; ++tile) {
     const long long ct = tile * 128;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) gb[h] = nodes + (size_t)min(ct + sr + 64 * h, N - 1) * d;
+    stage_rows(nodes, ct, N, dm.d, gb);
     f32x4 acc[4][4];
-    tile_product_bf16<VEC>(ga, gb, (size_t)Q * dpad, d, dpad, sA, sB, acc);
+    Tile::template product<VEC>(ga, gb, dm, slabs, acc);
+    // the rows' target scores, thresholds, bias terms and addresses are formed again for every tile: hoisted out of this loop they would
+    // sit in ~100 registers through the product, and the kernel would drop to one workgroup per compute unit
     int q0t = q0;
     asm volatile("" : "+v"(q0t));
-    tile_select(acc, q0t, ct + (wave & 1) * 64, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
+    action(acc, q0t, ct + (wave & 1) * 64);
   }
-  if (q0 < Q) topk_store(lists, q0, Q, k, partial + (size_t)(2 * strip + (wave & 1)) * Q * k);
+  return {q0, 2 * strip + (wave & 1)};
+}
+
+// Strip count (pass 3 of the fused evaluator): counters stay in registers over the strip.
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void strip_count_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const float *__restrict__ tscore, const unsigned *__restrict__ mask, long long mask_w,
+    uint2 *__restrict__ partial, int Q, long long N, int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  int g = 0, e = 0;
+  const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
+    tile_count(acc, q0, c0, Q, N, qb, cbias, head, tscore, mask, mask_w, g, e);
+  });
+  strip_store(g, e, w.q0, Q, partial + (size_t)w.part * Q);
+}
+
+// Strip select (top-k): the lists stay in LDS over the strip.
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void strip_select_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const unsigned *__restrict__ mask, long long mask_w, unsigned long long *__restrict__ partial,
+    int Q, long long N, int head, int q_blocks, int strips, int k) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  extern __shared__ __attribute__((aligned(16))) unsigned long long topk_dyn[];
+  unsigned long long *lists, *thr;
+  topk_lds(topk_dyn, k, lists, thr);
+  const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
+    tile_select(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
+  });
+  if (w.q0 < Q) topk_store(lists, w.q0, Q, k, partial + (size_t)w.part * Q * k);
 }
 
 // Merge pass, one wave per query: of the n_part lists of k keys the k largest, in k rounds -- round j takes the largest key below the
@@ -790,6 +722,68 @@ __global__ __launch_bounds__(WG) void rank_count_kernel(const float *__restrict_
   }
 }
 
+// ------------------------------------------------------------------ host side: what every entry point of a storage shares
+template <class Tile>
+constexpr bool is_bf16 = std::is_same<Tile, TileBf16>::value;
+
+inline int64_t k_pad32(int32_t d) { return ((int64_t)d + 31) / 32 * 32; }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <class Tile>
+TileDims tile_dims(int64_t Q, int32_t d) {
+  const int dpad = is_bf16<Tile> ? (int)k_pad32(d) : d;
+  return {d, dpad, (size_t)Q * dpad};
+}
+
+// The load path of the entity rows, decided here for every role: f(true_type) launches the VEC instantiations, f(false_type) the element
+// by element ones -- the same instantiation, the same bits on every route.  16-byte loads want fp32 rows of d % 4 == 0; bf16 rows of
+// d % 8 == 0 on a 16-byte aligned table (WN18, FB15k-237).
+template <class Tile, class F>
+auto with_vec(const typename Tile::elem *nodes, int32_t d, F f) {
+  const bool vec = is_bf16<Tile> ? d % 8 == 0 && aligned16(nodes) : d % 4 == 0;
+  return vec ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the query kernel of the storage: q = fp32 query vectors [Q][d], or their three bf16 terms [3][Q][k_pad32(d)]
+template <class Tile>
+void launch_query(hipStream_t st, const long long *b, int64_t Q, int32_t head, const typename Tile::elem *nodes, const float *rel,
+                  const float *sbias, const float *pbias, const float *obias, typename Tile::elem *q, float *qb, int32_t d) {
+  const dim3 grid((unsigned)((Q + 3) / 4));
+  if constexpr (is_bf16<Tile>)
+    hipLaunchKernelGGL(rank_query_bf16_kernel, grid, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, q, qb, d, (int)k_pad32(d));
+  else
+    hipLaunchKernelGGL(rank_query_kernel, grid, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, q, qb, d);
+}
+
+// q: the caller's scratch for launch_query; hint: what the storage adds to the argument message
+template <class Tile>
+int score_all(const char *name, const char *hint, const int64_t *batch, int64_t Q, int32_t head, const typename Tile::elem *nodes,
+              const float *rel, const float *sbias, const float *pbias, const float *obias, typename Tile::elem *q, float *qbias,
+              float *scores, int64_t n_nodes, int32_t d, void *stream) {
+  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || (Q && (!batch || !nodes || !rel || !q || !scores)) ||
+      (is_bf16<Tile> && !aligned16(q))) {
+    rgcn_set_error("%s: bad argument%s", name, hint);
+    return RGCN_EINVAL;
+  }
+  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr) || (sbias && !qbias)) {
+    rgcn_set_error("%s: biases must be all set (with the qbias scratch) or all NULL", name);
+    return RGCN_EINVAL;
+  }
+  if (Q == 0) return RGCN_OK;
+  const int qbl = (int)((Q + 127) / 128);
+  const int64_t nwg = ((n_nodes + 127) / 128) * qbl;
+  if (nwg > INT32_MAX) { rgcn_set_error("%s: too many scores in one call; split the batch", name); return RGCN_EUNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  launch_query<Tile>(st, reinterpret_cast<const long long *>(batch), Q, head, nodes, rel, sbias, pbias, obias, q, qbias, d);
+  const float *qb1 = sbias ? qbias : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
+  with_vec<Tile>(nodes, d, [&](auto vec) {
+    hipLaunchKernelGGL((score_all_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const typename Tile::elem *)q,
+                       nodes, tile_dims<Tile>(Q, d), qb1, cb1, scores, (int)Q, (long long)n_nodes, head, qbl);
+  });
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
 }  // namespace
 
 extern "C" int rgcn_distmult_score_all_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes,
@@ -797,36 +791,8 @@ extern "C" int rgcn_distmult_score_all_f32(const int64_t *batch, int64_t Q, int3
                                            const float *obias, float *qvec, float *qbias, float *scores,
                                            int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || (Q && (!batch || !nodes || !rel || !qvec || !scores))) {
-    rgcn_set_error("distmult_score_all: bad argument");
-    return RGCN_EINVAL;
-  }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr) || (sbias && !qbias)) {
-    rgcn_set_error("distmult_score_all: biases must be all set (with the qbias scratch) or all NULL");
-    return RGCN_EINVAL;
-  }
-  if (Q == 0) return RGCN_OK;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rank_query_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(WG), 0, st,
-                     reinterpret_cast<const long long *>(batch), (int)Q, head, nodes, rel, sbias, pbias, obias, qvec,
-                     qbias, d);
-  {     // (round 5: the register-only tile variants behind RGCN_RANK_TILE -- measured slower than this LDS-staged kernel in round 1 -- are gone)
-    const int qbl = (int)((Q + 127) / 128);
-    const int64_t nwg = ((n_nodes + 127) / 128) * qbl;
-    if (nwg > INT32_MAX) { rgcn_set_error("distmult_score_all: too many scores in one call; split the batch"); return RGCN_EUNSUPPORTED; }
-    const float *qb1 = sbias ? qbias : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
-    if (d % 4 == 0)
-      hipLaunchKernelGGL(score_all_lds_kernel<true>, dim3((unsigned)nwg), dim3(WG), 0, st, qvec, qb1, nodes, cb1, scores,
-                         (int)Q, (long long)n_nodes, d, head, qbl);
-    else
-      hipLaunchKernelGGL(score_all_lds_kernel<false>, dim3((unsigned)nwg), dim3(WG), 0, st, qvec, qb1, nodes, cb1, scores,
-                         (int)Q, (long long)n_nodes, d, head, qbl);
-    HIP_TRY(hipGetLastError());
-    return RGCN_OK;
-  }
+  return score_all<TileF32>("distmult_score_all", "", batch, Q, head, nodes, rel, sbias, pbias, obias, qvec, qbias, scores, n_nodes, d, stream);
 }
-
-static int64_t k_pad32(int32_t d) { return ((int64_t)d + 31) / 32 * 32; }
 
 extern "C" int64_t rgcn_distmult_score_all_bf16_workspace_bytes(int64_t Q, int32_t d) {
   return (Q < 0 || d <= 0) ? 0 : 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t);
@@ -837,34 +803,8 @@ extern "C" int rgcn_distmult_score_all_bf16(const int64_t *batch, int64_t Q, int
                                             const float *obias, uint16_t *qsplit, float *qbias, float *scores,
                                             int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || (Q && (!batch || !nodes || !rel || !qsplit || !scores)) ||
-      (reinterpret_cast<uintptr_t>(qsplit) & 15)) {
-    rgcn_set_error("distmult_score_all_bf16: bad argument (qsplit: 16-byte aligned)");
-    return RGCN_EINVAL;
-  }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr) || (sbias && !qbias)) {
-    rgcn_set_error("distmult_score_all_bf16: biases must be all set (with the qbias scratch) or all NULL");
-    return RGCN_EINVAL;
-  }
-  if (Q == 0) return RGCN_OK;
-  const int qbl = (int)((Q + 127) / 128);
-  const int64_t nwg = ((n_nodes + 127) / 128) * qbl;
-  if (nwg > INT32_MAX) { rgcn_set_error("distmult_score_all_bf16: too many scores in one call; split the batch"); return RGCN_EUNSUPPORTED; }
-  hipStream_t st = (hipStream_t)stream;
-  const int dpad = (int)k_pad32(d);
-  hipLaunchKernelGGL(rank_query_bf16_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(WG), 0, st,
-                     reinterpret_cast<const long long *>(batch), (int)Q, head, nodes, rel, sbias, pbias, obias, qsplit,
-                     qbias, d, dpad);
-  const float *qb1 = sbias ? qbias : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
-  // 16-byte loads of the entity rows: d % 8 == 0 on an aligned table (WN18, FB15k-237); else element by element
-  if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(nodes) & 15) == 0)
-    hipLaunchKernelGGL(score_all_bf16_kernel<true>, dim3((unsigned)nwg), dim3(WG), 0, st, qsplit, qb1, nodes, cb1, scores,
-                       (int)Q, (long long)n_nodes, d, dpad, head, qbl);
-  else
-    hipLaunchKernelGGL(score_all_bf16_kernel<false>, dim3((unsigned)nwg), dim3(WG), 0, st, qsplit, qb1, nodes, cb1, scores,
-                       (int)Q, (long long)n_nodes, d, dpad, head, qbl);
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
+  return score_all<TileBf16>("distmult_score_all_bf16", " (qsplit: 16-byte aligned)", batch, Q, head, nodes, rel, sbias, pbias, obias, qsplit,
+                             qbias, scores, n_nodes, d, stream);
 }
 
 extern "C" int rgcn_rank_filter_f32(float *scores, int64_t Q, int64_t n_nodes, const int32_t *filt_q,
@@ -906,86 +846,127 @@ inline int64_t fused_default_strips(int64_t Q, int64_t n_nodes, int64_t n_cu) {
   return std::max<int64_t>(1, std::min(n_tiles, (2 * std::min(n_cu, FUSED_CU_CAP) + qbl - 1) / qbl));
 }
 
-struct FusedLayout { int64_t qv, qb, part, mask, total, mask_w; };
-
+// The workspace of a strip route: query vectors | query-side bias terms | the strips' partials | filter bits.  bytes_per_cell: what a
+// (strip half, query) cell of the partials holds -- the (greater, equal) pair of the evaluator, k keys of the top-k.
 // strips = 0: room for the default of any device up to FUSED_CU_CAP units, by a bound that grows with Q and with N:
 // strips * Q <= min(n_tiles * Q, 2 * CAP * 128 + Q)
-inline FusedLayout fused_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t strips, bool bf16) {
-  FusedLayout L;
+struct StripLayout { int64_t qv, qb, part, mask, total, mask_w; };
+
+inline StripLayout strip_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t strips, bool bf16, int64_t bytes_per_cell) {
+  StripLayout L;
   L.mask_w = (n_nodes + 31) / 32;
   const int64_t n_tiles = (n_nodes + 127) / 128;
   const int64_t cells = strips > 0 ? strips * Q : std::min(n_tiles * Q, 2 * FUSED_CU_CAP * 128 + Q);
   L.qv = 0;
   L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
   L.part = L.qb + align16(2 * Q * (int64_t)sizeof(float));
-  L.mask = L.part + align16(2 * cells * (int64_t)sizeof(uint2));
+  L.mask = L.part + align16(2 * cells * bytes_per_cell);
   L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
   return L;
 }
 
-template <bool BF16, class T>
-int rank_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, const T *nodes, const float *rel, const float *sbias,
-               const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F, int32_t strips,
-               void *workspace, int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t d, void *stream) {
-  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || F < 0 || strips < 0 || (F && (!filt_q || !filt_n)) ||
-      (Q && (!batch || !nodes || !rel || !workspace || !greater || !ties || !tscore)) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-    rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; strips >= 0; F > 0 needs both filter lists)", name);
+// what the strip entry points share of their C signatures, in that order
+template <class E>
+struct StripArgs {
+  const char *name;
+  const int64_t *batch;
+  int64_t Q;
+  int32_t head;
+  const E *nodes;
+  const float *rel, *sbias, *pbias, *obias;
+  const int32_t *filt_q, *filt_n;
+  int64_t F;
+  int32_t strips;
+  void *workspace;
+  int64_t n_nodes;
+  int32_t d;
+  void *stream;
+};
+
+// Argument and bias checks of a strip entry point.  bad_own: the caller's conditions on its own arguments; hint: what they add to the message.
+template <class E>
+int strip_check(const StripArgs<E> &a, bool bad_own, const char *hint) {
+  if (a.Q < 0 || a.n_nodes <= 0 || a.d <= 0 || a.Q > INT32_MAX || a.F < 0 || a.strips < 0 || bad_own || (a.F && (!a.filt_q || !a.filt_n)) ||
+      (a.Q && (!a.batch || !a.nodes || !a.rel || !a.workspace)) || !aligned16(a.workspace)) {
+    rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; %sstrips >= 0; F > 0 needs both filter lists)", a.name, hint);
     return RGCN_EINVAL;
   }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) {
-    rgcn_set_error("%s: biases must be all set or all NULL", name);
+  if ((a.sbias != nullptr) != (a.pbias != nullptr) || (a.sbias != nullptr) != (a.obias != nullptr)) {
+    rgcn_set_error("%s: biases must be all set or all NULL", a.name);
     return RGCN_EINVAL;
   }
-  if (Q == 0) return RGCN_OK;
-  int dev = 0, n_cu = 0;
-  HIP_TRY(launch_device(&dev, &n_cu));
-  const int64_t qbl = (Q + 127) / 128, n_tiles = (n_nodes + 127) / 128;
-  const int64_t n_strips = strips > 0 ? strips : fused_default_strips(Q, n_nodes, n_cu);
-  // a strip's counters are 32-bit: (tiles of the longest strip) * 128 cells per query
-  if (n_strips * qbl > INT32_MAX || n_tiles > INT32_MAX || ((n_tiles + n_strips - 1) / n_strips + 1) * 128 > INT32_MAX) {
-    rgcn_set_error("%s: too many scores in one call; split the batch", name);
+  return RGCN_OK;
+}
+
+// a strip call that passed its checks (Q > 0): the grid, the carved workspace and the operands of its kernels
+template <class Tile>
+struct StripCall {
+  int dev;
+  int64_t qbl, n_strips, mask_w;
+  hipStream_t st;
+  const long long *b;
+  const typename Tile::elem *q;
+  TileDims dm;
+  const float *qb, *cbias;        // NULL without biases
+  void *part;
+  const unsigned *mask;           // NULL without a filter
+};
+
+// The rest of the preamble: the strips (too_many(n_strips): the caller's bound on them, `what` names it in the message), the workspace
+// carved, the filter bits built and the query kernel of the storage launched.
+template <class Tile, class TooMany>
+int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, TooMany too_many, const char *what,
+                StripCall<Tile> &c) {
+  int n_cu = 0;
+  HIP_TRY(launch_device(&c.dev, &n_cu));
+  c.qbl = (a.Q + 127) / 128;
+  c.n_strips = a.strips > 0 ? a.strips : fused_default_strips(a.Q, a.n_nodes, n_cu);
+  if (c.n_strips * c.qbl > INT32_MAX || too_many(c.n_strips)) {
+    rgcn_set_error("%s: too many %s in one call; split the batch", a.name, what);
     return RGCN_EUNSUPPORTED;
   }
-  const FusedLayout L = fused_layout(Q, n_nodes, d, strips, BF16);
-  char *ws = static_cast<char *>(workspace);
+  const StripLayout L = strip_layout(a.Q, a.n_nodes, a.d, a.strips, is_bf16<Tile>, bytes_per_cell);
+  char *ws = static_cast<char *>(a.workspace);
+  typename Tile::elem *q = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
   float *qb = reinterpret_cast<float *>(ws + L.qb);
-  uint2 *part = reinterpret_cast<uint2 *>(ws + L.part);
-  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const long long *b = reinterpret_cast<const long long *>(batch);
-  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
-  if (F) {
-    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
-    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
-                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, 0);
+  unsigned *mask = a.F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  c.mask_w = L.mask_w;
+  c.st = (hipStream_t)a.stream;
+  c.b = reinterpret_cast<const long long *>(a.batch);
+  c.q = q;
+  c.dm = tile_dims<Tile>(a.Q, a.d);
+  c.qb = a.sbias ? qb : nullptr;
+  c.cbias = a.sbias ? (a.head ? a.sbias : a.obias) : nullptr;
+  c.part = ws + L.part;
+  c.mask = mask;
+  if (a.F) {
+    HIP_TRY(zero_async(mask, (size_t)(a.Q * L.mask_w) * sizeof(unsigned), c.st));
+    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, c.st, mask,
+                       (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head, keep_target);
   }
-  const dim3 gq((unsigned)((Q + 3) / 4)), gt((unsigned)qbl), gc((unsigned)(n_strips * qbl));
-  if constexpr (BF16) {
-    uint16_t *qs = reinterpret_cast<uint16_t *>(ws + L.qv);
-    const int dpad = (int)k_pad32(d);
-    hipLaunchKernelGGL(rank_query_bf16_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qs, qb, d, dpad);
-    // 16-byte loads of the entity rows as in rgcn_distmult_score_all_bf16: the same instantiation, the same bits
-    auto run = [&](auto vec) {
-      constexpr bool V = decltype(vec)::value;
-      hipLaunchKernelGGL(rank_target_bf16_kernel<V>, gt, dim3(WG), 0, st, qs, qb1, nodes, cb1, b, tscore, (int)Q, d, dpad, head);
-      hipLaunchKernelGGL(rank_count_fused_bf16_kernel<V>, gc, dim3(WG), 0, st, qs, qb1, nodes, cb1, tscore, mask, (long long)L.mask_w,
-                         part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips);
-    };
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(nodes) & 15) == 0) run(std::true_type{});
-    else run(std::false_type{});
-  } else {
-    float *qvec = reinterpret_cast<float *>(ws + L.qv);
-    hipLaunchKernelGGL(rank_query_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qvec, qb, d);
-    auto run = [&](auto vec) {
-      constexpr bool V = decltype(vec)::value;
-      hipLaunchKernelGGL(rank_target_kernel<V>, gt, dim3(WG), 0, st, qvec, qb1, nodes, cb1, b, tscore, (int)Q, d, head);
-      hipLaunchKernelGGL(rank_count_fused_kernel<V>, gc, dim3(WG), 0, st, qvec, qb1, nodes, cb1, tscore, mask, (long long)L.mask_w,
-                         part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips);
-    };
-    if (d % 4 == 0) run(std::true_type{});
-    else run(std::false_type{});
-  }
-  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((Q + WG - 1) / WG)), dim3(WG), 0, st, part, (int)(2 * n_strips), (int)Q,
+  launch_query<Tile>(c.st, c.b, a.Q, a.head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, q, qb, a.d);
+  return RGCN_OK;
+}
+
+template <class Tile>
+int rank_fused(const StripArgs<typename Tile::elem> &a, int64_t *greater, int64_t *ties, float *tscore) {
+  if (int rc = strip_check(a, a.Q && (!greater || !ties || !tscore), "")) return rc;
+  if (a.Q == 0) return RGCN_OK;
+  StripCall<Tile> c;
+  const int64_t n_tiles = (a.n_nodes + 127) / 128;
+  // a strip's counters are 32-bit: (tiles of the longest strip) * 128 cells per query
+  auto too_many = [&](int64_t n_strips) { return n_tiles > INT32_MAX || ((n_tiles + n_strips - 1) / n_strips + 1) * 128 > INT32_MAX; };
+  if (int rc = strip_begin<Tile>(a, sizeof(uint2), 0, too_many, "scores", c)) return rc;
+  uint2 *part = static_cast<uint2 *>(c.part);
+  const int Q = (int)a.Q;
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    constexpr bool V = decltype(vec)::value;
+    hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
+                       a.head);
+    hipLaunchKernelGGL((strip_count_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
+                       (const float *)tscore, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+  });
+  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const uint2 *)part, (int)(2 * c.n_strips), Q,
                      reinterpret_cast<long long *>(greater), reinterpret_cast<long long *>(ties));
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -994,7 +975,7 @@ int rank_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, 
 }  // namespace
 
 extern "C" int64_t rgcn_distmult_rank_fused_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
-  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : fused_layout(Q, n_nodes, d, strips, bf16 != 0).total;
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, sizeof(uint2)).total;
 }
 
 extern "C" int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
@@ -1002,8 +983,8 @@ extern "C" int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int
                                             const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
                                             int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return rank_fused<false>("distmult_rank_fused", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                           greater, ties, tscore, n_nodes, d, stream);
+  return rank_fused<TileF32>({"distmult_rank_fused", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                              n_nodes, d, stream}, greater, ties, tscore);
 }
 
 extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
@@ -1011,8 +992,8 @@ extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, in
                                              const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
                                              int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return rank_fused<true>("distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                          greater, ties, tscore, n_nodes, d, stream);
+  return rank_fused<TileBf16>({"distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips,
+                               workspace, n_nodes, d, stream}, greater, ties, tscore);
 }
 
 // ------------------------------------------------------------------ top-k prediction: entry points
@@ -1020,99 +1001,37 @@ namespace {
 
 constexpr int TOPK_LDS_CU = 160 * 1024;        // LDS of a compute unit: the static operand slabs and the lists share it
 
-struct TopkLayout { int64_t qv, qb, part, mask, total, mask_w; };
+inline int64_t topk_cell_bytes(int64_t k) { return k * (int64_t)sizeof(unsigned long long); }       // k keys per (strip half, query)
 
-// FusedLayout with k keys of 8 bytes per (strip half, query) in place of the (greater, equal) pair; the same `cells` bound
-inline TopkLayout topk_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t k, int64_t strips, bool bf16) {
-  TopkLayout L;
-  L.mask_w = (n_nodes + 31) / 32;
-  const int64_t n_tiles = (n_nodes + 127) / 128;
-  const int64_t cells = strips > 0 ? strips * Q : std::min(n_tiles * Q, 2 * FUSED_CU_CAP * 128 + Q);
-  L.qv = 0;
-  L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
-  L.part = L.qb + align16(2 * Q * (int64_t)sizeof(float));
-  L.mask = L.part + align16(2 * cells * k * (int64_t)sizeof(unsigned long long));
-  L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
-  return L;
-}
-
-template <bool BF16, class T>
-int topk_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, const T *nodes, const float *rel, const float *sbias,
-               const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F, int32_t k, int32_t strips,
-               void *workspace, int64_t *ids, float *scores, int64_t n_nodes, int32_t d, void *stream) {
-  if (Q < 0 || n_nodes <= 0 || d <= 0 || Q > INT32_MAX || F < 0 || k < 1 || strips < 0 || (F && (!filt_q || !filt_n)) ||
-      (Q && (!batch || !nodes || !rel || !workspace || !ids || !scores)) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-    rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; k >= 1; strips >= 0; F > 0 needs both filter lists)", name);
-    return RGCN_EINVAL;
-  }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) {
-    rgcn_set_error("%s: biases must be all set or all NULL", name);
-    return RGCN_EINVAL;
-  }
+template <class Tile>
+int topk_fused(const StripArgs<typename Tile::elem> &a, int32_t k, int64_t *ids, float *scores) {
+  if (int rc = strip_check(a, k < 1 || (a.Q && (!ids || !scores)), "k >= 1; ")) return rc;
   if (k > TOPK_MAX) {
-    rgcn_set_error("%s: k = %d is above the native limit of %d; select from the materialised scores instead", name, (int)k, TOPK_MAX);
+    rgcn_set_error("%s: k = %d is above the native limit of %d; select from the materialised scores instead", a.name, (int)k, TOPK_MAX);
     return RGCN_EUNSUPPORTED;
   }
-  if (n_nodes > INT32_MAX) {
-    rgcn_set_error("%s: entity ids must fit 31 bits", name);
+  if (a.n_nodes > INT32_MAX) {
+    rgcn_set_error("%s: entity ids must fit 31 bits", a.name);
     return RGCN_EUNSUPPORTED;
   }
-  if (Q == 0) return RGCN_OK;
-  int dev = 0, n_cu = 0;
-  HIP_TRY(launch_device(&dev, &n_cu));
-  const int64_t qbl = (Q + 127) / 128;
-  const int64_t n_strips = strips > 0 ? strips : fused_default_strips(Q, n_nodes, n_cu);
-  if (n_strips * qbl > INT32_MAX || 2 * n_strips * k > INT32_MAX) {
-    rgcn_set_error("%s: too many strips in one call; split the batch", name);
-    return RGCN_EUNSUPPORTED;
-  }
-  const TopkLayout L = topk_layout(Q, n_nodes, d, k, strips, BF16);
-  char *ws = static_cast<char *>(workspace);
-  float *qb = reinterpret_cast<float *>(ws + L.qb);
-  unsigned long long *part = reinterpret_cast<unsigned long long *>(ws + L.part);
-  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const long long *b = reinterpret_cast<const long long *>(batch);
-  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
-  if (F) {
-    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
-    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
-                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, 1);
-  }
-  const dim3 gq((unsigned)((Q + 3) / 4)), gc((unsigned)(n_strips * qbl));
+  if (a.Q == 0) return RGCN_OK;
+  StripCall<Tile> c;
+  auto too_many = [&](int64_t n_strips) { return 2 * n_strips * k > INT32_MAX; };
+  if (int rc = strip_begin<Tile>(a, topk_cell_bytes(k), 1, too_many, "strips", c)) return rc;
+  unsigned long long *part = static_cast<unsigned long long *>(c.part);
   const size_t lds = (size_t)4 * 64 * (k + 1) * sizeof(unsigned long long);       // the lists and thresholds, sized by this call's k
   // the slabs are static LDS: the lists may take what they leave of the compute unit
-  constexpr size_t slabs = BF16 ? sizeof(uint16_t) * (2 * 3 * SLAB + 2 * SLAB) : sizeof(float) * (4 * 128 * LDS_LD);
-  auto strip_pass = [&](auto kc, auto... args) -> hipError_t {
-    constexpr auto kern = decltype(kc)::value;
-    hipError_t e = allow_lds<kern>(dev, slabs + lds, (int)(TOPK_LDS_CU - slabs));
+  constexpr size_t slabs = sizeof(typename Tile::Slabs);
+  HIP_TRY(with_vec<Tile>(a.nodes, a.d, [&](auto vec) -> hipError_t {
+    constexpr auto kern = strip_select_kernel<Tile, decltype(vec)::value>;
+    hipError_t e = allow_lds<kern>(c.dev, slabs + lds, (int)(TOPK_LDS_CU - slabs));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, gc, dim3(WG), lds, st, args...);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), lds, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.mask, (long long)c.mask_w, part,
+                       (int)a.Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips, (int)k);
     return hipSuccess;
-  };
-  if constexpr (BF16) {
-    uint16_t *qs = reinterpret_cast<uint16_t *>(ws + L.qv);
-    const int dpad = (int)k_pad32(d);
-    hipLaunchKernelGGL(rank_query_bf16_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qs, qb, d, dpad);
-    // 16-byte loads of the entity rows as in rgcn_distmult_score_all_bf16: the same instantiation, the same bits
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(nodes) & 15) == 0)
-      HIP_TRY(strip_pass(kern_c<topk_strip_bf16_kernel<true>>, (const uint16_t *)qs, qb1, nodes, cb1, (const unsigned *)mask,
-                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips, (int)k));
-    else
-      HIP_TRY(strip_pass(kern_c<topk_strip_bf16_kernel<false>>, (const uint16_t *)qs, qb1, nodes, cb1, (const unsigned *)mask,
-                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, dpad, head, (int)qbl, (int)n_strips, (int)k));
-  } else {
-    float *qvec = reinterpret_cast<float *>(ws + L.qv);
-    hipLaunchKernelGGL(rank_query_kernel, gq, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, qvec, qb, d);
-    if (d % 4 == 0)
-      HIP_TRY(strip_pass(kern_c<topk_strip_kernel<true>>, (const float *)qvec, qb1, nodes, cb1, (const unsigned *)mask,
-                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips, (int)k));
-    else
-      HIP_TRY(strip_pass(kern_c<topk_strip_kernel<false>>, (const float *)qvec, qb1, nodes, cb1, (const unsigned *)mask,
-                         (long long)L.mask_w, part, (int)Q, (long long)n_nodes, d, head, (int)qbl, (int)n_strips, (int)k));
-  }
-  hipLaunchKernelGGL(topk_merge_kernel, gq, dim3(WG), 0, st, (const unsigned long long *)part, (int)(2 * n_strips), (int)Q, (int)k,
-                     reinterpret_cast<long long *>(ids), scores);
+  }));
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((a.Q + 3) / 4)), dim3(WG), 0, c.st, (const unsigned long long *)part,
+                     (int)(2 * c.n_strips), (int)a.Q, (int)k, reinterpret_cast<long long *>(ids), scores);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1120,7 +1039,8 @@ int topk_fused(const char *name, const int64_t *batch, int64_t Q, int32_t head, 
 }  // namespace
 
 extern "C" int64_t rgcn_distmult_topk_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t k, int32_t strips, int32_t bf16) {
-  return (Q < 0 || n_nodes <= 0 || d <= 0 || k < 1 || k > TOPK_MAX || strips < 0) ? 0 : topk_layout(Q, n_nodes, d, k, strips, bf16 != 0).total;
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || k < 1 || k > TOPK_MAX || strips < 0)
+             ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, topk_cell_bytes(k)).total;
 }
 
 extern "C" int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
@@ -1128,8 +1048,8 @@ extern "C" int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t h
                                       const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
                                       float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return topk_fused<false>("distmult_topk", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, k, strips, workspace, ids,
-                           scores, n_nodes, d, stream);
+  return topk_fused<TileF32>({"distmult_topk", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes,
+                              d, stream}, k, ids, scores);
 }
 
 extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
@@ -1137,6 +1057,6 @@ extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t 
                                        const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
                                        float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return topk_fused<true>("distmult_topk_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, k, strips, workspace, ids,
-                          scores, n_nodes, d, stream);
+  return topk_fused<TileBf16>({"distmult_topk_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                               n_nodes, d, stream}, k, ids, scores);
 }
