@@ -856,6 +856,43 @@ RGCN_API int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t he
                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
                                      const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
                                      float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* 1-N softmax loss (an extension: the reference trains on sampled negatives only), forward: for each of the Q queries of `batch`
+ *   lse[q] = log sum_{n allowed} exp(s[q, n])      and      tscore[q] = s[q, target_q]
+ * with s the cells of rgcn_distmult_score_all_f32 / _bf16 bit for bit (the same product and bias epilogue) and `allowed` every
+ * n < n_nodes whose bit of the fused evaluator's mask is clear -- filt_q / filt_n [F] as in rgcn_distmult_rank_fused_*: an entry on a
+ * query's own target is IGNORED, so the target is always in the sum.  The loss of a query is lse[q] - tscore[q]; no [Q, n_nodes] buffer
+ * exists.  Passes on `stream`, no host synchronisation, no memset: the query pass; the target pass of the fused evaluator; the strip
+ * pass on its grid, each wave keeping one (m, l) = (largest score, sum exp(score - m)) pair per query row in registers and writing one
+ * pair per strip half and query ((-inf, 0) for a strip without a tile); a merge pass that folds the 2 strips pairs of a query in index
+ * order into m + log l (-inf when nothing was allowed).  exp in the strip pass is the hardware's 2^x on x log2 e (arguments <= 0).
+ * workspace: rgcn_distmult_lse_workspace_bytes(Q, n_nodes, d, strips, bf16) bytes -- the layout, and the size, of
+ * rgcn_distmult_rank_fused_workspace_bytes --, 16-byte aligned.  Errors as rgcn_distmult_rank_fused_*: RGCN_EINVAL for bad, NULL or
+ * misaligned arguments, strips < 0 and biases partly set; RGCN_EUNSUPPORTED beyond INT32_MAX workgroups; Q == 0 launches nothing.
+ * Filter entries and triples are NOT range-checked on the device (the Python wrapper checks). */
+RGCN_API int64_t rgcn_distmult_lse_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
+RGCN_API int rgcn_distmult_lse_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                   const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                   const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                   int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                    const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                    const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                    int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* 1-N softmax loss, gradient cells of the candidate columns [c_first, c_first + c_count) (c_first a multiple of 128, the chunk inside
+ * [0, n_nodes)), fp32 only: the product is computed again, one 128 x 128 tile per workgroup, and
+ *   dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),   a filtered cell 0,
+ * dS row-major [Q, c_count].  scale_q = gscale[per_query ? q : 0] / mean_over: gscale is a DEVICE float ([1], or [Q] with
+ * per_query != 0) -- the upstream gradient, never read back --, mean_over >= 1 the host's divisor of a mean (the ABI passes no float by
+ * value).  lse [Q]: what rgcn_distmult_lse_f32 returned for the same arguments.  The call stands alone: query vectors, bias terms and
+ * the filter bits OF THE CHUNK are formed again in `workspace` (rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d) bytes,
+ * 16-byte aligned: nothing of the forward's workspace has to outlive it, and the mask is [Q][ceil(c_count / 32)] words, not the whole
+ * [Q][ceil(n_nodes / 32)]).  No host synchronisation, no memset; errors as above. */
+RGCN_API int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d);
+RGCN_API int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                            const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
+                                            int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                            int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,10 +12,11 @@
 // because both operands use the same permutation and the sum over k does not care.
 // Second route (rgcn_distmult_rank_fused_*, utils/misc.py:40-58, 71-99): the same tile product with an epilogue that compares every score
 // with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.  Third (rgcn_distmult_topk_*):
-// an epilogue that selects the k best.
-// Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select) first; then a tile-precision trait
-// (TileF32 / TileBf16) and the four kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel --
-// each written once over <Tile, VEC>; then the entry points.
+// an epilogue that selects the k best.  Fourth (rgcn_distmult_lse_*, rgcn_distmult_softmax_grad_f32; an extension, the reference trains on
+// sampled negatives only): an epilogue that adds exp(score) for the 1-N softmax loss, and the gradient cells of that loss in column chunks.
+// Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select, add) first; then a tile-precision trait
+// (TileF32 / TileBf16) and the kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel,
+// strip_lse_kernel -- each written once over <Tile, VEC>, and softmax_grad_kernel (fp32); then the entry points.
 #include <cmath>
 #include <cstdlib>
 
@@ -482,7 +483,79 @@ __device__ __forceinline__ void topk_store(const unsigned long long *lists, int 
   for (int e = lane; e < n; e += 64) part[(size_t)q0 * k + e] = lds_ld64(lists + e);
 }
 
-// ------------------------------------------------------------------ the tile precision and the four kernel roles
+// ------------------------------------------------------------------ 1-N softmax loss: log-sum-exp per query
+// The product and epilogue once more, with an epilogue that ADDS: lse[q] = log sum exp(score) over the cells that are not filtered.
+// Every row carries a pair (m, l): m = the largest score seen, l = sum exp(score - m) -- scores beyond +-88 occur, exp(score) alone
+// overflows.  Two pairs merge as (max(m1, m2), l1 exp(m1 - m) + l2 exp(m2 - m)); the empty pair is (-inf, 0), and a merge against
+// m = -inf subtracts 0 instead (-inf - -inf is NaN).  exp is __expf (v_exp_f32 on x log2 e): every argument is <= 0, a term's relative
+// error is ~|x| 2^-23, and the terms with a large |x| are the ones that do not count.  exp(0) is exactly 1, so a row whose only cell is
+// its target has l = 1.
+__device__ __forceinline__ float row16_max_f(float v) {
+  v = fmaxf(v, __int_as_float(dpp_i<0xB1>(__float_as_int(v), __float_as_int(v))));      // the four steps of tile_count
+  v = fmaxf(v, __int_as_float(dpp_i<0x4E>(__float_as_int(v), __float_as_int(v))));
+  v = fmaxf(v, __int_as_float(dpp_i<0x141>(__float_as_int(v), __float_as_int(v))));
+  v = fmaxf(v, __int_as_float(dpp_i<0x140>(__float_as_int(v), __float_as_int(v))));
+  return v;
+}
+__device__ __forceinline__ float row16_sum_f(float v) {       // a + b = b + a: after each exchange both partners hold the same bits
+  v += __int_as_float(dpp_i<0xB1>(__float_as_int(v), __float_as_int(v)));
+  v += __int_as_float(dpp_i<0x4E>(__float_as_int(v), __float_as_int(v)));
+  v += __int_as_float(dpp_i<0x141>(__float_as_int(v), __float_as_int(v)));
+  v += __int_as_float(dpp_i<0x140>(__float_as_int(v), __float_as_int(v)));
+  return v;
+}
+__device__ __forceinline__ void lse_merge(float &m, float &l, float m2, float l2) {
+  const float mn = fmaxf(m, m2), ref = mn == -INFINITY ? 0.f : mn;
+  l = l * __expf(m - ref) + l2 * __expf(m2 - ref);
+  m = mn;
+}
+
+// The adding epilogue of one tile: tile_epilogue over the wave's whole 64 x 64 block as tile_select runs it (n_cols = c0 + 64: the 16
+// lanes of a row stay together; a column past N is clamped for its bias and counts as filtered), the mask words read as tile_count reads
+// them.  A row's four cells per lane wait in p[]; at the fourth the row's maximum and then its sum go over the 16 lanes, and lane
+// i = row keeps the tile's pair of that row -- merged into the wave's running (m, l) once per tile: two registers across the product.
+struct LseRow { unsigned w[2]; };
+
+__device__ __forceinline__ void tile_lse(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long N, const float *__restrict__ qb,
+                                         const float *__restrict__ cbias, int head, const unsigned *__restrict__ mask, long long mask_w,
+                                         float &m, float &l) {
+  const int i = threadIdx.x & 15;
+  float p[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  float tm = -INFINITY, tl = 0.f;
+  tile_epilogue(acc, q0, c0, Q, c0 + 64, qb, head,
+                [&](int, int qrow) {
+                  LseRow st{{0u, 0u}};
+                  if (mask) {
+                    const long long w0 = c0 >> 5;
+                    const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                    if (w0 < mask_w) st.w[0] = mrow[w0];                  // (the right half of a ragged last tile may start past N)
+                    if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  }
+                  return st;
+                },
+                [&](long long col) { return cbias[col < N ? col : N - 1]; },
+                [&](const LseRow &st, int row, int b, long long col, float sc_) {
+                  const bool out = col >= N || ((st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u);
+                  p[b] = out ? -INFINITY : sc_;
+                  if (b == 3) {
+                    const float rm = row16_max_f(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])));
+                    const float ref = rm == -INFINITY ? 0.f : rm;
+                    const float rl = row16_sum_f((__expf(p[0] - ref) + __expf(p[1] - ref)) + (__expf(p[2] - ref) + __expf(p[3] - ref)));
+                    tm = i == row ? rm : tm;
+                    tl = i == row ? rl : tl;
+                  }
+                });
+  lse_merge(m, l, tm, tl);
+}
+
+// a wave's pairs -> partial[2 strip + candidate half of the wave][q] = (m, l); the rows as strip_store maps them
+__device__ __forceinline__ void lse_store(float m, float l, int q0, int Q, float2 *__restrict__ part) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
+  const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
+  if (qrow < Q) part[qrow] = float2{m, l};
+}
+
+// ------------------------------------------------------------------ the tile precision and the kernel roles
 // What a kernel has to know about the storage of the entity table: the operand element type, the static LDS slabs of a workgroup, the
 // stride of the query rows and which product loop runs.  Every role below is written once over <Tile, VEC> (VEC: 16-byte loads of the
 // entity rows); the roles of one <Tile, VEC> share one product and tile_epilogue, hence the same bits for the same pair of rows.
@@ -628,6 +701,89 @@ __global__ __launch_bounds__(WG) void strip_select_kernel(
     tile_select(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, lists, thr, k);
   });
   if (w.q0 < Q) topk_store(lists, w.q0, Q, k, partial + (size_t)w.part * Q * k);
+}
+
+// Strip log-sum-exp (1-N softmax loss): the wave's (m, l) pairs stay in registers over the strip; a strip without a tile writes (-inf, 0).
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void strip_lse_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const unsigned *__restrict__ mask, long long mask_w, float2 *__restrict__ partial, int Q, long long N,
+    int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  float m = -INFINITY, l = 0.f;
+  const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
+    tile_lse(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, m, l);
+  });
+  lse_store(m, l, w.q0, Q, partial + (size_t)w.part * Q);
+}
+
+// the strips' pairs [n_part][Q] merged in index order (one answer for one `strips`); accurate expf / logf: Q values
+__global__ __launch_bounds__(WG) void lse_merge_kernel(const float2 *__restrict__ partial, int n_part, int Q, float *__restrict__ lse) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= Q) return;
+  float m = -INFINITY, l = 0.f;
+  for (int p = 0; p < n_part; ++p) {
+    const float2 v = partial[(size_t)p * Q + q];
+    const float mn = fmaxf(m, v.x);
+    if (mn == -INFINITY) continue;                           // both empty: -inf - -inf would be NaN
+    l = l * expf(m - mn) + v.y * expf(v.x - mn);
+    m = mn;
+  }
+  lse[q] = m == -INFINITY ? -INFINITY : m + logf(l);
+}
+
+// Gradient cells of the 1-N softmax loss, on the score-all grid cut to the candidate columns [c_first, c_first + c_count) (c_first a
+// multiple of 128: tiles and mask words align as in tile_count): dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),
+// a filtered cell 0; scale_q = gscale[per_query ? q : 0] * inv_q -- the upstream gradient is read on the device.  mask: the filter
+// bits of THIS chunk, [Q][mask_w] with bit 0 of word 0 = column c_first.  The product is recomputed (fp32 only): s is bit for bit the
+// cell the strip kernel added, so a row whose only cell is its target gets exp(0) - 1 = 0.
+struct GradRow { float lse, scale; long long tgt; unsigned w[2]; float *out; };
+
+template <bool VEC>
+__global__ __launch_bounds__(WG) void softmax_grad_kernel(
+    const float *__restrict__ q, const float *__restrict__ nodes, TileDims dm, const float *__restrict__ qb, const float *__restrict__ cbias,
+    const long long *__restrict__ batch, const float *__restrict__ lse, const float *__restrict__ gscale, int per_query, float inv_q,
+    const unsigned *__restrict__ mask, long long mask_w, float *__restrict__ dS, int Q, long long N, long long c_first, long long c_count,
+    int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) TileF32::Slabs slabs;
+  const int wave = threadIdx.x >> 6, i = threadIdx.x & 15;
+  const int qt = (blockIdx.x % q_blocks) * 128;
+  const long long ct = c_first + (long long)(blockIdx.x / q_blocks) * 128;
+  const float *ga[2], *gb[2];
+  stage_rows(q, qt, Q, dm.d, ga);
+  stage_rows(nodes, ct, N, dm.d, gb);
+  f32x4 acc[4][4];
+  TileF32::product<VEC>(ga, gb, dm, slabs, acc);
+  const long long c0 = ct + (wave & 1) * 64;
+  tile_epilogue(acc, qt + (wave >> 1) * 64, c0, Q, c_first + c_count, qb, head,
+                [&](int, int qrow) {
+                  GradRow st{lse[qrow], gscale[per_query ? qrow : 0] * inv_q, rank_target(batch, qrow, head), {0u, 0u},
+                             dS + (size_t)qrow * c_count - c_first};
+                  if (mask) {
+                    const long long w0 = (c0 - c_first) >> 5;
+                    const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                    if (w0 < mask_w) st.w[0] = mrow[w0];
+                    if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  }
+                  return st;
+                },
+                [&](long long col) { return cbias[col]; },
+                [&](const GradRow &st, int, int b, long long col, float sc_) {
+                  const bool out = (st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u;
+                  const float p = __expf(sc_ - st.lse) - (col == st.tgt ? 1.f : 0.f);
+                  st.out[col] = out ? 0.f : st.scale * p;
+                });
+}
+
+// the filter bits of one chunk of candidate columns (rank_mask_kernel with keep_target = 0, cut to [c_first, c_end))
+__global__ void chunk_mask_kernel(unsigned *__restrict__ mask, long long mask_w, const int *__restrict__ fq, const int *__restrict__ fn,
+                                  long long F, const long long *__restrict__ batch, int head, long long c_first, long long c_end) {
+  for (long long e = (long long)blockIdx.x * WG + threadIdx.x; e < F; e += (long long)gridDim.x * WG) {
+    const int q = fq[e];
+    const long long n = fn[e];
+    if (n >= c_first && n < c_end && n != rank_target(batch, q, head))
+      atomicOr(mask + (size_t)q * mask_w + ((n - c_first) >> 5), 1u << ((n - c_first) & 31));
+  }
 }
 
 // Merge pass, one wave per query: of the n_part lists of k keys the k largest, in k rounds -- round j takes the largest key below the
@@ -1059,4 +1215,105 @@ extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t 
   (void)n_rel;
   return topk_fused<TileBf16>({"distmult_topk_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
                                n_nodes, d, stream}, k, ids, scores);
+}
+
+// ------------------------------------------------------------------ 1-N softmax loss: entry points
+namespace {
+
+template <class Tile>
+int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore) {
+  if (int rc = strip_check(a, a.Q && (!lse || !tscore), "")) return rc;
+  if (a.Q == 0) return RGCN_OK;
+  StripCall<Tile> c;
+  auto too_many = [](int64_t) { return false; };            // the pairs are floats: no counter to overflow
+  if (int rc = strip_begin<Tile>(a, sizeof(float2), 0, too_many, "strips", c)) return rc;
+  float2 *part = static_cast<float2 *>(c.part);
+  const int Q = (int)a.Q;
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    constexpr bool V = decltype(vec)::value;
+    hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
+                       a.head);
+    hipLaunchKernelGGL((strip_lse_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
+                       c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+  });
+  hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float2 *)part, (int)(2 * c.n_strips), Q, lse);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+// the workspace of a gradient-cell call: query vectors | query-side bias terms | the filter bits of the chunk [Q][ceil(c_count / 32)]
+struct GradLayout { int64_t qv, qb, mask, total, mask_w; };
+
+inline GradLayout grad_layout(int64_t Q, int64_t c_count, int32_t d) {
+  GradLayout L;
+  L.mask_w = (c_count + 31) / 32;
+  L.qv = 0;
+  L.qb = L.qv + align16(Q * (int64_t)d * (int64_t)sizeof(float));
+  L.mask = L.qb + align16(2 * Q * (int64_t)sizeof(float));
+  L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
+  return L;
+}
+
+}  // namespace
+
+extern "C" int64_t rgcn_distmult_lse_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, sizeof(float2)).total;
+}
+
+extern "C" int rgcn_distmult_lse_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                     const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                     const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                     int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileF32>({"distmult_lse", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes, d,
+                             stream}, lse, tscore);
+}
+
+extern "C" int rgcn_distmult_lse_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                      const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                      int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileBf16>({"distmult_lse_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                              n_nodes, d, stream}, lse, tscore);
+}
+
+extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
+  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d).total;
+}
+
+extern "C" int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                              const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                              const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
+                                              int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                              int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  const StripArgs<float> a{"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes,
+                           d, stream};
+  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > n_nodes - c_count || mean_over < 1;
+  const float inv_q = 1.0f / (float)mean_over;
+  if (int rc = strip_check(a, bad_chunk || (Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
+  if (Q == 0) return RGCN_OK;
+  const int64_t qbl = (Q + 127) / 128, nwg = ((c_count + 127) / 128) * qbl;
+  if (nwg > INT32_MAX) { rgcn_set_error("distmult_softmax_grad: too many cells in one call; take a smaller chunk"); return RGCN_EUNSUPPORTED; }
+  const GradLayout L = grad_layout(Q, c_count, d);
+  char *ws = static_cast<char *>(workspace);
+  float *qv = reinterpret_cast<float *>(ws + L.qv), *qb = reinterpret_cast<float *>(ws + L.qb);
+  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const long long *b = reinterpret_cast<const long long *>(batch);
+  if (F) {
+    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
+    hipLaunchKernelGGL(chunk_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
+                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, (long long)c_first, (long long)(c_first + c_count));
+  }
+  launch_query<TileF32>(st, b, Q, head, nodes, rel, sbias, pbias, obias, qv, qb, d);
+  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
+  with_vec<TileF32>(nodes, d, [&](auto vec) {
+    hipLaunchKernelGGL((softmax_grad_kernel<decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const float *)qv, nodes,
+                       tile_dims<TileF32>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
+                       (int)Q, (long long)n_nodes, (long long)c_first, (long long)c_count, head, (int)qbl);
+  });
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
 }

@@ -5,6 +5,8 @@ experiments/predict_links.py (:19-228) without sacred.  Reads the reference's co
     python experiments/predict_links.py configs/rgcn/lp-WN18.yaml [--data DIR] [--epochs N]
 
 training.{epochs,graph_batch_size,sampling_method,negative_sampling.{sampling_rate,head_prob},optimiser.*}
+training.objective (an extension, absent in the reference): "negative-sampling" (default: the reference's sampled-negative BCE) or "1-n"
+(softmax cross-entropy of every sampled positive against ALL entities, tails and heads, unfiltered; configs/rgcn/lp-WN18-1n.yaml)
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""
@@ -37,6 +39,10 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     fused_eval: utils.misc.evaluate's `fused` (True: rank without the score matrix; None: only where that matrix would need chunks)."""
     dataset, training, encoder = cfg["dataset"], cfg["training"], cfg["encoder"]
     decoder, evaluation = cfg.get("decoder", {}), cfg.get("evaluation", {})
+    objective = training.get("objective", "negative-sampling")
+    if objective not in ("negative-sampling", "1-n"):
+        raise NotImplementedError(f"'{objective}' training objective has not been implemented!")
+    one_to_n = objective == "1-n"
     max_epochs = epochs or training.get("epochs", 5000)
     graph_batch_size = training.get("graph_batch_size")
     sampling_function = select_sampling(training.get("sampling_method", "uniform"))
@@ -116,21 +122,37 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
             else:
                 positives = sampling_function(train, sample_size=graph_batch_size, entities=n2i)
             positives = torch.as_tensor(positives, dtype=torch.long).to(device)
-            negatives = positives[:, None, :].expand(graph_batch_size, neg_sample_rate, 3).contiguous()
-            negatives = negative_sampling(negatives, num_nodes, head_corrupt_prob, device=device)
-            batch_idx = torch.cat([positives, negatives], dim=0)
-            train_lbl = torch.cat([torch.ones(graph_batch_size, device=device),
-                                   torch.zeros(graph_batch_size * neg_sample_rate, device=device)])
+            if one_to_n:                          # every entity is a candidate: nothing to draw, no labels
+                batch_idx, train_lbl = positives, torch.empty(0, device=device)
+            else:
+                batch_idx, train_lbl = corrupt(positives)
             graph = positives
             if edge_dropout > 0.0:                # self-loop dropout happens inside the layer
                 graph = graph[torch.randperm(graph.size(0), device=device)]
                 graph = graph[round((1 - edge_dropout) * graph.size(0)):, :]     # (keeps the edge_dropout share, as upstream)
         return graph, batch_idx, train_lbl
 
+    def corrupt(positives):
+        """the reference's batch: the positives, then neg_sample_rate corrupted copies of each, and their labels"""
+        negatives = positives[:, None, :].expand(graph_batch_size, neg_sample_rate, 3).contiguous()
+        negatives = negative_sampling(negatives, num_nodes, head_corrupt_prob, device=device)
+        batch_idx = torch.cat([positives, negatives], dim=0)
+        train_lbl = torch.cat([torch.ones(graph_batch_size, device=device),
+                               torch.zeros(graph_batch_size * neg_sample_rate, device=device)])
+        return batch_idx, train_lbl
+
+    def step_loss(graph, batch_idx, train_lbl):
+        if one_to_n:      # 1-N softmax: half the tail loss, half the head loss, unfiltered (static shapes: the captured step works)
+            x = model.encode(graph)
+            decoder_ = model.scoring_function
+            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False) + decoder_.softmax_loss(batch_idx, x, head=True))
+            return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
+        predictions, penalty = model(graph, batch_idx)
+        return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
+
     def train_step(graph, batch_idx, train_lbl):
         optimiser.zero_grad(set_to_none=False)
-        predictions, penalty = model(graph, batch_idx)
-        loss = bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
+        loss = step_loss(graph, batch_idx, train_lbl)
         loss.backward(gradient=unit_gradient(loss.device))      # (no ones_like() fill per step; MaskedCrossEntropy skips the multiplication)
         optimiser.step()
         return loss
@@ -185,8 +207,7 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
         else:
             optimiser.zero_grad()
             graph, batch_idx, train_lbl = sample_inputs()
-            predictions, penalty = model(graph, batch_idx)
-            loss = bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
+            loss = step_loss(graph, batch_idx, train_lbl)
             t2 = time.time()
             loss.backward(gradient=unit_gradient(loss.device))
             optimiser.step()

@@ -1079,15 +1079,18 @@ def basis_dcomps_csr(X, D, csr, R, B, d):
 G_TRANS_A, G_TRANS_B = 1, 2
 
 
-def gemm(A, B, bias=None, trans_a=False, trans_b=False, split_k=1):
+def gemm(A, B, bias=None, trans_a=False, trans_b=False, split_k=1, out=None):
     """C = op(A) @ op(B) (+ bias) on the matrix cores (rgcn_gemm_f32; fp32, exact FMA chains).  A: [M, K] or, trans_a,
-    stored [K, M]; B: [K, N] or, trans_b, stored [N, K]."""
+    stored [K, M]; B: [K, N] or, trans_b, stored [N, K].  out: a contiguous fp32 [M, N] to write C into (rows of a larger table, say)."""
     _req(A, "A"); _req(B, "B"); _req(bias, "bias")
     assert A.dim() == 2 and B.dim() == 2
     M, K = (A.shape[1], A.shape[0]) if trans_a else A.shape
     N = B.shape[0] if trans_b else B.shape[1]
     assert (B.shape[1] if trans_b else B.shape[0]) == K, f"gemm: inner dimensions {tuple(A.shape)} x {tuple(B.shape)}"
-    C = torch.empty((M, N), device=A.device, dtype=torch.float32)
+    if out is not None:
+        _req(out, "out")
+        assert out.shape == (M, N), f"gemm: out must be {(M, N)}"
+    C = out if out is not None else torch.empty((M, N), device=A.device, dtype=torch.float32)
     if M == 0 or N == 0:
         return C
     scratch = None
@@ -2361,3 +2364,107 @@ def distmult_topk(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k
                                                 _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, k, strips,
                                                 _dp(ws), _dp(ids), _dp(scores), N, rel.shape[0], d, _stream(dev)), "distmult_topk")
     return ids, scores
+
+
+# ----------------------------------------------------------------------------- 1-N softmax loss (an extension)
+def checked_queries(batch, N, n_rel, filt_q, filt_n, bf16):
+    """-> batch, its triples inside the tables and the filter entries inside [Q, N) (an entry out of range would set a bit outside the
+    mask).  Read back at once, as distmult_rank_fused does.  Under route deferred_checks = 1 an unfiltered call does not synchronise: one
+    device flag goes to the deferred queue and the triples are clamped into the tables meanwhile (the kernels do not range-check; the
+    IndexError arrives with a later call or check_deferred_errors()); inside a stream capture nothing is checked -- the captured step
+    was validated before.  Filter lists are always checked at once: a filtered step is an eager one."""
+    Q = batch.shape[0]
+    F = 0 if filt_q is None else filt_q.shape[0]
+    if not Q:
+        return batch
+    if F:
+        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
+            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    if _deferred_mode():
+        if torch.cuda.is_current_stream_capturing():
+            return batch
+        s, p, o = batch[:, 0], batch[:, 1], batch[:, 2]
+        bad = (batch.amin() < 0) | (s.amax() >= N) | (o.amax() >= N) | (p.amax() >= n_rel)
+        dev_check_err(bad.to(torch.int32).reshape(1), "1-N softmax loss triples (s, o < num_nodes, p < num_relations)", IndexError)
+        return torch.stack([s.clamp(0, N - 1), p.clamp(0, n_rel - 1), o.clamp(0, N - 1)], 1)
+    lo, hi = batch.amin(0), batch.amax(0)
+    if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < n_rel):
+        if bf16:
+            raise IndexError("triple index out of range")
+        raise AssertionError("triple index out of range")
+    return batch
+
+
+def _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, strips=0):
+    """the argument requirements of distmult_lse and distmult_softmax_grad (those distmult_rank_fused and distmult_topk state inline) -> (bf16, Q, N, d, F)"""
+    bf16 = nodes.dtype == torch.bfloat16
+    if bf16:
+        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
+    else:
+        _req(nodes, "nodes"); _req(rel, "relations")
+        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
+            _req(b, n)
+    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
+    Q, (N, d) = batch.shape[0], nodes.shape
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    assert rel.shape[1] == d, "relation and node embeddings differ in width"
+    assert (sbias is None) == (pbias is None) == (obias is None), "biases must be all set or all None"
+    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
+        "filt_q and filt_n: two int32 lists of one length, or neither"
+    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
+    return bf16, Q, N, d, (0 if filt_q is None else filt_q.shape[0])
+
+
+def lse_workspace_bytes(Q, N, d, strips=0, bf16=False):
+    """bytes of the log-sum-exp route's workspace (the fused evaluator's layout: query vectors, strip partials, filter mask); needs no
+    device; 0 for arguments the call refuses"""
+    return int(lib().rgcn_distmult_lse_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
+
+
+def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False):
+    """(lse, tscore) fp32 [Q]: lse[q] = log sum exp of the cells of distmult_score_all[_bf16] over every entity that is not on the int32
+    device lists (filt_q, filt_n) -- an entry on a query's own target is ignored, as in distmult_rank_fused --, tscore[q] = the target's
+    cell, without the [Q, N] score matrix.  The 1-N softmax loss of a query is lse - tscore.  fp32 or bf16 nodes (rel and biases fp32).
+    strips: as in distmult_rank_fused.  checked: `batch` went through checked_queries already (a caller that uses it again afterwards)."""
+    bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, strips)
+    if not checked:
+        batch = checked_queries(batch, N, rel.shape[0], filt_q if F else None, filt_n if F else None, bf16)
+    dev = nodes.device
+    lse = torch.empty(Q, device=dev, dtype=torch.float32)
+    tscore = torch.empty(Q, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    with _on(dev), _timed("lse_fused_bf16" if bf16 else "lse_fused"):
+        if bf16:
+            _check(lib().rgcn_distmult_lse_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                                _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips, _dp(ws), _dp(lse),
+                                                _dp(tscore), N, rel.shape[0], d, _stream(dev)), "distmult_lse_bf16")
+        else:
+            _check(lib().rgcn_distmult_lse_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                               _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips, _dp(ws), _dp(lse),
+                                               _dp(tscore), N, rel.shape[0], d, _stream(dev)), "distmult_lse")
+    return lse, tscore
+
+
+def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None):
+    """dS fp32 [Q, c_count]: the gradient cells of the 1-N softmax loss on the candidate columns [c_first, c_first + c_count),
+    scale_q (exp(s[q, c] - lse[q]) - [c == target_q]), filtered cells 0; scale_q = gscale / mean_over with gscale a device float [1] or
+    [Q] (never read back).  fp32 only.  lse: distmult_lse's of the same arguments.  The caller has range-checked the triples and the
+    lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to write into."""
+    bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n)
+    assert not bf16, "distmult_softmax_grad is fp32 only"
+    _req(lse, "lse"); _req(gscale, "gscale")
+    assert lse.shape == (Q,) and gscale.numel() in (1, Q), "lse [Q]; gscale [1] or [Q]"
+    assert c_first % 128 == 0 and c_count >= 1 and 0 <= c_first and c_first + c_count <= N, "a chunk starts on a multiple of 128 inside [0, N)"
+    dev = nodes.device
+    if out is None:
+        out = torch.empty(Q * c_count, device=dev, dtype=torch.float32)
+    _req(out, "out")
+    assert out.numel() >= Q * c_count
+    dS = out.view(-1)[:Q * c_count].view(Q, c_count)
+    ws = torch.empty(max(int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d)), 16), device=dev, dtype=torch.uint8)
+    with _on(dev), _timed("softmax_grad"):
+        _check(lib().rgcn_distmult_softmax_grad_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                                    _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
+                                                    1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over), c_first, c_count,
+                                                    _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad")
+    return dS

@@ -1304,6 +1304,121 @@ def _rows16(t):
         t.data_ptr() % 16 == 0
 
 
+SOFTMAX_CHUNK_BYTES = 1 << 30      # the backward's dS buffer per chunk of candidate columns: utils.misc._SCORE_BYTES, the evaluator's budget
+
+
+def softmax_chunk_plan(Q, N, chunk_bytes):
+    """[(c_first, c_count), ...]: the candidate columns [0, N) cut into the chunks of the 1-N softmax loss's backward.  Every c_first is
+    a multiple of 128 (the tile and mask-word alignment of the gradient-cell kernel), every chunk but the last a multiple of 128 wide with
+    Q * c_count * 4 <= chunk_bytes -- but never narrower than one tile column of 128 --, the last one ragged; one chunk when the whole
+    [Q, N] matrix fits the budget."""
+    assert Q >= 0 and N >= 1 and chunk_bytes >= 1
+    if 4 * Q * N <= chunk_bytes:
+        return [(0, N)]
+    per = max(128, chunk_bytes // (4 * Q) // 128 * 128)
+    return [(c, min(per, N - c)) for c in range(0, N, per)]
+
+
+class _DistMultSoftmaxLoss(torch.autograd.Function):
+    """loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q] on fp32 tables (bf16 tables: forward only).  Saves lse [Q] and the
+    inputs; the backward recomputes the product chunk by chunk (softmax_chunk_plan) into one reused [Q, c_count] buffer."""
+
+    @staticmethod
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes):
+        batch = batch.reshape(-1, 3).contiguous()
+        nodes, relations = dense(nodes), dense(relations)
+        # range-checked here, once, for the forward and the backward (under deferred checks: clamped, the error queued)
+        batch = _native.checked_queries(batch, nodes.shape[0], relations.shape[0], filt_q, filt_n, nodes.dtype == torch.bfloat16)
+        lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True)
+        ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse)
+        ctx.head, ctx.mean, ctx.chunk_bytes = bool(head), mean, chunk_bytes
+        loss = lse - tscore
+        return loss.mean() if mean else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse = ctx.saved_tensors
+        need_n, need_r = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        need_b = sbias is not None and any(ctx.needs_input_grad[4:7])
+        Q, (N, d), dev = batch.shape[0], nodes.shape, nodes.device
+        dn = dr = dsb = dpb = dob = None
+        if Q and (need_n or need_r or need_b):
+            if not _is_unit(g):
+                g = dense(g.to(torch.float32))
+            anchor, p = batch[:, 2 if ctx.head else 0], batch[:, 1]
+            qv = nodes[anchor] * rel[p]                                       # the query vectors, as the query kernel forms them
+            plan = softmax_chunk_plan(Q, N, ctx.chunk_bytes)
+            buf = torch.empty(Q * plan[0][1], device=dev, dtype=torch.float32)
+            dn = torch.empty(N, d, device=dev, dtype=torch.float32) if need_n else None
+            # the candidate-side bias gradient is dS^T times a column of ones: a product of its own into its own [N, 1] column (beside qv
+            # it would make the rows of dnodes d + 1 wide and cost a second [N, d] copy to take them apart)
+            ones = torch.ones(Q, 1, device=dev) if need_b else None
+            cand = torch.empty(N, 1, device=dev, dtype=torch.float32) if need_b else None
+            dqv = None
+            for c_first, c_count in plan:
+                dS = _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
+                                                   Q if ctx.mean else 1, c_first, c_count, out=buf)
+                # both products are skinny (d wide): K is cut into slices, summed in a fixed order, where the output tiles alone would
+                # leave most of the chip idle
+                if dn is not None:                                            # candidate side: every row written once, nothing accumulated
+                    _native.gemm(dS, qv, trans_a=True, split_k=_split_k(Q, c_count, d), out=dn[c_first:c_first + c_count])
+                if cand is not None:
+                    _native.gemm(dS, ones, trans_a=True, split_k=_split_k(Q, c_count, 1), out=cand[c_first:c_first + c_count])
+                if need_n or need_r:                                          # query side: the chunks' partials added in chunk order
+                    part = _native.gemm(dS, nodes[c_first:c_first + c_count], split_k=_split_k(c_count, Q, d))
+                    dqv = part if dqv is None else dqv.add_(part)
+            if need_n:
+                dn.index_add_(0, anchor, dqv * rel[p])
+            if need_r:
+                dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor])
+            if need_b:
+                cand = cand.view(N)
+                zeros = torch.zeros(N, device=dev)
+                dsb, dob = (cand, zeros) if ctx.head else (zeros, cand)
+                dpb = torch.zeros_like(pbias)
+        else:
+            dn = torch.zeros_like(nodes) if need_n else None
+            dr = torch.zeros_like(rel) if need_r else None
+            if need_b:
+                dsb, dpb, dob = torch.zeros_like(sbias), torch.zeros_like(pbias), torch.zeros_like(obias)
+        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None
+
+
+def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
+                          reduction="mean", strips=0, chunk_bytes=None):
+    """1-N softmax cross-entropy of DistMult (an extension: the reference trains on sampled negatives only).  For each triple of `batch`
+    (int64 [Q, 3]) every entity is scored as its head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- and
+        loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q],
+    `allowed` being every entity that is not on the int32 device lists (filt_q, filt_n); an entry on a query's own target is ignored (as in
+    distmult_rank_all), so the target is always in the sum.  Returns the mean over the queries, or the vector with reduction="none".
+    The [Q, N] logits never exist: the forward is one strip pass with a running (max, sum) per query (DESIGN.md 4.5) and keeps lse [Q];
+    the backward computes the product again in chunks of candidate columns (softmax_chunk_plan: Q * c_count * 4 <= chunk_bytes, default
+    SOFTMAX_CHUNK_BYTES) into one reused buffer dS and contracts each chunk on the matrix cores -- dnodes[chunk] = dS^T qv, every row
+    written once, and dqv += dS nodes[chunk], the chunks added in chunk order.  The one unordered sum of the route comes last:
+    dnodes[anchor_q] += dqv[q] * rel[p_q] and drel[p_q] += dqv[q] * nodes[anchor_q] are index_add_ (fp32 atomics over Q rows), so two
+    runs may differ in the last bits of those rows.  The query-side bias gradients (pbias, and obias if head else sbias) are
+    sum_n dS[q, n] = 0 in exact arithmetic and are returned as zeros.  strips: as in distmult_rank_all.
+    bf16 nodes (DESIGN.md 4.6): with nothing that requires grad the bf16 kernels run on the bf16 table -- a test-set cross-entropy --;
+    otherwise the table is widened to fp32 here, the fp32 route runs and autograd rounds dnodes once on the way back: the upcast policy,
+    CORRECTNESS ONLY (there is no native bf16 backward).  Relations and biases are fp32, or bf16 with bf16 nodes (widened here)."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    if chunk_bytes is None:
+        chunk_bytes = SOFTMAX_CHUNK_BYTES
+    assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
+    params = (nodes, relations, sbias, pbias, obias)
+    if nodes.dtype == torch.bfloat16:
+        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+        widen = lambda t: None if t is None else t.float()     # noqa: E731  (a no-op on fp32)
+        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
+            nodes = nodes.float()
+    return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
+                                      chunk_bytes)
+
+
 class _MaskedCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, row_label, lab_rows):
