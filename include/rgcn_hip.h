@@ -357,23 +357,27 @@ RGCN_API int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_pa
  * workgroup; one flush of global atomics at the end).
  *   rec       chunk records of rgcn_bwd_blk_prepare_f32 whose relation word is  rel | local << 16  (local = the relation's slot in its
  *             owner wave); inside a tile the chunks are grouped by owner wave
- *   own_ptr   [n_tiles * waves + 1]: own_ptr[tile * waves + w] = first chunk of wave w in the tile
+ *   own_ptr   [n_tiles * waves + 1]: own_ptr[tile * waves + w] = first chunk of wave w in the tile (read when group_ptr is NULL)
+ *   group_ptr, shared_rel   NULL, -1; or the SHARED form of the plan: [n_tiles * (waves + 1) + 1] with group_ptr[tile * (waves + 1) + w] = first
+ *             chunk of wave w, group `waves` of a tile = the chunks of relation shared_rel, which belong to no wave (local = units / waves - 1
+ *             in their relation word): every wave whose last slot names shared_rel in unit_rel takes them, two at a time, from a counter in
+ *             LDS after its own range; their sums leave the workgroup through one wave
  *   unit_rel  [units]: unit_rel[w * (units / waves) + local] = relation, -1 = unused slot
  * flags: RGCN_F_RELU; dbias as rgcn_bwd_blk_f32.  No hub pieces.  Sums in arrival order.  Same autograd duals of layers.py:293-301. */
 RGCN_API int32_t rgcn_bwd_own_waves(void);
 RGCN_API int32_t rgcn_bwd_own_units(void);
 RGCN_API int32_t rgcn_bwd_own_max_rows(void);
 RGCN_API int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_packed, float *dX, float *dW, const void *rec,
-                              const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
-                              int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
+                              const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
+                              int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
 /* rgcn_bwd_own_bf16: the same backward on bf16 storage (replaces layers.py:293-301's duals for a layer called with bf16 features):
  * G [n_src][16], X [n_dst][16] and dX [n_dst][16] are bf16 (uint16_t bit patterns).  G is gathered as 32-byte rows and widened; every product
  * and sum is fp32 (the dX tile fp64 in LDS), dX is rounded to bf16 once (round to nearest even, NaN stays NaN).  Wt_packed, dW and dbias stay
- * fp32.  Records, own_ptr, unit_rel and dbias as rgcn_bwd_own_f32; flags = 0 (no ReLU mask: the caller masks G); n_src < 2^26 (the records
+ * fp32.  Records, own_ptr, group_ptr / shared_rel, unit_rel and dbias as rgcn_bwd_own_f32; flags = 0 (no ReLU mask: the caller masks G); n_src < 2^26 (the records
  * address rows as src << 6). */
 RGCN_API int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float *Wt_packed, uint16_t *dX, float *dW, const void *rec,
-                               const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
-                               int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
+                               const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
+                               int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream);
 /* Soft-window plans (round 6), built on the device: the relation-tile plan of rgcn_spmm_blk_f32 / rgcn_bwd_own_f32 in the order those
  * kernels are fast on -- what replaces the reference's per-forward stack_matrices -> sum_sparse -> sparse COO pipeline (utils.py:143-166, :71-97;
  * layers.py:255-279) for them.  Messages (dst <- src, rel, val; alive may be NULL) are bucketed by (dst / tile_rows, rel), every bucket padded to a
@@ -387,7 +391,8 @@ RGCN_API int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float
  *                               (first chunk of every group).  own_waves = 0: a group is a tile (group_ptr = the tile pointer).  own_waves > 0
  *                               (rgcn_bwd_own_f32): a group is (tile, owner wave); relation r is cut into parts[r] units unit_base[r] .. , chunk j of a
  *                               bucket belongs to unit unit_base[r] + j % parts[r], owned by wave unit_owner[u] under the local number unit_local[u];
- *                               chunk_rel = rel | local << 16. */
+ *                               chunk_rel = rel | local << 16.  own_waves counts the GROUPS of a tile: the shared form of the owner plan
+ *                               passes the kernel's waves + 1 and gives the shared relation's one unit the owner `waves` (the last group). */
 RGCN_API int64_t rgcn_softwin_tmp_bytes(int64_t n);
 RGCN_API int rgcn_softwin_order(const int32_t *dst, const int32_t *src, const int32_t *rel, const uint8_t *alive, int64_t M, int64_t n_dst,
                                 int64_t n_src, int32_t R, int32_t tile_rows, uint64_t *keys, uint64_t *keys_sorted, int32_t *order,

@@ -26,6 +26,11 @@
 //
 // The chunk records are the block-tile kernel's (rgcn_bwd_blk_prepare_f32, 176 bytes); the relation word carries the local relation
 // number in its high half: rel | li << 16.  own_ptr[tile * NW + wave] = first chunk of the wave in the tile (n_tiles * NW + 1 entries).
+// Shared group (own_relations(shared=True)): the relation with the most messages -- S1: the self loops, 41 chunks per tile that gather the
+// tile's own rows -- belongs to no wave; its chunks are group NW of a tile (group_ptr, NW + 1 groups per tile) and go, two at a time, to
+// whichever wave is done with its own range, and the waves' sums of it leave the workgroup as ONE set of atomics.  S1: 0.4139 -> 0.4019 ms
+// per launch against that relation cut into two owned parts.  Cutting relations to level the waves does not pay: every part is one more
+// set of atomics per workgroup on the relation's 1 KiB of dW when the kernel ends (profiles/own_shared_*.txt).
 // No hub pieces: plans with hub tiles keep the block-tile kernel.
 #include <stdlib.h>
 #include <string.h>
@@ -73,8 +78,8 @@ size_t bwd_own_lds(int rows) { return (size_t)rows * 192 + (size_t)OWN_NW * BW_S
 template <bool RELU, int NW, int K, int ABL = 0, bool BF = false>
 __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     const float *__restrict__ G, const float *__restrict__ X, const float *__restrict__ Wtp, float *__restrict__ dX,
-    float *__restrict__ dWout, const char *__restrict__ rec, const int *__restrict__ own_ptr, int n_tiles, int tile_rows, int n_dst,
-    float *__restrict__ dbias, int n_src, const int *__restrict__ unit_rel) {
+    float *__restrict__ dWout, const char *__restrict__ rec, const int *__restrict__ gptr, int gstride, int shared_rel, int n_tiles,
+    int tile_rows, int n_dst, float *__restrict__ dbias, int n_src, const int *__restrict__ unit_rel) {
   constexpr int U = OWN_U, NT = 64 * NW;
   constexpr int TQ = (OWN_MAX_ROWS * 4 + NT - 1) / NT;            // float4 of a tile a thread carries / converts per tile, at most
   static_assert(K <= 9, "dw_add lists nine accumulator cases");
@@ -87,13 +92,34 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
   const double2 *dxd2 = reinterpret_cast<const double2 *>(lds);
   float4 *xt4 = reinterpret_cast<float4 *>(lds + xt_off);         // X tile [rows][16] floats
   float *xs = reinterpret_cast<float *>(lds + xs_off) + wave * BW_SCR2;
+  // The shared group (gstride = NW + 1 groups per tile, shared_rel >= 0): chunks of relation shared_rel that belong to no wave.  A wave whose
+  // last slot names that relation takes them U at a time from a counter in LDS (the 64 spare bytes behind the scratch) once its own range
+  // is done, so the waves reach the tile's barrier together; its sums sit in accumulator K - 1 (the chunks' local number).
+  int *ctr = reinterpret_cast<int *>(lds + xs_off + (unsigned)NW * BW_SCR2 * 4u);
+  const bool takes = shared_rel >= 0 && __builtin_amdgcn_readfirstlane(unit_rel[wave * K + K - 1]) == shared_rel;
+  auto take = [&]() {
+    int v = 0;
+    if (lane == 0) v = __hip_atomic_fetch_add(ctr, U, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(v);
+  };
+  // a tile's ranges: [a, b) this wave's own chunks, [sa, sb) the shared group (empty for a wave that does not take part)
+  auto ranges = [&](int tt, int &a, int &b, int &sa, int &sb) {
+    const int *g = gptr + (size_t)tt * gstride;
+    a = __builtin_amdgcn_readfirstlane(g[wave]);
+    b = __builtin_amdgcn_readfirstlane(g[wave + 1]);
+    sa = sb = 0;
+    if (takes) {
+      sa = __builtin_amdgcn_readfirstlane(g[NW]);
+      sb = __builtin_amdgcn_readfirstlane(g[NW + 1]);
+    }
+  };
 
   int t = blockIdx.x;
   int row0 = t * tile_rows;
   int nrows = min(tile_rows, n_dst - row0);
-  int c0 = own_ptr[(size_t)t * NW + wave], c1 = own_ptr[(size_t)t * NW + wave + 1];
-  c0 = __builtin_amdgcn_readfirstlane(c0);
-  c1 = __builtin_amdgcn_readfirstlane(c1);
+  int c0, c1, s0, s1;
+  ranges(t, c0, c1, s0, s1);
+  if (tid == 0) lds_st(ctr, 0);
   float4 gs = make_float4(0.f, 0.f, 0.f, 0.f);
   const long long g_n4 = dbias ? (long long)n_src * 4 : 0, g_step = (long long)gridDim.x * NT;
   long long g_i = (long long)blockIdx.x * NT + tid;
@@ -146,8 +172,16 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
   if (c0 < c1) request_idx(c0, c1 - 1);
 
   for (;;) {
-    const int last = c1 - 1;
-    for (int c = c0; c < c1; c += U) {
+    // the wave's pairs of this tile: its own range (the first pair was requested a tile ago), then what the counter deals it
+    int c = c0, last = c1 - 1;
+    bool sh = false;
+    if (c > last && s0 < s1) {
+      sh = true;
+      c = s0 + take();
+      last = s1 - 1;
+      if (c <= last) request_idx(c, last);
+    }
+    while (c <= last) {
       unsigned w0_[U];
       uint2 rw_[U];
       float v_[U];
@@ -174,7 +208,17 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
         w_[j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(Wtp) + (size_t)(hd_[j] & 0xFFFF) * 1024 + w_lane);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (c + U < c1) request_idx(c + U, last);
+      {     // the pair after this one, requested a trip ahead: the next of the own range, else the next the counter hands out
+        int cn = c + U, lastn = last;
+        if (sh || (cn > last && s0 < s1)) {
+          sh = true;
+          cn = s0 + take();
+          lastn = s1 - 1;
+        }
+        if (cn <= lastn) request_idx(cn, lastn);
+        c = cn;
+        last = lastn;
+      }
       __builtin_amdgcn_sched_barrier(0);
       if (ABL & 16) {
 #pragma unroll
@@ -242,15 +286,14 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     }
     // the next tile of this workgroup: its X rows, this wave's first chunks and one float4 of G (bias gradient) are requested before the barrier
     const int tn = t + (int)gridDim.x;
-    int c0n = 0, c1n = 0, row0n = 0, nrn = 0;
+    int c0n = 0, c1n = 0, s0n = 0, s1n = 0, row0n = 0, nrn = 0;
     float4 xn[TQ];
 #pragma unroll
     for (int q = 0; q < TQ; ++q) xn[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tn < n_tiles) {
       row0n = tn * tile_rows;
       nrn = min(tile_rows, n_dst - row0n);
-      c0n = __builtin_amdgcn_readfirstlane(own_ptr[(size_t)tn * NW + wave]);
-      c1n = __builtin_amdgcn_readfirstlane(own_ptr[(size_t)tn * NW + wave + 1]);
+      ranges(tn, c0n, c1n, s0n, s1n);
 #pragma unroll
       for (int q = 0; q < TQ; ++q)
         if (tid + q * NT < nrn * 4) {
@@ -289,6 +332,7 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       }
     }
     if (tn >= n_tiles) break;
+    if (tid == 0) lds_st(ctr, 0);                                  // (between the barriers: nobody takes from it)
 #pragma unroll
     for (int q = 0; q < TQ; ++q) {
       const int idx = tid + q * NT;
@@ -300,7 +344,7 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       }
     }
     lds_barrier();                                                 // the next tile is installed (nobody waits for the dX stores)
-    t = tn; row0 = row0n; nrows = nrn; c0 = c0n; c1 = c1n;
+    t = tn; row0 = row0n; nrows = nrn; c0 = c0n; c1 = c1n; s0 = s0n; s1 = s1n;
   }
   if (dbias) {
     for (; g_i < g_n4; g_i += g_step) {
@@ -325,10 +369,25 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     }
   }
   // the wave's accumulators leave the CU once.  D fragment: lane 16k + m, element e = row 4k + e (input feature), column m
+  if (shared_rel >= 0) {     // the shared relation's NW accumulators: summed through the waves' scratch, one wave's atomics for the workgroup
+    __syncthreads();                                               // (every wave is done with its scratch)
+    *reinterpret_cast<f32x4 *>(xs + 4 * lane) = takes ? accw[K - 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    if (wave == 0) {
+      const float *all = reinterpret_cast<const float *>(lds + xs_off) + 4 * lane;
+      f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = 0; i < NW; ++i) a += *reinterpret_cast<const f32x4 *>(all + i * BW_SCR2);
+      float *o = dWout + (size_t)shared_rel * 256 + (4 * k) * 16 + m;
+      atomicAdd(o, a[0]);
+      atomicAdd(o + 16, a[1]);
+      atomicAdd(o + 32, a[2]);
+      atomicAdd(o + 48, a[3]);
+    }
+  }
 #pragma unroll
   for (int li = 0; li < K; ++li) {
     const int r = __builtin_amdgcn_readfirstlane(unit_rel[wave * K + li]);
-    if (r >= 0) {
+    if (r >= 0 && !(takes && li == K - 1)) {
       float *o = dWout + (size_t)r * 256 + (4 * k) * 16 + m;
       atomicAdd(o, accw[li][0]);
       atomicAdd(o + 16, accw[li][1]);
@@ -346,11 +405,18 @@ extern "C" int32_t rgcn_bwd_own_waves(void) { return OWN_NW; }
 extern "C" int32_t rgcn_bwd_own_units(void) { return OWN_NW * OWN_K; }
 extern "C" int32_t rgcn_bwd_own_max_rows(void) { return OWN_MAX_ROWS; }
 
+// group_ptr / shared_rel of the two entries: the plan's pointer array with OWN_NW + 1 groups per tile and the shared relation, or NULL / -1
+// (the kernel then walks own_ptr, OWN_NW groups per tile, and there is no shared group)
+static bool own_groups_ok(const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, int64_t n_tiles, int32_t R) {
+  if (!group_ptr) return own_ptr && shared_rel < 0;
+  return shared_rel >= 0 && shared_rel < R && n_tiles * (int64_t)(OWN_NW + 1) < INT32_MAX;
+}
+
 extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_packed, float *dX, float *dW, const void *rec,
-                                const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
-                                int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
-  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !own_ptr || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
-      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX) {
+                                const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
+                                int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
+  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
+      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || !own_groups_ok(own_ptr, group_ptr, shared_rel, n_tiles, R)) {
     rgcn_set_error("bwd_own: bad argument");
     return RGCN_EINVAL;
   }
@@ -358,7 +424,10 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
     rgcn_set_error("bwd_own: tiles of at most %d rows (got %d)", rgcn_bwd_own_max_rows(), tile_rows);
     return RGCN_EUNSUPPORTED;
   }
-  if (dbias && (n_src <= 0 || n_src >= (int64_t(1) << 29))) { rgcn_set_error("bwd_own: dbias needs 0 < n_src < 2^29"); return RGCN_EINVAL; }
+  if (n_src <= 0 || n_src >= (int64_t(1) << 26)) {
+    rgcn_set_error("bwd_own: the records address G rows as src << 6 in 32 bits: 0 < n_src < 2^26");
+    return RGCN_EINVAL;
+  }
   hipStream_t st = (hipStream_t)stream;
   int dev = 0, n_cu = 0;
   HIP_TRY(launch_device(&dev, &n_cu));
@@ -369,8 +438,8 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
     constexpr auto kern = decltype(k)::value;
     hipError_t e = allow_lds<kern>(dev, lds, OWN_LDS_MAX);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, G, X, Wt_packed, dX, dW, static_cast<const char *>(rec), own_ptr, (int)n_tiles,
-                       tile_rows, (int)n_dst, dbias, (int)n_src, unit_rel);
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, G, X, Wt_packed, dX, dW, static_cast<const char *>(rec), group_ptr ? group_ptr : own_ptr,
+                       group_ptr ? OWN_NW + 1 : OWN_NW, group_ptr ? shared_rel : -1, (int)n_tiles, tile_rows, (int)n_dst, dbias, (int)n_src, unit_rel);
     return hipGetLastError();
   };
 #ifdef RGCN_ABLATIONS
@@ -389,10 +458,11 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
 }
 
 extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float *Wt_packed, uint16_t *dX, float *dW, const void *rec,
-                                 const int32_t *own_ptr, const int32_t *unit_rel, int64_t n_tiles, int32_t tile_rows, int64_t n_dst,
-                                 int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
-  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !own_ptr || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
-      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || n_src <= 0 || n_src >= (int64_t(1) << 26) || flags != 0) {
+                                 const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
+                                 int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
+  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
+      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || n_src <= 0 || n_src >= (int64_t(1) << 26) || flags != 0 ||
+      !own_groups_ok(own_ptr, group_ptr, shared_rel, n_tiles, R)) {
     rgcn_set_error("bwd_own_bf16: bad argument (the records address G rows as src << 6 in 32 bits: n_src < 2^26; no flags)");
     return RGCN_EINVAL;
   }
@@ -411,8 +481,8 @@ extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const flo
     hipError_t e = allow_lds<kern>(dev, lds, OWN_LDS_MAX);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * OWN_NW), lds, st, reinterpret_cast<const float *>(G), reinterpret_cast<const float *>(X),
-                       Wt_packed, reinterpret_cast<float *>(dX), dW, static_cast<const char *>(rec), own_ptr, (int)n_tiles, tile_rows, (int)n_dst,
-                       dbias, (int)n_src, unit_rel);
+                       Wt_packed, reinterpret_cast<float *>(dX), dW, static_cast<const char *>(rec), group_ptr ? group_ptr : own_ptr,
+                       group_ptr ? OWN_NW + 1 : OWN_NW, group_ptr ? shared_rel : -1, (int)n_tiles, tile_rows, (int)n_dst, dbias, (int)n_src, unit_rel);
     return hipGetLastError();
   };
   HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>>));

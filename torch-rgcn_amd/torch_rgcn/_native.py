@@ -493,25 +493,58 @@ def build_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_ro
     return p
 
 
-def own_relations(counts, n_waves, per_wave):
-    """relation -> owner waves for the relation-owner backward (rgcn_bwd_own_f32).  The unit of ownership is a PART of a relation: a
-    relation much larger than a wave's fair share (the self-loop relation; the one relation of a graph with few of them) is cut into parts,
-    part q takes the relation's chunks q, q + parts, ... of every (tile, relation) bucket; every part has its own accumulator and they all
-    leave the CU into the same dW_r.  Parts are split greedily (largest part first) until no part exceeds half a wave's fair share or the
-    n_waves * per_wave slots are used up, then packed onto the waves by longest-processing-time, at most per_wave per wave.
-    -> (parts[R], unit_base[R], owner[U], local[U], unit_rel[n_waves * per_wave] (-1: unused), max load / mean load), U = sum(parts);
-    None when there are more relations than slots."""
-    import heapq
-    counts = np.asarray(counts, dtype=np.int64)
+def _own_pack(counts, parts, n_waves, per_wave, rounds):
+    """own_relations' second half: the units of `parts` onto the waves by longest-processing-time.  rounds: [(relations, cap)] -- the units
+    of these relations are dealt, largest first, to the least loaded wave that holds fewer than cap units.  -> (own_relations' six values,
+    the waves' loads)"""
     R = len(counts)
-    slots = n_waves * per_wave
-    if R > slots:
+    unit_base = np.cumsum(parts) - parts
+    U = int(parts.sum())
+    usize = np.concatenate([np.full(parts[r], counts[r] / parts[r]) for r in range(R)]) if R else np.zeros(0)
+    urel = np.repeat(np.arange(R), parts)
+    load, used = [0.0] * n_waves, [0] * n_waves
+    owner, local = np.zeros(U, np.int64), np.zeros(U, np.int64)
+    unit_rel = np.full(n_waves * per_wave, -1, np.int32)
+    for rels, cap in rounds:
+        units = [u for r in rels for u in range(unit_base[r], unit_base[r] + parts[r])]
+        for u in sorted(units, key=lambda u: (-usize[u], u)):
+            w = min((i for i in range(n_waves) if used[i] < cap), key=lambda i: (load[i], i))
+            owner[u], local[u] = w, used[w]
+            unit_rel[w * per_wave + used[w]] = urel[u]
+            used[w] += 1
+            load[w] += usize[u]
+    mean = max(1.0, float(sum(load)) / n_waves)
+    return (parts, unit_base, owner, local, unit_rel, max(load) / mean), load
+
+
+def _own_level_parts(counts, n_waves, per_wave):
+    """own_relations(level=True): the layout in which every wave holds the same number of whole relations and the same fraction of every
+    relation that is cut -- (parts[R], rounds for _own_pack) or None where it does not exist or does not fit the slots.  The relation with
+    the most messages is cut in n_waves parts; of the others, n_waves * q stay whole (q each) and the L largest are cut in n_waves / L
+    parts, one part per wave: q + (L > 0) + 1 units per wave (S1, 101 relations on 16 x 8: 6 + 1 + 1)."""
+    R = len(counts)
+    if R < 1 or n_waves < 1:
+        return None
+    order = sorted(range(R), key=lambda r: (-int(counts[r]), r))
+    q, L = divmod(R - 1, n_waves)
+    if (L and n_waves % L) or q + (1 if L else 0) + 1 > per_wave:
         return None
     parts = np.ones(R, np.int64)
+    parts[order[0]] = n_waves
+    cut, whole = order[1:1 + L], order[1 + L:]
+    for r in cut:
+        parts[r] = n_waves // L
+    return parts, [(whole, q), (cut, q + 1), (order[:1], q + (1 if L else 0) + 1)]
+
+
+def _own_split(counts, rels, parts, n_waves, slots):
+    """own_relations' first half on the relations `rels`: the largest part is cut once more while it exceeds half a wave's fair share of
+    all messages and the units stay within `slots`"""
+    import heapq
     target = max(1.0, float(counts.sum()) / n_waves)
-    heap = [(-float(counts[r]), r) for r in range(R)]
+    heap = [(-float(counts[r]), r) for r in rels]
     heapq.heapify(heap)
-    units = R
+    units = len(heap)
     while units < slots and heap:
         size, r = heap[0]
         if -size <= 0.5 * target:
@@ -519,34 +552,116 @@ def own_relations(counts, n_waves, per_wave):
         parts[r] += 1
         units += 1
         heapq.heapreplace(heap, (-float(counts[r]) / parts[r], r))
-    unit_base = np.cumsum(parts) - parts
-    U = int(parts.sum())
-    usize = np.concatenate([np.full(parts[r], counts[r] / parts[r]) for r in range(R)]) if R else np.zeros(0)
-    urel = np.repeat(np.arange(R), parts)
-    load, used = [0.0] * n_waves, [0] * n_waves
-    owner, local = np.zeros(U, np.int64), np.zeros(U, np.int64)
-    unit_rel = np.full(slots, -1, np.int32)
-    for u in sorted(range(U), key=lambda u: (-usize[u], u)):
-        w = min((i for i in range(n_waves) if used[i] < per_wave), key=lambda i: (load[i], i))
-        owner[u], local[u] = w, used[w]
-        unit_rel[w * per_wave + used[w]] = urel[u]
-        used[w] += 1
-        load[w] += usize[u]
-    mean = max(1.0, float(sum(load)) / n_waves)
-    return parts, unit_base, owner, local, unit_rel, max(load) / mean
+    return parts
 
 
-def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves=0, own_per_wave=0):
+def _own_shared(counts, n_waves, per_wave, level):
+    """own_relations(shared=True): the relation with the most messages belongs to NO wave -- its chunks are one more group per tile, dealt
+    at run time -- and every wave that has its last slot free keeps an accumulator for it there (local number per_wave - 1).  The other
+    relations are packed as ever onto the slots before it (where they need more than per_wave - 1 slots per wave they stay whole and the
+    waves with a full set do not take shared chunks; level: in the level layout of _own_level_parts where that leaves the busiest wave
+    less).  None where no wave has a slot left for it.  The balance figure takes the shared messages as dealt to the least loaded waves.
+    S1: the 100 other relations stay whole, 7 on four waves and 6 on twelve, and all sixteen take self-loop chunks."""
+    R = len(counts)
+    big = min(range(R), key=lambda r: (-int(counts[r]), r))
+    others = [r for r in range(R) if r != big]
+    if counts[big] <= 0 or len(others) >= n_waves * per_wave:
+        return None
+    roomy = len(others) <= n_waves * (per_wave - 1)
+    cap = per_wave - 1 if roomy else per_wave
+    parts = _own_split(counts, others, np.ones(R, np.int64), n_waves, n_waves * cap if roomy else 0)
+    packed, load = _own_pack(counts, parts, n_waves, per_wave, [(others, cap)])
+    q, L = divmod(len(others), n_waves)
+    if level and (not L or n_waves % L == 0) and q + (1 if L else 0) <= per_wave - 1:
+        order = sorted(others, key=lambda r: (-int(counts[r]), r))
+        parts_lv = np.ones(R, np.int64)
+        for r in order[:L]:
+            parts_lv[r] = n_waves // L
+        packed_lv, load_lv = _own_pack(counts, parts_lv, n_waves, per_wave, [(order[L:], q), (order[:L], q + 1)])
+        if max(load_lv) < max(load):
+            packed, load = packed_lv, load_lv
+    parts, unit_base, owner, local, unit_rel, _ = packed
+    owner[unit_base[big]], local[unit_base[big]] = n_waves, per_wave - 1
+    takers = [w for w in range(n_waves) if unit_rel[w * per_wave + per_wave - 1] < 0]
+    if not takers:
+        return None
+    for w in takers:
+        unit_rel[w * per_wave + per_wave - 1] = big
+    fill = sorted(load[w] for w in takers)         # the shared messages fill the takers up from the least loaded one
+    left, level = float(counts[big]), float(fill[0])
+    for i in range(len(fill)):
+        nxt = float(fill[i + 1]) if i + 1 < len(fill) else float("inf")
+        if left <= (nxt - level) * (i + 1):
+            level += left / (i + 1)
+            break
+        left -= (nxt - level) * (i + 1)
+        level = nxt
+    mean = max(1.0, float(counts.sum()) / n_waves)
+    return parts, unit_base, owner, local, unit_rel, max(max(load), level) / mean, (big, per_wave - 1)
+
+
+def own_relations(counts, n_waves, per_wave, level=False, shared=False):
+    """relation -> owner waves for the relation-owner backward (rgcn_bwd_own_f32).  The unit of ownership is a PART of a relation: a
+    relation much larger than a wave's fair share (the self-loop relation; the one relation of a graph with few of them) is cut into parts,
+    part q takes the relation's chunks q, q + parts, ... of every (tile, relation) bucket; every part has its own accumulator and they all
+    leave the CU into the same dW_r.  Parts are split greedily (largest part first) until no part exceeds half a wave's fair share or the
+    n_waves * per_wave slots are used up, then packed onto the waves by longest-processing-time, at most per_wave per wave.
+    level: splitting goes on while the busiest wave's load drops and slots remain -- the level layout of _own_level_parts where it fits
+    the slots and its busiest wave holds less than the packing above gives it, else that packing, unchanged.  Every part of a relation
+    is one more set of atomics per workgroup on that relation's 1 KiB of dW when the kernel ends, and that costs more than level waves
+    gain: S1 +0.07 ms per launch with the self loops in 16 parts, +0.016 ms with four relations in 4 parts.  graph.win_plan
+    does not ask for it.
+    shared: a seventh value, (shared relation, its local number) of _own_shared's form -- the shared relation's one unit has owner n_waves --
+    or None where that form does not exist (the other six values are then those of shared=False).
+    -> (parts[R], unit_base[R], owner[U], local[U], unit_rel[n_waves * per_wave] (-1: unused), max load / mean load), U = sum(parts);
+    None when there are more relations than slots."""
+    counts = np.asarray(counts, dtype=np.int64)
+    R = len(counts)
+    slots = n_waves * per_wave
+    if R > slots:
+        return None
+    if shared:
+        sh = _own_shared(counts, n_waves, per_wave, level)
+        if sh is not None:
+            return sh
+    parts = _own_split(counts, range(R), np.ones(R, np.int64), n_waves, slots)
+    packed, load = _own_pack(counts, parts, n_waves, per_wave, [(range(R), per_wave)])
+    lv = _own_level_parts(counts, n_waves, per_wave) if level else None
+    if lv is not None:
+        packed_lv, load_lv = _own_pack(counts, lv[0], n_waves, per_wave, lv[1])
+        if max(load_lv) < max(load):
+            packed = packed_lv
+    return packed + (None,) if shared else packed
+
+
+def _own_plan_fields(p, own, group_ptr, own_waves, own_per_wave, groups):
+    """the owner fields of a soft-window plan from own_relations' answer and the pointer array of its `groups` groups per tile.  Shared form
+    (groups = own_waves + 1: the shared relation's chunks are the last group of every tile): group_ptr is what the kernel walks; own_ptr
+    keeps n_tiles * own_waves + 1 entries (a tile's last wave runs to the end of the tile there: its range includes the shared one) and
+    shared_ptr[tile] = (first, end) of the shared range."""
+    p.unit_rel = torch.from_numpy(own[4]).to(group_ptr.device)
+    p.own_waves, p.own_per_wave, p.own_balance = own_waves, own_per_wave, float(own[5])
+    p.group_ptr, p.shared_ptr, p.shared_rel, p.shared_local = None, None, -1, -1
+    if groups == own_waves:
+        p.own_ptr = group_ptr
+        return
+    p.group_ptr = group_ptr
+    tiles = group_ptr[:-1].view(p.n_tiles, groups)
+    p.own_ptr = torch.cat([tiles[:, :own_waves].reshape(-1), group_ptr[-1:]]).contiguous()
+    p.shared_ptr = torch.stack([tiles[:, own_waves], group_ptr[groups::groups]], 1).contiguous()
+    p.shared_rel, p.shared_local = int(own[6][0]), int(own[6][1])
+
+
+def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves=0, own_per_wave=0, own_level=False, own_shared=False):
     """build_softwin_plan through the C ABI (rgcn_softwin_order / rgcn_softwin_fill: two rocPRIM radix sorts, a histogram, three scans, four small
     kernels): the form the layers use on the GPU.  Two host reads (m_pad / live messages / the relations' message counts; nothing else)."""
     dev = dst.device
     M = dst.shape[0]
     n_tiles = (n_dst + tile_rows - 1) // tile_rows
     nbk = n_tiles * num_rels
-    n_groups = n_tiles * max(own_waves, 1)
     L = lib()
     # (the chunks sorted in the second step number at most M / 16 + one per non-empty bucket)
-    tmp_bytes = int(L.rgcn_softwin_tmp_bytes(max(M, nbk + 1, n_groups + 1, M // CHUNK + min(nbk, M) + 1)))
+    tmp_bytes = int(L.rgcn_softwin_tmp_bytes(max(M, nbk + 1, n_tiles * (own_waves + 1) + 1, M // CHUNK + min(nbk, M) + 1)))
     tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
     keys = torch.empty(2 * max(M, 1), dtype=torch.int64, device=dev)
     order = torch.empty(2 * max(M, 1), dtype=torch.int32, device=dev)
@@ -560,9 +675,11 @@ def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels,
     m_pad, n_live, max_cnt = int(host[0]), int(host[1]), int(host[2])
     own = None
     if own_waves:
-        own = own_relations(host[3:], own_waves, own_per_wave)
+        own = own_relations(host[3:], own_waves, own_per_wave, own_level, own_shared)
         if own is None:
             return None
+    groups = own_waves + 1 if own is not None and own_shared and own[6] is not None else max(own_waves, 1)     # groups of chunks per tile
+    n_groups = n_tiles * groups
     n_chunks = m_pad // CHUNK
     p = BuiltPlan()
     p.device = dev
@@ -582,18 +699,16 @@ def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels,
     nc1, mp1 = max(n_chunks, 1), max(m_pad, 1)
     with _on(dev):
         _check(L.rgcn_softwin_fill(_dp(dst), _dp(src), _dp(val), _dp(keys[max(M, 1):]), _dp(order[max(M, 1):]), n_live, n_dst, n_src, num_rels, tile_rows,
-                                   _dp(bucket_base), _dp(bucket_first), m_pad, _dp(tabs[0]), _dp(tabs[1]), _dp(tabs[2]), _dp(tabs[3]), own_waves,
+                                   _dp(bucket_base), _dp(bucket_first), m_pad, _dp(tabs[0]), _dp(tabs[1]), _dp(tabs[2]), _dp(tabs[3]), groups if own_waves else 0,
                                    _dp(stage[:mp1]), _dp(stage[mp1:]), _dp(stage_val), _dp(ckeys[:nc1]), _dp(ckeys[nc1:]), _dp(cidx[:nc1]),
                                    _dp(cidx[nc1:]), _dp(crel), _dp(group_cnt), _dp(p.src), _dp(p.dst), _dp(p.val), _dp(p.chunk_rel), _dp(group_ptr),
                                    _dp(tmp), tmp_bytes, _stream(dev)), "softwin_fill")
-    p.tile_ptr = group_ptr[::max(own_waves, 1)].contiguous()
+    p.tile_ptr = group_ptr[::groups].contiguous()
     p.run_ptr = torch.zeros(n_tiles * (num_rels + 1), dtype=torch.int32, device=dev)
     p.run_ptr[0::num_rels + 1] = p.tile_ptr[:-1]
     p.run_ptr[num_rels::num_rels + 1] = p.tile_ptr[1:]
     if own is not None:
-        p.own_ptr = group_ptr
-        p.unit_rel = torch.from_numpy(own[4]).to(dev)
-        p.own_waves, p.own_per_wave, p.own_balance = own_waves, own_per_wave, float(own[5])
+        _own_plan_fields(p, own, group_ptr, own_waves, own_per_wave, groups)
     p.pack, p.aux = None, None
     p.soft_windows = True
     p.units_host = np.zeros((0, 4), np.int32)      # (not None: _blk_units cuts hub tiles into pieces from tile_ptr)
@@ -603,7 +718,7 @@ def build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels,
     return p
 
 
-def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves=0, own_per_wave=0):
+def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves=0, own_per_wave=0, own_level=False, own_shared=False):
     """Plan of tall workgroup-owned tiles for the block-tile kernels (rgcn_spmm_blk_f32, rgcn_bwd_own_f32) in SOFT-WINDOW order (round 6):
 
       * inside a (tile, relation) bucket the slots are sorted by SOURCE row -- the block-tile kernels add with ds_add_f64 and the chunk
@@ -620,7 +735,9 @@ def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_r
     own_waves waves (own_relations: LPT over the message counts, at most own_per_wave units per wave); a tile's chunks are grouped by owner
     wave, each wave's chunks ordered by first source: own_ptr[tile * own_waves + wave] = the wave's first chunk; chunk_rel carries the unit's
     local number in its high half (rel | local << 16); unit_rel[wave * own_per_wave + local] = relation.  None when the relations do not
-    fit the slots.
+    fit the slots.  own_level, own_shared: own_relations(level=..., shared=...) -- graph.win_plan asks for the shared form; in it
+    the shared relation's chunks are one more group behind the own_waves owned groups of every tile (_own_plan_fields: group_ptr,
+    shared_ptr), dealt to the waves at run time, and their relation word carries the shared local number.
 
     On the GPU this is build_softwin_plan_device (the C ABI: rgcn_softwin_order / rgcn_softwin_fill); the body below is the same procedure in
     torch ops (two sorts, a histogram, two scans) -- CPU tensors (tests/test_softwin_plan.py checks the invariants on it) and
@@ -628,7 +745,7 @@ def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_r
     block-tile kernels read -- and there is no packed slot array."""
     dev = dst.device
     if dev.type == "cuda" and routes.get("softwin_build", "device") != "torch":
-        return build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves, own_per_wave)
+        return build_softwin_plan_device(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_rows, own_waves, own_per_wave, own_level, own_shared)
     M = dst.shape[0]
     n_tiles = (n_dst + tile_rows - 1) // tile_rows
     nbk = n_tiles * num_rels
@@ -638,7 +755,8 @@ def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_r
     key = bucket * n_src + s64
     if live is not None:
         key = torch.where(live, key, torch.full_like(key, nbk * n_src))       # dropped messages sort behind everything
-    perm = torch.argsort(key)
+    stable = bool(own_level or own_shared)      # (ties as the device builder's radix sorts leave them: by position)
+    perm = torch.argsort(key, stable=stable)
     n_live = M if live is None else int(live.sum().item())
     perm = perm[:n_live]
     bs = bucket[perm]
@@ -658,18 +776,19 @@ def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_r
     own = None
     if own_waves:
         live_rel = r64 if live is None else r64[live]
-        own = own_relations(torch.bincount(live_rel, minlength=num_rels).cpu().numpy(), own_waves, own_per_wave)
+        own = own_relations(torch.bincount(live_rel, minlength=num_rels).cpu().numpy(), own_waves, own_per_wave, own_level, own_shared)
         if own is None:
             return None
+        groups = own_waves + 1 if own_shared and own[6] is not None else own_waves
         parts_t, ubase_t = torch.from_numpy(own[0]).to(dev), torch.from_numpy(own[1]).to(dev)
         owner_t, local_t = torch.from_numpy(own[2]).to(dev), torch.from_numpy(own[3]).to(dev)
         crel0 = cb % num_rels
         first_chunk = torch.cumsum(padded // CHUNK, 0) - padded // CHUNK          # first chunk of every bucket (bucket-major layout)
         cunit = ubase_t[crel0] + (torch.arange(n_chunks, device=dev) - first_chunk[cb]) % parts_t[crel0]      # chunk j of its bucket -> part j % parts
-        cgroup = ctile * own_waves + owner_t[cunit]                             # (tile, owner wave) of every chunk
+        cgroup = ctile * groups + owner_t[cunit]                                # (tile, owner wave) of every chunk
     else:
         cgroup = ctile
-    cperm = torch.argsort(cgroup * n_src + S[:m_pad:CHUNK].long())             # inside a tile (a wave's share of it): by the chunk's first source (a real slot)
+    cperm = torch.argsort(cgroup * n_src + S[:m_pad:CHUNK].long(), stable=stable)             # inside a tile (a wave's share of it): by the chunk's first source (a real slot)
     idx = (cperm[:, None] * CHUNK + torch.arange(CHUNK, device=dev)[None, :]).reshape(-1)
     p = BuiltPlan()
     p.device = dev
@@ -682,10 +801,9 @@ def build_softwin_plan(dst, src, rel, val, alive, n_dst, n_src, num_rels, tile_r
     crel = cb % num_rels
     if own is not None:
         crel = crel | (local_t[cunit] << 16)
-        gcnt = torch.bincount(cgroup, minlength=n_tiles * own_waves)
-        p.own_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(gcnt, 0)]).to(torch.int32)
-        p.unit_rel = torch.from_numpy(own[4]).to(dev)
-        p.own_waves, p.own_per_wave, p.own_balance = own_waves, own_per_wave, float(own[5])
+        gcnt = torch.bincount(cgroup, minlength=n_tiles * groups)
+        group_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(gcnt, 0)]).to(torch.int32)
+        _own_plan_fields(p, own, group_ptr, own_waves, own_per_wave, groups)
     p.chunk_rel = crel[cperm].to(torch.int32).contiguous() if n_chunks else _i32(0, dev)
     tcnt = torch.bincount(ctile, minlength=n_tiles)
     tend = torch.cumsum(tcnt, 0)
@@ -1613,7 +1731,8 @@ def bwd_own_rows(n_nodes, device=None):
 def bwd_own(G, X, W, plan, relu=False, want_db=False):
     """(dX, dW[, db]) of the hidden-16 layer from one walk of a soft-window plan with relation ownership (build_softwin_plan(own_waves=...)):
     rgcn_bwd_own_f32 -- dX tile in LDS doubles, every relation's dW in the registers of its owner wave, the X rows of the tile in LDS next to it.
-    relu: X is the output of a ReLU and dX is wanted BEFORE it.  Sums in arrival order (not bit-reproducible)."""
+    relu: X is the output of a ReLU and dX is wanted BEFORE it.  Sums in arrival order (not bit-reproducible).  A plan in the shared form
+    (own_shared=True: plan.group_ptr, plan.shared_rel) has the chunks of its largest relation dealt to the waves at run time."""
     _req(G, "grad_output"); _req(X, "features"); _req(W, "weights")
     assert W.shape[1:] == (16, 16) and G.shape == (plan.n_src, 16) and X.shape == (plan.n_dst, 16) and W.shape[0] == plan.num_rels
     assert getattr(plan, "own_ptr", None) is not None, "bwd_own: a plan made with build_softwin_plan(own_waves=...)"
@@ -1624,8 +1743,8 @@ def bwd_own(G, X, W, plan, relu=False, want_db=False):
     dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
     rec = _blk_rec(plan)
     with _on(dev), _timed("bwd_fused"):
-        _check(lib().rgcn_bwd_own_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel),
-                                      plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0,
+        _check(lib().rgcn_bwd_own_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(getattr(plan, "group_ptr", None)),
+                                      getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0,
                                       _dp(db) if want_db else None, plan.n_src, _stream(dev)), "bwd_own")
     return (dX, dW, db if want_db else None)
 
@@ -1642,8 +1761,8 @@ def bwd_own_bf16(G, X, W, plan, relu=False, want_db=False):
     dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
     rec = _blk_rec(plan)
     with _on(dev), _timed("bwd_own_bf16"):
-        _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(plan.unit_rel), plan.n_tiles,
-                                       plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(db) if want_db else None, plan.n_src,
+        _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(getattr(plan, "group_ptr", None)),
+                                       getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(db) if want_db else None, plan.n_src,
                                        _stream(dev)), "bwd_own_bf16")
     return (dX, dW, db if want_db else None)
 

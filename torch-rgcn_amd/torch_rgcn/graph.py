@@ -163,12 +163,14 @@ class RelGraph:
             s, p, o, val, alive = self._dev
             dst, src = (s, o) if kind == "fwd" else (o, s)
             own = {}
-            if kind == "bwd_own":     # transposed plan, a tile's chunks grouped by the wave that owns their relation (rgcn_bwd_own_f32)
+            # transposed plan, a tile's chunks grouped by the wave that owns their relation (rgcn_bwd_own_f32), the chunks of the largest
+            # relation as a group of their own that the waves share at run time (_native.own_relations)
+            if kind == "bwd_own":
                 nw, per_wave, max_rows = _native.bwd_own_geometry()
                 if rows > max_rows or self.num_rels > nw * per_wave:
                     self._plans[key] = None
                     return None
-                own = {"own_waves": nw, "own_per_wave": per_wave}
+                own = {"own_waves": nw, "own_per_wave": per_wave, "own_shared": True}
             plan = _native.build_softwin_plan(dst, src, p, val, alive, self.num_nodes, self.num_nodes, self.num_rels, rows, **own)
             # a wave that owns far more messages than the others holds every tile back: such graphs keep the block-tile kernel
             if plan is not None and own and plan.own_balance > _OWN_MAX_IMBALANCE:
