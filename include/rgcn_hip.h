@@ -898,6 +898,62 @@ RGCN_API int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int
                                             const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
                                             int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
                                             int32_t n_rel, int32_t d, void *stream);
+/* Device-resident filter index: the known completions of one direction as a sorted table on the device, in place of
+ * the per-call lists (filt_q, filt_n, F).  fkeys [K] (int64), STRICTLY ASCENDING, key = p * n_nodes + o for head queries (the known
+ * heads of (?, p, o)) and p * n_nodes + s for tail queries; fptr [K + 1] (int64); fvals [fptr[K]] (int32), the completions of key k in
+ * fvals[fptr[k] .. fptr[k + 1]), ASCENDING AND UNIQUE within a key, each in [0, n_nodes).  NOTHING of the index is range-checked on the
+ * device: its builder (functional.FilterIndex) validates it once on the host.  K = 0 with NULL pointers = no filter, as F = 0 is.
+ *
+ * rgcn_filter_mask_index zeroes the caller's mask [Q][ceil(c_count / 32)] (uint32) and sets, for each query q of `batch`, the bit
+ * n - c_first of row q for every completion n of the query's key inside the columns [c_first, c_first + c_count) (inside [0, n_nodes));
+ * keep_target == 0 skips a completion equal to the query's own target (batch[q, 0] for head queries, batch[q, 2] for tail queries).  One
+ * wave per query: the key's binary search, two more over the key's sorted completions for the column range, then integer atomic OR.
+ * These are the bits the list forms set from (filt_q, filt_n); the _index entry points below call it on the mask of their workspace.
+ * n_nodes is the entity count the keys were formed with.  No host synchronisation, no memset. */
+RGCN_API int rgcn_filter_mask_index(const int64_t *batch, int64_t Q, int32_t head, const int64_t *fkeys, const int64_t *fptr,
+                                    const int32_t *fvals, int64_t K, int32_t keep_target, int64_t c_first, int64_t c_count, uint32_t *mask,
+                                    int64_t n_nodes, void *stream);
+/* rgcn_rank_filter_f32 from the index: scores[q, n] = -inf for every completion n of query q's key other than the query's own target
+ * (scores row-major [Q, n_nodes]); keep_target != 0 (prediction: the query has no target) writes that cell too, as a list built for
+ * prediction does.  Index contract as above: keys strictly ascending, fvals ascending within a key, nothing checked. */
+RGCN_API int rgcn_rank_filter_index_f32(float *scores, const int64_t *batch, int64_t Q, int32_t head, int64_t n_nodes, const int64_t *fkeys,
+                                        const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t keep_target, void *stream);
+/* The filtered entry points with the index (fkeys, fptr, fvals, K) where the list forms take (filt_q, filt_n, F): everything else --
+ * the workspace sizes and layouts, the passes, the errors -- is the list form's, and with the same excluded cells every result is bit
+ * for bit the list form's (the mask is filled another way; the product kernels are the same).  Index contract as above: keys strictly
+ * ascending, fvals ascending and unique within a key, nothing range-checked on the device, the index validated by its builder.  Ranking,
+ * log-sum-exp and gradient cells skip a completion on the query's own target; top-k excludes every completion. */
+RGCN_API int rgcn_distmult_rank_fused_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
+                                                void *stream);
+RGCN_API int rgcn_distmult_rank_fused_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                 const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                 const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                 int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
+                                                 void *stream);
+RGCN_API int rgcn_distmult_topk_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                          const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
+                                          int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_topk_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                           const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
+                                           int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                         const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                         const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
+                                         float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                          const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
+                                          float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                  int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
+                                                  float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -828,6 +828,66 @@ __global__ void rank_mask_kernel(unsigned *__restrict__ mask, long long mask_w, 
   }
 }
 
+// ------------------------------------------------------------------ device-resident filter index
+// The key -> completions table of one direction: keys [K] strictly ascending (key = p * N + the query's fixed entity), ptr [K + 1], vals
+// ascending and unique within a key.  Validated once by its builder (functional.FilterIndex): nothing is range-checked here.
+struct FilterIndexDev {
+  const long long *keys, *ptr;
+  const int *vals;
+  long long K;
+};
+
+// first position in [lo, hi) whose element is not below x
+template <class T>
+__device__ __forceinline__ long long index_lower_bound(const T *__restrict__ a, long long lo, long long hi, long long x) {
+  while (lo < hi) {
+    const long long mid = lo + ((hi - lo) >> 1);
+    if ((long long)a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// The walk of one wave over the known completions of query q inside the columns [c_first, c_end): every lane forms the key and runs the
+// same three searches (uniform over the wave), then the lanes stride the span by 64; f(n) takes a completion.  keep_target == 0 skips
+// the query's own target.  A key that is absent has no completions.
+template <class F>
+__device__ __forceinline__ void index_walk(const FilterIndexDev &ix, const long long *__restrict__ batch, int q, int head, long long N,
+                                           int keep_target, long long c_first, long long c_end, F f) {
+  const int lane = threadIdx.x & 63;
+  const long long key = batch[3 * q + 1] * N + batch[3 * q + (head ? 2 : 0)];
+  const long long k = index_lower_bound(ix.keys, 0, ix.K, key);
+  if (k >= ix.K || ix.keys[k] != key) return;
+  const long long end = ix.ptr[k + 1];
+  const long long lo = index_lower_bound(ix.vals, ix.ptr[k], end, c_first);
+  const long long hi = index_lower_bound(ix.vals, lo, end, c_end);
+  const long long tgt = rank_target(batch, q, head);
+  for (long long e = lo + lane; e < hi; e += 64) {
+    const long long n = ix.vals[e];
+    if (keep_target || n != tgt) f(n);
+  }
+}
+
+// filter bits from the index, one wave per query row: what rank_mask_kernel (c_first = 0, c_end = N) and chunk_mask_kernel set from the
+// lists of the same completions; bit 0 of word 0 = column c_first
+__global__ __launch_bounds__(WG) void index_mask_kernel(unsigned *__restrict__ mask, long long mask_w, FilterIndexDev ix,
+                                                        const long long *__restrict__ batch, int Q, int head, long long N,
+                                                        int keep_target, long long c_first, long long c_end) {
+  const int q = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+  if (q >= Q) return;
+  index_walk(ix, batch, q, head, N, keep_target, c_first, c_end, [&](long long n) {
+    atomicOr(mask + (size_t)q * mask_w + ((n - c_first) >> 5), 1u << ((n - c_first) & 31));
+  });
+}
+
+// the same walk for the materialised route: -inf where index_mask_kernel sets a bit of the whole row (ranking skips the target, as
+// filter_scores does; prediction keeps it)
+__global__ __launch_bounds__(WG) void index_filter_kernel(float *__restrict__ scores, FilterIndexDev ix, const long long *__restrict__ batch,
+                                                          int Q, int head, long long N, int keep_target) {
+  const int q = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+  if (q >= Q) return;
+  index_walk(ix, batch, q, head, N, keep_target, 0, N, [&](long long n) { scores[(size_t)q * N + n] = -INFINITY; });
+}
+
 // the strips' partials [n_part][Q] summed into the int64 outputs (integers: any order is exact)
 __global__ __launch_bounds__(WG) void rank_reduce_kernel(const uint2 *__restrict__ partial, int n_part, int Q,
                                                          long long *__restrict__ greater, long long *__restrict__ ties) {
@@ -1037,7 +1097,20 @@ struct StripArgs {
   int64_t n_nodes;
   int32_t d;
   void *stream;
+  FilterIndexDev ix;              // the index forms: K > 0 fills the mask from the index (filt_q / filt_n NULL, F = 0)
 };
+
+inline FilterIndexDev filter_index(const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals, int64_t K) {
+  return {reinterpret_cast<const long long *>(fkeys), reinterpret_cast<const long long *>(fptr), fvals, (long long)K};
+}
+inline bool bad_index(const FilterIndexDev &ix) { return ix.K < 0 || (ix.K && (!ix.keys || !ix.ptr || !ix.vals)); }
+
+// index_mask_kernel on a zeroed mask of the columns [c_first, c_end)
+inline void launch_index_mask(hipStream_t st, unsigned *mask, int64_t mask_w, const FilterIndexDev &ix, const long long *b, int64_t Q,
+                              int32_t head, int64_t n_nodes, int keep_target, int64_t c_first, int64_t c_end) {
+  hipLaunchKernelGGL(index_mask_kernel, dim3((unsigned)((Q + WG / 64 - 1) / (WG / 64))), dim3(WG), 0, st, mask, (long long)mask_w, ix, b, (int)Q,
+                     head, (long long)n_nodes, keep_target, (long long)c_first, (long long)c_end);
+}
 
 // Argument and bias checks of a strip entry point.  bad_own: the caller's conditions on its own arguments; hint: what they add to the message.
 template <class E>
@@ -1045,6 +1118,10 @@ int strip_check(const StripArgs<E> &a, bool bad_own, const char *hint) {
   if (a.Q < 0 || a.n_nodes <= 0 || a.d <= 0 || a.Q > INT32_MAX || a.F < 0 || a.strips < 0 || bad_own || (a.F && (!a.filt_q || !a.filt_n)) ||
       (a.Q && (!a.batch || !a.nodes || !a.rel || !a.workspace)) || !aligned16(a.workspace)) {
     rgcn_set_error("%s: bad argument (workspace: 16-byte aligned; %sstrips >= 0; F > 0 needs both filter lists)", a.name, hint);
+    return RGCN_EINVAL;
+  }
+  if (bad_index(a.ix) || (a.ix.K && a.F)) {
+    rgcn_set_error("%s: bad filter index (K >= 0; K > 0 needs keys, ptr and vals, and no filter lists beside them)", a.name);
     return RGCN_EINVAL;
   }
   if ((a.sbias != nullptr) != (a.pbias != nullptr) || (a.sbias != nullptr) != (a.obias != nullptr)) {
@@ -1085,7 +1162,7 @@ int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
   char *ws = static_cast<char *>(a.workspace);
   typename Tile::elem *q = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
   float *qb = reinterpret_cast<float *>(ws + L.qb);
-  unsigned *mask = a.F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
   c.mask_w = L.mask_w;
   c.st = (hipStream_t)a.stream;
   c.b = reinterpret_cast<const long long *>(a.batch);
@@ -1095,11 +1172,11 @@ int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
   c.cbias = a.sbias ? (a.head ? a.sbias : a.obias) : nullptr;
   c.part = ws + L.part;
   c.mask = mask;
-  if (a.F) {
-    HIP_TRY(zero_async(mask, (size_t)(a.Q * L.mask_w) * sizeof(unsigned), c.st));
+  if (mask) HIP_TRY(zero_async(mask, (size_t)(a.Q * L.mask_w) * sizeof(unsigned), c.st));
+  if (a.F)
     hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, c.st, mask,
                        (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head, keep_target);
-  }
+  if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.head, a.n_nodes, keep_target, 0, a.n_nodes);
   launch_query<Tile>(c.st, c.b, a.Q, a.head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, q, qb, a.d);
   return RGCN_OK;
 }
@@ -1150,6 +1227,26 @@ extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, in
   (void)n_rel;
   return rank_fused<TileBf16>({"distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips,
                                workspace, n_nodes, d, stream}, greater, ties, tscore);
+}
+
+extern "C" int rgcn_distmult_rank_fused_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                  int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
+                                                  void *stream) {
+  (void)n_rel;
+  return rank_fused<TileF32>({"distmult_rank_fused_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
+                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, greater, ties, tscore);
+}
+
+extern "C" int rgcn_distmult_rank_fused_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                   int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
+                                                   void *stream) {
+  (void)n_rel;
+  return rank_fused<TileBf16>({"distmult_rank_fused_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
+                               workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, greater, ties, tscore);
 }
 
 // ------------------------------------------------------------------ top-k prediction: entry points
@@ -1217,6 +1314,24 @@ extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t 
                                n_nodes, d, stream}, k, ids, scores);
 }
 
+extern "C" int rgcn_distmult_topk_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                            const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
+                                            int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return topk_fused<TileF32>({"distmult_topk_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
+                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
+}
+
+extern "C" int rgcn_distmult_topk_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                             const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                             const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
+                                             int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return topk_fused<TileBf16>({"distmult_topk_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
+                               workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
+}
+
 // ------------------------------------------------------------------ 1-N softmax loss: entry points
 namespace {
 
@@ -1278,9 +1393,64 @@ extern "C" int rgcn_distmult_lse_bf16(const int64_t *batch, int64_t Q, int32_t h
                               n_nodes, d, stream}, lse, tscore);
 }
 
+extern "C" int rgcn_distmult_lse_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                           const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
+                                           float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileF32>({"distmult_lse_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace, n_nodes,
+                             d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
+}
+
+extern "C" int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                            const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
+                                            float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileBf16>({"distmult_lse_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
+                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
+}
+
 extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
   return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d).total;
 }
+
+namespace {
+
+// what the list form and the index form of the gradient-cell entry share: a.F fills the chunk's mask from the lists, a.ix.K from the index
+int softmax_grad(const StripArgs<float> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
+                 int64_t c_count, float *dS) {
+  const int64_t Q = a.Q, n_nodes = a.n_nodes;
+  const int32_t head = a.head, d = a.d;
+  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > n_nodes - c_count || mean_over < 1;
+  const float inv_q = 1.0f / (float)mean_over;
+  if (int rc = strip_check(a, bad_chunk || (Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
+  if (Q == 0) return RGCN_OK;
+  const int64_t qbl = (Q + 127) / 128, nwg = ((c_count + 127) / 128) * qbl;
+  if (nwg > INT32_MAX) { rgcn_set_error("%s: too many cells in one call; take a smaller chunk", a.name); return RGCN_EUNSUPPORTED; }
+  const GradLayout L = grad_layout(Q, c_count, d);
+  char *ws = static_cast<char *>(a.workspace);
+  float *qv = reinterpret_cast<float *>(ws + L.qv), *qb = reinterpret_cast<float *>(ws + L.qb);
+  unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  hipStream_t st = (hipStream_t)a.stream;
+  const long long *b = reinterpret_cast<const long long *>(a.batch);
+  if (mask) HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
+  if (a.F)
+    hipLaunchKernelGGL(chunk_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
+                       (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, b, head, (long long)c_first, (long long)(c_first + c_count));
+  if (a.ix.K) launch_index_mask(st, mask, L.mask_w, a.ix, b, Q, head, n_nodes, 0, c_first, c_first + c_count);
+  launch_query<TileF32>(st, b, Q, head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, qv, qb, d);
+  const float *qb1 = a.sbias ? qb : nullptr, *cb1 = a.sbias ? (head ? a.sbias : a.obias) : nullptr;
+  with_vec<TileF32>(a.nodes, d, [&](auto vec) {
+    hipLaunchKernelGGL((softmax_grad_kernel<decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const float *)qv, a.nodes,
+                       tile_dims<TileF32>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
+                       (int)Q, (long long)n_nodes, (long long)c_first, (long long)c_count, head, (int)qbl);
+  });
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
 
 extern "C" int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                               const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
@@ -1288,32 +1458,49 @@ extern "C" int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, i
                                               int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
                                               int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  const StripArgs<float> a{"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes,
-                           d, stream};
-  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > n_nodes - c_count || mean_over < 1;
-  const float inv_q = 1.0f / (float)mean_over;
-  if (int rc = strip_check(a, bad_chunk || (Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
-  if (Q == 0) return RGCN_OK;
-  const int64_t qbl = (Q + 127) / 128, nwg = ((c_count + 127) / 128) * qbl;
-  if (nwg > INT32_MAX) { rgcn_set_error("distmult_softmax_grad: too many cells in one call; take a smaller chunk"); return RGCN_EUNSUPPORTED; }
-  const GradLayout L = grad_layout(Q, c_count, d);
-  char *ws = static_cast<char *>(workspace);
-  float *qv = reinterpret_cast<float *>(ws + L.qv), *qb = reinterpret_cast<float *>(ws + L.qb);
-  unsigned *mask = F ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const long long *b = reinterpret_cast<const long long *>(batch);
-  if (F) {
-    HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
-    hipLaunchKernelGGL(chunk_mask_kernel, dim3((unsigned)std::min<int64_t>((F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
-                       (long long)L.mask_w, filt_q, filt_n, (long long)F, b, head, (long long)c_first, (long long)(c_first + c_count));
+  return softmax_grad({"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes, d,
+                       stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                    const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                    const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                    int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
+                                                    float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad({"distmult_softmax_grad_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0, workspace, n_nodes,
+                       d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
+}
+
+// ------------------------------------------------------------------ device-resident filter index: the mask and the materialised route
+extern "C" int rgcn_filter_mask_index(const int64_t *batch, int64_t Q, int32_t head, const int64_t *fkeys, const int64_t *fptr,
+                                      const int32_t *fvals, int64_t K, int32_t keep_target, int64_t c_first, int64_t c_count, uint32_t *mask,
+                                      int64_t n_nodes, void *stream) {
+  const FilterIndexDev ix = filter_index(fkeys, fptr, fvals, K);
+  if (Q < 0 || Q > INT32_MAX || n_nodes <= 0 || bad_index(ix) || c_first < 0 || c_count <= 0 || c_first > n_nodes - c_count ||
+      (Q && (!batch || !mask))) {
+    rgcn_set_error("filter_mask_index: bad argument (K > 0 needs keys, ptr and vals; the columns inside [0, n_nodes))");
+    return RGCN_EINVAL;
   }
-  launch_query<TileF32>(st, b, Q, head, nodes, rel, sbias, pbias, obias, qv, qb, d);
-  const float *qb1 = sbias ? qb : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
-  with_vec<TileF32>(nodes, d, [&](auto vec) {
-    hipLaunchKernelGGL((softmax_grad_kernel<decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const float *)qv, nodes,
-                       tile_dims<TileF32>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
-                       (int)Q, (long long)n_nodes, (long long)c_first, (long long)c_count, head, (int)qbl);
-  });
+  if (Q == 0) return RGCN_OK;
+  const int64_t mask_w = (c_count + 31) / 32;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(zero_async(mask, (size_t)(Q * mask_w) * sizeof(unsigned), st));
+  if (K) launch_index_mask(st, mask, mask_w, ix, reinterpret_cast<const long long *>(batch), Q, head, n_nodes, keep_target, c_first, c_first + c_count);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+extern "C" int rgcn_rank_filter_index_f32(float *scores, const int64_t *batch, int64_t Q, int32_t head, int64_t n_nodes, const int64_t *fkeys,
+                                          const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t keep_target, void *stream) {
+  const FilterIndexDev ix = filter_index(fkeys, fptr, fvals, K);
+  if (Q < 0 || Q > INT32_MAX || n_nodes <= 0 || bad_index(ix) || (Q && K && (!scores || !batch))) {
+    rgcn_set_error("rank_filter_index: bad argument");
+    return RGCN_EINVAL;
+  }
+  if (K == 0 || Q == 0) return RGCN_OK;
+  hipLaunchKernelGGL(index_filter_kernel, dim3((unsigned)((Q + WG / 64 - 1) / (WG / 64))), dim3(WG), 0, (hipStream_t)stream, scores, ix,
+                     reinterpret_cast<const long long *>(batch), (int)Q, head, (long long)n_nodes, keep_target);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

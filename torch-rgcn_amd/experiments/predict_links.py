@@ -6,7 +6,9 @@ experiments/predict_links.py (:19-228) without sacred.  Reads the reference's co
 
 training.{epochs,graph_batch_size,sampling_method,negative_sampling.{sampling_rate,head_prob},optimiser.*}
 training.objective (an extension, absent in the reference): "negative-sampling" (default: the reference's sampled-negative BCE) or "1-n"
-(softmax cross-entropy of every sampled positive against ALL entities, tails and heads, unfiltered; configs/rgcn/lp-WN18-1n.yaml)
+(softmax cross-entropy of every sampled positive against ALL entities, tails and heads; configs/rgcn/lp-WN18-1n.yaml);
+training.filtered (1-n only, default false; configs/rgcn/lp-WN18-1n-filtered.yaml): the other known completions of a query -- from the
+TRAINING triples only -- are left out of its softmax, looked up in a device-resident FilterIndex, so the step is captured all the same
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""
@@ -22,7 +24,7 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch_rgcn  # noqa: E402
 from torch_rgcn import routes  # noqa: E402
-from torch_rgcn.functional import bce_with_logits, unit_gradient  # noqa: E402
+from torch_rgcn.functional import FilterIndex, bce_with_logits, unit_gradient  # noqa: E402
 from torch_rgcn.models import CompressionRelationPredictor, LinkPredictor  # noqa: E402
 from utils.data import load_link_prediction_data  # noqa: E402
 from utils.misc import evaluate, generate_true_dict, negative_sampling, select_sampling  # noqa: E402
@@ -30,19 +32,23 @@ from utils.misc import evaluate, generate_true_dict, negative_sampling, select_s
 OPTIMISERS = {"adam": torch.optim.Adam, "adamw": torch.optim.AdamW, "adagrad": torch.optim.Adagrad, "sgd": torch.optim.SGD}
 
 
-def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=None, hipgraph=None, fused_eval=None):
+def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=None, hipgraph=None, fused_eval=None, device_filter=False):
     """-> (loss per epoch, {"mrr", "hits@1", "hits@3", "hits@10"} of the final evaluation).
     The training step (per-step graph build, encoder, decoder, loss, backward, optimiser) is captured once in a hipGraph and replayed
     every epoch on freshly sampled inputs copied into static buffers -- BY DEFAULT (hipgraph=None: unless route `capture` is "0";
     falls back to the eager loop, with a warning, if the capture fails; True insists, False is the reference's loop literally).
     The capture runs under the sync-free plan builder (route deferred_checks = 1, scoped to the warm-up and the capture).
-    fused_eval: utils.misc.evaluate's `fused` (True: rank without the score matrix; None: only where that matrix would need chunks)."""
+    fused_eval: utils.misc.evaluate's `fused` (True: rank without the score matrix; None: only where that matrix would need chunks).
+    device_filter: utils.misc.evaluate's `device_filter` (the evaluation filter from a device-resident index, no host lists)."""
     dataset, training, encoder = cfg["dataset"], cfg["training"], cfg["encoder"]
     decoder, evaluation = cfg.get("decoder", {}), cfg.get("evaluation", {})
     objective = training.get("objective", "negative-sampling")
     if objective not in ("negative-sampling", "1-n"):
         raise NotImplementedError(f"'{objective}' training objective has not been implemented!")
     one_to_n = objective == "1-n"
+    train_filtered = bool(training.get("filtered", False))
+    if train_filtered and not one_to_n:
+        raise ValueError("training.filtered needs training.objective: 1-n (sampled negatives are not filtered)")
     max_epochs = epochs or training.get("epochs", 5000)
     graph_batch_size = training.get("graph_batch_size")
     sampling_function = select_sampling(training.get("sampling_method", "uniform"))
@@ -53,7 +59,7 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     filtered = evaluation.get("filtered", False)
     eval_every = evaluation.get("check_every", 2000)
     eval_kw = dict(batch_size=evaluation.get("batch_size", 16), verbose=evaluation.get("verbose", False) and not quiet,
-                   filter_candidates=filtered, fused=fused_eval)
+                   filter_candidates=filtered, fused=fused_eval, device_filter=device_filter)
 
     (n2i, nodes), (r2i, relations), train, test, all_triples = load_link_prediction_data(
         dataset["name"], use_test_set=evaluation.get("final_run", False), directory=data_dir, synthetic=synthetic)
@@ -80,6 +86,8 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     test = torch.tensor(test, dtype=torch.long)
     train = np.asarray(train, dtype=np.int64)          # sampled from every epoch: keep it an array
     train_graph = torch.from_numpy(train)
+    # the filter of the 1-N loss: the TRAINING triples alone (validation and test triples must not reach the loss), indexed once
+    train_filter = FilterIndex(generate_true_dict(train), num_nodes, device) if train_filtered else None
     if encoder["model"] == "rgcn":
         kind = LinkPredictor
     elif encoder["model"] == "c-rgcn":
@@ -142,10 +150,11 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
         return batch_idx, train_lbl
 
     def step_loss(graph, batch_idx, train_lbl):
-        if one_to_n:      # 1-N softmax: half the tail loss, half the head loss, unfiltered (static shapes: the captured step works)
+        if one_to_n:      # 1-N softmax: half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
             x = model.encode(graph)
             decoder_ = model.scoring_function
-            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False) + decoder_.softmax_loss(batch_idx, x, head=True))
+            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False, filt=train_filter) +
+                          decoder_.softmax_loss(batch_idx, x, head=True, filt=train_filter))
             return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
         predictions, penalty = model(graph, batch_idx)
         return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
@@ -244,6 +253,9 @@ if __name__ == "__main__":
     ap.add_argument("--eager", action="store_true", help="the reference's loop literally: no hipGraph capture")
     ap.add_argument("--fused-eval", action="store_true", help="rank with the fused evaluator (no score matrix) whatever the size; "
                     "the default takes it only where the score matrix of the test set exceeds the 1 GiB chunk budget")
+    ap.add_argument("--device-filter", action="store_true", help="evaluate with the filter looked up in a device-resident index "
+                    "instead of host-built lists per chunk (the same ranks)")
     a = ap.parse_args()
     run(yaml.safe_load(open(a.config)), a.data, a.epochs, max_test=a.max_test, synthetic=True if a.synthetic else None,
-        hipgraph=False if a.eager else (True if a.hipgraph else None), fused_eval=True if a.fused_eval else None)
+        hipgraph=False if a.eager else (True if a.hipgraph else None), fused_eval=True if a.fused_eval else None,
+        device_filter=a.device_filter)

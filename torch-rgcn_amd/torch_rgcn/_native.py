@@ -2375,16 +2375,61 @@ def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obi
     return scores
 
 
+def _index_args(filt, head, N, device, filt_q=None):
+    """the (fkeys, fptr, fvals, K) arguments of an _index entry point from a functional.FilterIndex: the table of the direction `head`
+    asks for, NULLs for an index without keys.  The index was validated when it was built: nothing is checked per call but that it is
+    the index of these tensors."""
+    assert filt_q is None, "a FilterIndex or the filter lists, not both"
+    assert filt.num_nodes == N and filt.device == device, "the FilterIndex belongs to another entity table or device"
+    keys, ptr, vals = filt.tables[0 if head else 1]
+    K = keys.shape[0]
+    return (_dp(keys), _dp(ptr), _dp(vals), K) if K else (None, None, None, 0)
+
+
+def filter_mask_index(batch, head, filt, keep_target=False, c_first=0, c_count=None, out=None):
+    """int32 [Q, ceil(c_count / 32)]: the filter bits of the candidate columns [c_first, c_first + c_count) (default: all of them) for the
+    queries of `batch` (int64 [Q, 3], device, range-checked by the caller), filled on the device from a functional.FilterIndex -- bit
+    n - c_first of row q is set for every known completion n of query q; keep_target=False leaves the query's own target out.  The words
+    are the uint32 words the product kernels read.  out: an int32 buffer of that shape to fill."""
+    _req(batch, "batch", torch.int64)
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    Q, N, dev = batch.shape[0], filt.num_nodes, batch.device
+    c_count = N - c_first if c_count is None else c_count
+    assert 0 <= c_first and c_count >= 1 and c_first + c_count <= N, "the columns lie inside [0, N)"
+    ix = _index_args(filt, head, N, dev)
+    mask = out if out is not None else torch.empty(Q, (c_count + 31) // 32, device=dev, dtype=torch.int32)
+    _req(mask, "mask", torch.int32)
+    assert mask.shape == (Q, (c_count + 31) // 32)
+    with _on(dev), _timed("filter_mask_index"):
+        _check(lib().rgcn_filter_mask_index(_dp(batch), Q, 1 if head else 0, ix[0], ix[1], ix[2], ix[3], 1 if keep_target else 0, c_first,
+                                            c_count, _dp(mask), N, _stream(dev)), "filter_mask_index")
+    return mask
+
+
+def rank_filter_index(scores, batch, head, filt, keep_target=False):
+    """rank_filter from a functional.FilterIndex: scores[q, n] = -inf for every known completion n of query q but its own target
+    (keep_target=True, prediction: the query has no target, that cell too)"""
+    _req(scores, "scores"); _req(batch, "batch", torch.int64)
+    Q, N = scores.shape
+    assert batch.shape == (Q, 3)
+    ix = _index_args(filt, head, N, scores.device)
+    with _on(scores.device), _timed("rank_filter_index"):
+        _check(lib().rgcn_rank_filter_index_f32(_dp(scores), _dp(batch), Q, 1 if head else 0, N, ix[0], ix[1], ix[2], ix[3],
+                                                1 if keep_target else 0, _stream(scores.device)), "rank_filter_index")
+    return scores
+
+
 def rank_fused_workspace_bytes(Q, N, d, strips=0, bf16=False):
     """bytes of the fused evaluator's workspace (query vectors, strip partials, the [Q][ceil(N / 32)] filter mask); needs no device"""
     return int(lib().rgcn_distmult_rank_fused_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
 
 
-def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0):
+def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None):
     """(greater, ties, tscore) of every query of `batch` (int64 [Q, 3], device) without the [Q, N] score matrix: what rank_count returns
     after distmult_score_all[_bf16] and rank_filter on (filt_q, filt_n) (int32 device lists, None = raw ranks), plus the target's own
     score -- utils/misc.py:40-58, 71-99.  fp32 or bf16 nodes (rel and biases fp32).  strips: candidate strips per block of 128 queries
-    (0 = the library's choice).  A filter entry on a query's own target is ignored."""
+    (0 = the library's choice).  A filter entry on a query's own target is ignored.  filt: a functional.FilterIndex in place of the
+    lists -- the mask is filled on the device from the index, the same counts (its own profile tags: rank_fused_index[_bf16])."""
     bf16 = nodes.dtype == torch.bfloat16
     if bf16:
         _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
@@ -2414,6 +2459,20 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     ties = torch.empty(Q, device=dev, dtype=torch.int64)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    if filt is not None:
+        ix = _index_args(filt, head, N, dev, filt_q)
+        with _on(dev), _timed("rank_fused_index_bf16" if bf16 else "rank_fused_index"):
+            if bf16:
+                _check(lib().rgcn_distmult_rank_fused_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                                 _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(greater),
+                                                                 _dp(ties), _dp(tscore), N, rel.shape[0], d, _stream(dev)),
+                       "distmult_rank_fused_index_bf16")
+            else:
+                _check(lib().rgcn_distmult_rank_fused_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                                _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(greater),
+                                                                _dp(ties), _dp(tscore), N, rel.shape[0], d, _stream(dev)),
+                       "distmult_rank_fused_index")
+        return greater, ties, tscore
     with _on(dev), _timed("rank_fused_bf16" if bf16 else "rank_fused"):
         if bf16:
             _check(lib().rgcn_distmult_rank_fused_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
@@ -2444,6 +2503,18 @@ def distmult_topk(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k
     device lists (filt_q, filt_n) is excluded; rows with fewer than k candidates end in id -1, score -inf.  fp32 or bf16 nodes (rel and
     biases fp32).  1 <= k <= TOPK_MAX (the library refuses a larger k).  strips: as in distmult_rank_fused.  NaN scores are outside the
     contract."""
+    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, None)
+
+
+def distmult_topk_index(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0):
+    """distmult_topk with a functional.FilterIndex in place of the lists: every known completion of a query is excluded, the same rows
+    (its own profile tags: topk_fused_index[_bf16])"""
+    assert filt is not None, "distmult_topk_index needs a FilterIndex"
+    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, None, None, strips, filt)
+
+
+def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
+    """distmult_topk and distmult_topk_index: the filter as lists, as an index, or none"""
     bf16 = nodes.dtype == torch.bfloat16
     if bf16:
         _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
@@ -2473,6 +2544,18 @@ def distmult_topk(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k
     ids = torch.empty(Q, k, device=dev, dtype=torch.int64)
     scores = torch.empty(Q, k, device=dev, dtype=torch.float32)
     ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    if filt is not None:
+        ix = _index_args(filt, head, N, dev, filt_q)
+        with _on(dev), _timed("topk_fused_index_bf16" if bf16 else "topk_fused_index"):
+            if bf16:
+                _check(lib().rgcn_distmult_topk_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                           _dp(obias), ix[0], ix[1], ix[2], ix[3], k, strips, _dp(ws), _dp(ids), _dp(scores),
+                                                           N, rel.shape[0], d, _stream(dev)), "distmult_topk_index_bf16")
+            else:
+                _check(lib().rgcn_distmult_topk_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                          _dp(obias), ix[0], ix[1], ix[2], ix[3], k, strips, _dp(ws), _dp(ids), _dp(scores),
+                                                          N, rel.shape[0], d, _stream(dev)), "distmult_topk_index")
+        return ids, scores
     with _on(dev), _timed("topk_fused_bf16" if bf16 else "topk_fused"):
         if bf16:
             _check(lib().rgcn_distmult_topk_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
@@ -2491,7 +2574,8 @@ def checked_queries(batch, N, n_rel, filt_q, filt_n, bf16):
     mask).  Read back at once, as distmult_rank_fused does.  Under route deferred_checks = 1 an unfiltered call does not synchronise: one
     device flag goes to the deferred queue and the triples are clamped into the tables meanwhile (the kernels do not range-check; the
     IndexError arrives with a later call or check_deferred_errors()); inside a stream capture nothing is checked -- the captured step
-    was validated before.  Filter lists are always checked at once: a filtered step is an eager one."""
+    was validated before.  Filter LISTS are always checked at once: a step filtered by lists is an eager one.  A functional.FilterIndex
+    was validated when it was built and needs no check here: its callers pass no lists and take the unfiltered path."""
     Q = batch.shape[0]
     F = 0 if filt_q is None else filt_q.shape[0]
     if not Q:
@@ -2540,11 +2624,12 @@ def lse_workspace_bytes(Q, N, d, strips=0, bf16=False):
     return int(lib().rgcn_distmult_lse_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
 
 
-def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False):
+def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False, filt=None):
     """(lse, tscore) fp32 [Q]: lse[q] = log sum exp of the cells of distmult_score_all[_bf16] over every entity that is not on the int32
     device lists (filt_q, filt_n) -- an entry on a query's own target is ignored, as in distmult_rank_fused --, tscore[q] = the target's
     cell, without the [Q, N] score matrix.  The 1-N softmax loss of a query is lse - tscore.  fp32 or bf16 nodes (rel and biases fp32).
-    strips: as in distmult_rank_fused.  checked: `batch` went through checked_queries already (a caller that uses it again afterwards)."""
+    strips: as in distmult_rank_fused.  checked: `batch` went through checked_queries already (a caller that uses it again afterwards).
+    filt: a functional.FilterIndex in place of the lists (profile tags lse_fused_index[_bf16])."""
     bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, strips)
     if not checked:
         batch = checked_queries(batch, N, rel.shape[0], filt_q if F else None, filt_n if F else None, bf16)
@@ -2552,6 +2637,18 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     lse = torch.empty(Q, device=dev, dtype=torch.float32)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    if filt is not None:
+        ix = _index_args(filt, head, N, dev, filt_q)
+        with _on(dev), _timed("lse_fused_index_bf16" if bf16 else "lse_fused_index"):
+            if bf16:
+                _check(lib().rgcn_distmult_lse_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                          _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(lse), _dp(tscore), N,
+                                                          rel.shape[0], d, _stream(dev)), "distmult_lse_index_bf16")
+            else:
+                _check(lib().rgcn_distmult_lse_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                         _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(lse), _dp(tscore), N,
+                                                         rel.shape[0], d, _stream(dev)), "distmult_lse_index")
+        return lse, tscore
     with _on(dev), _timed("lse_fused_bf16" if bf16 else "lse_fused"):
         if bf16:
             _check(lib().rgcn_distmult_lse_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
@@ -2564,11 +2661,13 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     return lse, tscore
 
 
-def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None):
+def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None,
+                          filt=None):
     """dS fp32 [Q, c_count]: the gradient cells of the 1-N softmax loss on the candidate columns [c_first, c_first + c_count),
     scale_q (exp(s[q, c] - lse[q]) - [c == target_q]), filtered cells 0; scale_q = gscale / mean_over with gscale a device float [1] or
     [Q] (never read back).  fp32 only.  lse: distmult_lse's of the same arguments.  The caller has range-checked the triples and the
-    lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to write into."""
+    lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to write into.  filt: a functional.FilterIndex in
+    place of the lists -- the chunk's mask is filled from it (profile tag softmax_grad_index)."""
     bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n)
     assert not bf16, "distmult_softmax_grad is fp32 only"
     _req(lse, "lse"); _req(gscale, "gscale")
@@ -2581,9 +2680,18 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     assert out.numel() >= Q * c_count
     dS = out.view(-1)[:Q * c_count].view(Q, c_count)
     ws = torch.empty(max(int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d)), 16), device=dev, dtype=torch.uint8)
+    per_query = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0
+    if filt is not None:
+        ix = _index_args(filt, head, N, dev, filt_q)
+        with _on(dev), _timed("softmax_grad_index"):
+            _check(lib().rgcn_distmult_softmax_grad_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                              _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
+                                                              int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
+                                                              _stream(dev)), "distmult_softmax_grad_index")
+        return dS
     with _on(dev), _timed("softmax_grad"):
         _check(lib().rgcn_distmult_softmax_grad_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
                                                     _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
-                                                    1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over), c_first, c_count,
+                                                    per_query, int(mean_over), c_first, c_count,
                                                     _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad")
     return dS

@@ -8,6 +8,7 @@ Both are the custom-Function form of what the reference leaves to autograd
 autograd engine's thread and launches on that thread's current HIP stream; it uses
 nothing but the tensors saved on ctx and the immutable RelGraph.
 """
+import numpy as np
 import torch
 
 from . import _native, routes
@@ -1248,19 +1249,81 @@ def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, ob
     return _native.distmult_score_all(batch, head, nodes, relations, sbias, pbias, obias, out=out)
 
 
-def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0):
+class FilterIndex:
+    """The known completions of every query key, resident on the device: what the filtered routes take as `filt=` in place
+    of the per-batch int32 lists (filt_q, filt_n).  true_triples: the pair utils.misc.generate_true_dict returns -- (p, o) -> known heads
+    and (s, p) -> known tails.  Per direction (tables[0]: heads, tables[1]: tails) three device tensors
+        keys int64 [K]      strictly ascending, key = p * num_nodes + o (heads) or p * num_nodes + s (tails),
+        ptr  int64 [K + 1],
+        vals int32 [ptr[K]] the completions of key k in vals[ptr[k]:ptr[k + 1]], ascending and deduplicated,
+    from which a kernel fills a query batch's filter mask (one binary search per query) -- no host pass, no upload and no length F per
+    call, so a filtered step has static shapes and can be captured.  Everything is validated HERE, once, on the host (`host_tables`, which
+    needs no GPU): an entity outside [0, num_nodes) or a negative relation raises IndexError, and no call checks the index again.  An
+    empty dictionary gives K = 0, an index that filters nothing.  The tensors never require grad; one index serves any number of calls."""
+
+    def __init__(self, true_triples, num_nodes, device):
+        self.num_nodes = int(num_nodes)
+        self.tables = [tuple(torch.from_numpy(a).to(device) for a in t) for t in self.host_tables(true_triples, num_nodes)]
+        self.device = self.tables[0][0].device
+
+    @staticmethod
+    def host_tables(true_triples, num_nodes):
+        """-> [(keys, ptr, vals) of the heads, (keys, ptr, vals) of the tails] as numpy arrays (int64, int64, int32): the numpy stage"""
+        n = int(num_nodes)
+        if n < 1:
+            raise IndexError("a FilterIndex needs num_nodes >= 1")
+        out = []
+        for table, rel_at, ent_at in ((true_triples[0], 0, 1), (true_triples[1], 1, 0)):      # heads: (p, o) -> [s]; tails: (s, p) -> [o]
+            lens = np.fromiter((len(v) for v in table.values()), np.int64, len(table))
+            total = int(lens.sum())
+            rel = np.repeat(np.fromiter((k[rel_at] for k in table), np.int64, len(table)), lens)
+            ent = np.repeat(np.fromiter((k[ent_at] for k in table), np.int64, len(table)), lens)
+            comp = np.fromiter((x for v in table.values() for x in v), np.int64, total)
+            if total and (rel.min() < 0 or ent.min() < 0 or ent.max() >= n or comp.min() < 0 or comp.max() >= n):
+                raise IndexError(f"true triples: an entity outside [0, {n}) or a negative relation")
+            if total and int(rel.max()) > (np.iinfo(np.int64).max - n) // n:
+                raise IndexError("true triples: relation * num_nodes does not fit 64 bits")
+            key = rel * n + ent
+            order = np.lexsort((comp, key))
+            key, comp = key[order], comp[order]
+            first = np.ones(total, bool)
+            first[1:] = (key[1:] != key[:-1]) | (comp[1:] != comp[:-1])           # a duplicate triple is one completion
+            key, comp = key[first], comp[first]
+            keys, counts = np.unique(key, return_counts=True)
+            ptr = np.zeros(len(keys) + 1, np.int64)
+            np.cumsum(counts, out=ptr[1:])
+            out.append((keys.astype(np.int64), ptr, comp.astype(np.int32)))
+        return out
+
+
+def _filter_args(filt, filt_q, filt_n, nodes):
+    """the argument rules of `filt=`: a FilterIndex or the lists, built for this entity table, on its device"""
+    if filt is None:
+        return
+    if not isinstance(filt, FilterIndex):
+        raise TypeError(f"filt must be a FilterIndex, got {type(filt).__name__}")
+    if filt_q is not None or filt_n is not None:
+        raise ValueError("filt (a FilterIndex) and filt_q / filt_n (the lists) are mutually exclusive")
+    if filt.device != nodes.device:
+        raise ValueError(f"the FilterIndex is on {filt.device}, the entity table on {nodes.device}")
+    if filt.num_nodes != nodes.shape[0]:
+        raise ValueError(f"the FilterIndex was built for {filt.num_nodes} entities, the entity table has {nodes.shape[0]}")
+
+
+def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None):
     """(greater, ties, tscore) [Q]: for each triple of `batch` the number of entities that score above its target as the head (head=True)
     or the tail, the number that score the same (the target included) and the target's score -- the counts `_native.rank_count` takes from
     the score matrix of distmult_score_all after `_native.rank_filter` on the int32 device lists (filt_q, filt_n), without that matrix
     (utils/misc.py:40-58, 71-99).  No autograd.  fp32 or bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16
-    (widened here), as in distmult_score_all."""
+    (widened here), as in distmult_score_all.  filt: a FilterIndex in place of the lists (not both: ValueError) -- the same counts."""
+    _filter_args(filt, filt_q, filt_n, nodes)
     if nodes.dtype == torch.bfloat16:
         for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
             if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
                 raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
         widen = lambda t: None if t is None else t.float()     # noqa: E731
         relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
-    return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips)
+    return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, filt=filt)
 
 
 def distmult_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt_q=None, filt_n=None, strips=0):
@@ -1268,13 +1331,30 @@ def distmult_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obi
     tail -- the rows of distmult_score_all after `_native.rank_filter` on the int32 device lists (filt_q, filt_n), sorted by score
     descending and id ascending and cut at k, without that matrix.  The predicted column of `batch` is ignored and every
     listed cell is excluded; rows with fewer than k candidates end in id -1, score -inf.  No autograd.  k <= _native.TOPK_MAX.  fp32 or
-    bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16 (widened here), as in distmult_rank_all."""
+    bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16 (widened here), as in distmult_rank_all.  With a FilterIndex in
+    place of the lists: distmult_topk_all_index (this function's parameter list is the one its callers know; it stays)."""
+    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, None)
+
+
+def distmult_topk_all_index(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0):
+    """distmult_topk_all with `filt`, a FilterIndex, in place of the lists: every known completion of a query is excluded -- the same
+    rows, bit for bit, with no list built on the host.  The index must be on the tensors' device and built for nodes.shape[0] entities
+    (ValueError)."""
+    if filt is None:
+        raise ValueError("distmult_topk_all_index needs a FilterIndex (distmult_topk_all takes lists or no filter)")
+    _filter_args(filt, None, None, nodes)
+    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, None, None, strips, filt)
+
+
+def _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
     if nodes.dtype == torch.bfloat16:
         for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
             if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
                 raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
         widen = lambda t: None if t is None else t.float()     # noqa: E731
         relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+    if filt is not None:
+        return _native.distmult_topk_index(batch, head, nodes, relations, sbias, pbias, obias, k, filt, strips)
     return _native.distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips)
 
 
@@ -1321,17 +1401,20 @@ def softmax_chunk_plan(Q, N, chunk_bytes):
 
 class _DistMultSoftmaxLoss(torch.autograd.Function):
     """loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q] on fp32 tables (bf16 tables: forward only).  Saves lse [Q] and the
-    inputs; the backward recomputes the product chunk by chunk (softmax_chunk_plan) into one reused [Q, c_count] buffer."""
+    inputs; the backward recomputes the product chunk by chunk (softmax_chunk_plan) into one reused [Q, c_count] buffer.  filt: a
+    FilterIndex in place of the lists; it is not a tensor input and is kept by reference on ctx (never written, needs no grad), so the
+    head and the tail loss of a step share one index."""
 
     @staticmethod
-    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes):
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes, filt=None):
         batch = batch.reshape(-1, 3).contiguous()
         nodes, relations = dense(nodes), dense(relations)
         # range-checked here, once, for the forward and the backward (under deferred checks: clamped, the error queued)
         batch = _native.checked_queries(batch, nodes.shape[0], relations.shape[0], filt_q, filt_n, nodes.dtype == torch.bfloat16)
-        lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True)
+        # (with a FilterIndex there are no lists: checked_queries takes its unfiltered path -- no read-back under deferred checks)
+        lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True, filt=filt)
         ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse)
-        ctx.head, ctx.mean, ctx.chunk_bytes = bool(head), mean, chunk_bytes
+        ctx.head, ctx.mean, ctx.chunk_bytes, ctx.filt = bool(head), mean, chunk_bytes, filt
         loss = lse - tscore
         return loss.mean() if mean else loss
 
@@ -1357,7 +1440,7 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
             dqv = None
             for c_first, c_count in plan:
                 dS = _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
-                                                   Q if ctx.mean else 1, c_first, c_count, out=buf)
+                                                   Q if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt)
                 # both products are skinny (d wide): K is cut into slices, summed in a fixed order, where the output tiles alone would
                 # leave most of the chip idle
                 if dn is not None:                                            # candidate side: every row written once, nothing accumulated
@@ -1381,16 +1464,18 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
             dr = torch.zeros_like(rel) if need_r else None
             if need_b:
                 dsb, dpb, dob = torch.zeros_like(sbias), torch.zeros_like(pbias), torch.zeros_like(obias)
-        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None
+        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None, None
 
 
 def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
-                          reduction="mean", strips=0, chunk_bytes=None):
+                          reduction="mean", strips=0, chunk_bytes=None, filt=None):
     """1-N softmax cross-entropy of DistMult (an extension: the reference trains on sampled negatives only).  For each triple of `batch`
     (int64 [Q, 3]) every entity is scored as its head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- and
         loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q],
     `allowed` being every entity that is not on the int32 device lists (filt_q, filt_n); an entry on a query's own target is ignored (as in
     distmult_rank_all), so the target is always in the sum.  Returns the mean over the queries, or the vector with reduction="none".
+    filt: a FilterIndex in place of the lists (not both: ValueError) -- the same loss and gradients, bit for bit, with nothing built on
+    the host and nothing read back: under route deferred_checks = 1 the filtered step does not synchronise and can be captured.
     The [Q, N] logits never exist: the forward is one strip pass with a running (max, sum) per query (DESIGN.md 4.5) and keeps lse [Q];
     the backward computes the product again in chunks of candidate columns (softmax_chunk_plan: Q * c_count * 4 <= chunk_bytes, default
     SOFTMAX_CHUNK_BYTES) into one reused buffer dS and contracts each chunk on the matrix cores -- dnodes[chunk] = dS^T qv, every row
@@ -1406,6 +1491,7 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     if chunk_bytes is None:
         chunk_bytes = SOFTMAX_CHUNK_BYTES
     assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
+    _filter_args(filt, filt_q, filt_n, nodes)
     params = (nodes, relations, sbias, pbias, obias)
     if nodes.dtype == torch.bfloat16:
         for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
@@ -1416,7 +1502,7 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
             nodes = nodes.float()
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
-                                      chunk_bytes)
+                                      chunk_bytes, filt)
 
 
 class _MaskedCE(torch.autograd.Function):

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from torch_rgcn import _native
-from torch_rgcn.functional import distmult_rank_all, distmult_score_all, distmult_topk_all
+from torch_rgcn.functional import (FilterIndex, distmult_rank_all, distmult_score_all, distmult_topk_all,  # noqa: F401  (FilterIndex: re-exported)
+                                   distmult_topk_all_index)
 from torch_rgcn.layers import DistMult
 
 _SCORE_BYTES = 1 << 30     # score-matrix budget per chunk of queries
@@ -98,6 +99,21 @@ def _filter_index(true_triples, num_nodes):
     return idx
 
 
+_DEVICE_FILTER_CACHE = []      # [(true_triples object, num_nodes, device, FilterIndex)], kept like _FILTER_CACHE
+
+
+def _device_filter_index(true_triples, num_nodes, device):
+    """the FilterIndex of (true_triples, num_nodes) on `device`, built and uploaded on first use"""
+    device = torch.device(device)
+    for obj, n, dev, idx in _DEVICE_FILTER_CACHE:
+        if obj is true_triples and n == num_nodes and dev == device:
+            return idx
+    idx = FilterIndex(true_triples, num_nodes, device)
+    del _DEVICE_FILTER_CACHE[:-3]
+    _DEVICE_FILTER_CACHE.append((true_triples, num_nodes, device, idx))
+    return idx
+
+
 def filter_scores(scores, batch, true_triples, head=True):
     """scores of known true triples that are not the target -> -inf, in place (misc.py:40-58)"""
     rows, cols = _filter_index(true_triples, scores.shape[1]).lists(batch.cpu().numpy(), head)
@@ -105,8 +121,10 @@ def filter_scores(scores, batch, true_triples, head=True):
         _native.rank_filter(scores, torch.from_numpy(rows).to(scores.device), torch.from_numpy(cols).to(scores.device))
 
 
-def _rank_chunk(scores, batch, true_triples, head, filter_candidates):
-    if filter_candidates:
+def _rank_chunk(scores, batch, true_triples, head, filter_candidates, index=None):
+    if filter_candidates and index is not None:
+        _native.rank_filter_index(scores, batch, head, index)
+    elif filter_candidates:
         filter_scores(scores, batch, true_triples, head=head)
     raw, ties = _native.rank_count(scores, batch, head)
     return (raw + (ties - 1) // 2 + 1).tolist()
@@ -129,7 +147,7 @@ def _fused_batch(num_queries, num_nodes, dim):
 
 @torch.no_grad()
 def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hits_at_k=[1, 3, 10],
-             filter_candidates=True, verbose=True, fused=None):
+             filter_candidates=True, verbose=True, fused=None, device_filter=False):
     """(mrr, hits tuple, ranks): head queries for the whole test set first, then tail queries (misc.py:60-110).
 
     `batch_size` only bounds the score matrix of models without an `encode`/DistMult pair; the fast path scores as many
@@ -137,7 +155,10 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
 
     `fused` (extension; see use_fused): the fast path's second route counts the ranks in the product kernel and never writes the score
     matrix (`functional.distmult_rank_all`) -- the same ranks, memory O(Q N / 8) instead of O(4 Q N).  Models without
-    `encode` or DistMult keep the reference's route whatever `fused` says."""
+    `encode` or DistMult keep the reference's route whatever `fused` says.
+
+    `device_filter` (extension): the known completions come from a device-resident FilterIndex (built once per (true_triples, num_nodes,
+    device) and cached) on every route -- no filter list is formed on the host and none is uploaded per chunk.  The same ranks."""
     device = next(model.parameters()).device
     test_set = torch.as_tensor(test_set, dtype=torch.long)
     decoder = getattr(model, "scoring_function", None)
@@ -152,6 +173,7 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
             batch_size = max(batch_size, min(len(test_set), max(64, _SCORE_BYTES // (4 * num_nodes))))
         params = (decoder.relations.detach(), *((decoder.sbias.detach(), decoder.pbias.detach(), decoder.obias.detach())
                                                 if decoder.b_init else ()))
+    index = _device_filter_index(true_triples, num_nodes, device) if (filter_candidates and device_filter) else None
     ranks = []
     for head in (True, False):
         for fr in range(0, len(test_set), batch_size):
@@ -159,11 +181,11 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
             bn = batch.shape[0]
             if fuse:        # no score matrix: the filter lists become a bit mask, the counts come out of the product kernel
                 rows = cols = None
-                if filter_candidates:
+                if filter_candidates and index is None:
                     r, c = _filter_index(true_triples, num_nodes).lists(test_set[fr:fr + batch_size].numpy(), head)
                     if len(r):
                         rows, cols = torch.from_numpy(r).to(device), torch.from_numpy(c).to(device)
-                raw, ties, _ = distmult_rank_all(batch, head, x, *params, filt_q=rows, filt_n=cols)
+                raw, ties, _ = distmult_rank_all(batch, head, x, *params, filt_q=rows, filt_n=cols, filt=index)
                 ranks.extend((raw + (ties - 1) // 2 + 1).tolist())
                 continue
             if fast:        # (bf16 embeddings: the bf16 matrix instructions on the bf16 table, fp32 scores -- DESIGN.md 4.6)
@@ -174,7 +196,7 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
                 scores, _ = model(graph, torch.cat([ar, bexp] if head else [bexp, ar], dim=2))
                 scores = scores.float().contiguous()
             assert scores.shape == (bn, num_nodes)
-            ranks.extend(_rank_chunk(scores, batch, true_triples, head, filter_candidates))
+            ranks.extend(_rank_chunk(scores, batch, true_triples, head, filter_candidates, index))
         if verbose:
             print(f"  ranked {len(test_set)} {'head' if head else 'tail'} queries")
     mrr = sum(1.0 / r for r in ranks) / len(ranks)
@@ -211,7 +233,9 @@ def predict(model, graph, queries, num_nodes, k=10, head=False, true_triples=Non
 
     The graph is encoded once.  fused=None takes the product kernel's selecting epilogue (`functional.distmult_topk_all`; DESIGN.md 4.5:
     no score matrix) whenever k <= _native.TOPK_MAX; fused=False, or a larger k, sorts chunks of the materialised scores -- the same
-    answer.  An extension: the reference has no counterpart."""
+    answer.  `true_triples` may also be a FilterIndex (built from that pair, for num_nodes entities, on the model's device): the known
+    completions are then looked up on the device instead of in per-chunk host lists -- the same rows.  An extension: the reference has no
+    counterpart."""
     decoder = getattr(model, "scoring_function", None)
     if not (hasattr(model, "encode") and isinstance(decoder, DistMult)):
         raise TypeError("predict needs a model with an `encode` method and a DistMult `scoring_function`")
@@ -228,20 +252,28 @@ def predict(model, graph, queries, num_nodes, k=10, head=False, true_triples=Non
         batch_size = _topk_batch(len(queries), num_nodes, x.shape[1], k)
     else:       # the scores, the sorted scores and their int64 columns
         batch_size = min(len(queries), max(1, _SCORE_BYTES // (16 * num_nodes)))
+    index = true_triples if isinstance(true_triples, FilterIndex) else None
+    if index is not None and (index.num_nodes != num_nodes or index.device != x.device):
+        raise ValueError(f"the FilterIndex is for {index.num_nodes} entities on {index.device}, the model has {num_nodes} on {x.device}")
     ids, scores = [], []
     for fr in range(0, len(queries), max(batch_size, 1)):
         host = queries[fr:fr + batch_size]
         batch = host.to(device).contiguous()
         rows = cols = None
-        if true_triples is not None:
+        if true_triples is not None and index is None:
             r, c = _filter_index(true_triples, num_nodes).lists(host.cpu().numpy(), head, keep_target=True)
             if len(r):
                 rows, cols = torch.from_numpy(r).to(device), torch.from_numpy(c).to(device)
         if fuse:
-            i, s = distmult_topk_all(batch, head, x, *params, k=k, filt_q=rows, filt_n=cols)
+            if index is not None:
+                i, s = distmult_topk_all_index(batch, head, x, *params, k=k, filt=index)
+            else:
+                i, s = distmult_topk_all(batch, head, x, *params, k=k, filt_q=rows, filt_n=cols)
         else:
             sc = distmult_score_all(batch, head, x, *params)
-            if rows is not None:
+            if index is not None:
+                _native.rank_filter_index(sc, batch, head, index, keep_target=True)
+            elif rows is not None:
                 _native.rank_filter(sc, rows, cols)
             i, s = _topk_of_scores(sc, k)
         ids.append(i)
