@@ -898,6 +898,22 @@ RGCN_API int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int
                                             const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
                                             int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
                                             int32_t n_rel, int32_t d, void *stream);
+/* The same gradient cells on a bf16 entity table: nodes bf16 [n_nodes, d], rel and the biases fp32, dS fp32 row-major
+ * [Q, c_count] as above, the same chunk contract.  The product runs on v_mfma_f32_16x16x32_bf16 from the three bf16 terms of the fp32
+ * query vector nodes[fixed] * rel[p] (their sum is the vector exactly, as in rgcn_distmult_score_all_bf16): s is bit for bit the cell
+ * rgcn_distmult_score_all_bf16 stores and rgcn_distmult_lse_bf16 adds, so a row whose only allowed cell is its target gets
+ * exp(0) - 1 = 0.  lse [Q]: what rgcn_distmult_lse_bf16 returned for the same arguments.  16-byte loads of the entity rows when
+ * d % 8 == 0 and `nodes` is 16-byte aligned, element by element otherwise -- the choice the forward makes for the same table.
+ * workspace: rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d) bytes (the query terms 3 Q ceil32(d) bf16, 2 Q bias terms,
+ * the chunk's mask [Q][ceil(c_count / 32)]; no device is asked; 0 for arguments the call refuses), 16-byte aligned.  Errors as the fp32
+ * form: RGCN_EINVAL for a bad chunk, NULL or misaligned arguments, biases partly set and mean_over < 1; RGCN_EUNSUPPORTED beyond
+ * INT32_MAX workgroups; Q == 0 launches nothing; nothing is launched on a refused call.  No host synchronisation, no memset. */
+RGCN_API int64_t rgcn_distmult_softmax_grad_bf16_workspace_bytes(int64_t Q, int64_t c_count, int32_t d);
+RGCN_API int rgcn_distmult_softmax_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                             const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
+                                             int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                             int32_t n_rel, int32_t d, void *stream);
 /* Device-resident filter index: the known completions of one direction as a sorted table on the device, in place of
  * the per-call lists (filt_q, filt_n, F).  fkeys [K] (int64), STRICTLY ASCENDING, key = p * n_nodes + o for head queries (the known
  * heads of (?, p, o)) and p * n_nodes + s for tail queries; fptr [K + 1] (int64); fvals [fptr[K]] (int32), the completions of key k in
@@ -954,6 +970,11 @@ RGCN_API int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_t 
                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
                                                   int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
                                                   float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                   int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
+                                                   float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,9 @@
            Forward + backward: the fused route (default chunk budget, and 64 MiB chunks) against an ATen autograd step
            (nodes[s] * rel[p]) @ nodes.T -> F.cross_entropy, which holds the logits and their gradient.
   million  N = 1,000,000: the fused route alone (the logits would be 20 GB, with their gradient 40 GB).
+  bf16     at both sizes, the table of the case rounded to bf16 and trained: forward + backward on the upcast route (the table widened
+           to fp32, the fp32 kernels: the only route before bf16_backward existed) against the native route (bf16_backward="native"),
+           with the bytes each holds between its forward and its backward.
 The variants of a group ALTERNATE launch by launch (a drift of the shared host hits all alike); HIP events; median, minimum and quartiles
 of --steps after --warmup.  Peak memory: the rise of torch.cuda.max_memory_allocated over one call of each variant from an emptied
 cache.  No figure is a threshold: the fused forward recomputes nothing but writes nothing either, the fused backward computes the
@@ -96,6 +99,44 @@ def fused_step(nodes, rel, batch, chunk_bytes=None):
     return run
 
 
+def bf16_leg(nodes, rel, batch, steps, warmup):
+    """forward + backward of the bf16 table on both routes of bf16_backward: times, peak memory, the bytes held between the forward and
+    the backward, per-kernel times (softmax_grad / softmax_grad_bf16 among them), and how far the two routes' results are apart"""
+    from torch_rgcn import functional
+    nb = nodes.detach().to(torch.bfloat16).requires_grad_(True)
+
+    def step_of(route):
+        def run():
+            nb.grad = rel.grad = None
+            loss = functional.distmult_softmax_loss(batch, False, nb, rel, bf16_backward=route)
+            loss.backward(gradient=functional.unit_gradient(loss.device))
+            return loss
+        return run
+
+    def held_of(route):
+        nb.grad = rel.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        before = torch.cuda.memory_allocated()
+        loss = functional.distmult_softmax_loss(batch, False, nb, rel, bf16_backward=route)
+        torch.cuda.synchronize()
+        held = int(torch.cuda.memory_allocated() - before)
+        del loss
+        return held
+    step = {route: step_of(route) for route in ("upcast", "native")}
+    res = measure(step, steps, warmup)
+    out = {}
+    for route, run in step.items():
+        res[route]["held_between_forward_and_backward_bytes"] = held_of(route)
+        res[route]["kernels_ms"] = kernels_of(run)
+        out[route] = (float(run().detach()), nb.grad.float().clone())
+    res["fp32_table_bytes"] = 4 * nodes.numel()
+    res["loss"] = {route: out[route][0] for route in out}
+    res["dnodes_max_abs_difference_over_max"] = float((out["native"][1] - out["upcast"][1]).abs().max() / out["upcast"][1].abs().max())
+    res["native_step_over_upcast"] = round(res["native"]["ms_median"] / res["upcast"]["ms_median"], 3)
+    return res
+
+
 def aten_step(nodes, rel, batch):
     def run():
         nodes.grad = rel.grad = None
@@ -130,6 +171,8 @@ def wn18(steps, warmup, N=40_943):
     res["dnodes_max_abs_difference_over_max"] = float((g_fused - nodes.grad).abs().max() / nodes.grad.abs().max())
     res["fused_forward_over_materialised"] = round(res["forward"]["fused"]["ms_median"] / res["forward"]["score_all_logsumexp"]["ms_median"], 3)
     res["fused_step_over_aten"] = round(res["forward_backward"]["fused"]["ms_median"] / res["forward_backward"]["aten_matmul_cross_entropy"]["ms_median"], 3)
+    nodes.grad = rel.grad = None
+    res["bf16"] = bf16_leg(nodes, rel, batch, steps, warmup)
     return res
 
 
@@ -146,6 +189,8 @@ def million(steps, warmup, N=1_000_000):
     res["forward_backward"] = measure(step, steps, warmup)
     res["forward_backward"]["fused"]["kernels_ms"] = kernels_of(step["fused"])
     res["loss"] = float(step["fused"]().detach())
+    nodes.grad = rel.grad = None
+    res["bf16"] = bf16_leg(nodes, rel, batch, steps, warmup)
     return res
 
 

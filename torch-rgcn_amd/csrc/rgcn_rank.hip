@@ -12,11 +12,11 @@
 // because both operands use the same permutation and the sum over k does not care.
 // Second route (rgcn_distmult_rank_fused_*, utils/misc.py:40-58, 71-99): the same tile product with an epilogue that compares every score
 // with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.  Third (rgcn_distmult_topk_*):
-// an epilogue that selects the k best.  Fourth (rgcn_distmult_lse_*, rgcn_distmult_softmax_grad_f32; an extension, the reference trains on
+// an epilogue that selects the k best.  Fourth (rgcn_distmult_lse_*, rgcn_distmult_softmax_grad_*; an extension, the reference trains on
 // sampled negatives only): an epilogue that adds exp(score) for the 1-N softmax loss, and the gradient cells of that loss in column chunks.
 // Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select, add) first; then a tile-precision trait
 // (TileF32 / TileBf16) and the kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel,
-// strip_lse_kernel -- each written once over <Tile, VEC>, and softmax_grad_kernel (fp32); then the entry points.
+// strip_lse_kernel, softmax_grad_kernel -- each written once over <Tile, VEC>; then the entry points.
 #include <cmath>
 #include <cstdlib>
 
@@ -735,25 +735,26 @@ __global__ __launch_bounds__(WG) void lse_merge_kernel(const float2 *__restrict_
 // Gradient cells of the 1-N softmax loss, on the score-all grid cut to the candidate columns [c_first, c_first + c_count) (c_first a
 // multiple of 128: tiles and mask words align as in tile_count): dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),
 // a filtered cell 0; scale_q = gscale[per_query ? q : 0] * inv_q -- the upstream gradient is read on the device.  mask: the filter
-// bits of THIS chunk, [Q][mask_w] with bit 0 of word 0 = column c_first.  The product is recomputed (fp32 only): s is bit for bit the
-// cell the strip kernel added, so a row whose only cell is its target gets exp(0) - 1 = 0.
+// bits of THIS chunk, [Q][mask_w] with bit 0 of word 0 = column c_first.  The product is recomputed by the product loop of the
+// storage: s is bit for bit the cell the strip kernel of the same <Tile, VEC> added, so a row whose only cell is its target gets
+// exp(0) - 1 = 0.  dS is fp32 for both storages.
 struct GradRow { float lse, scale; long long tgt; unsigned w[2]; float *out; };
 
-template <bool VEC>
+template <class Tile, bool VEC>
 __global__ __launch_bounds__(WG) void softmax_grad_kernel(
-    const float *__restrict__ q, const float *__restrict__ nodes, TileDims dm, const float *__restrict__ qb, const float *__restrict__ cbias,
-    const long long *__restrict__ batch, const float *__restrict__ lse, const float *__restrict__ gscale, int per_query, float inv_q,
-    const unsigned *__restrict__ mask, long long mask_w, float *__restrict__ dS, int Q, long long N, long long c_first, long long c_count,
-    int head, int q_blocks) {
-  __shared__ __attribute__((aligned(16))) TileF32::Slabs slabs;
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const long long *__restrict__ batch, const float *__restrict__ lse, const float *__restrict__ gscale,
+    int per_query, float inv_q, const unsigned *__restrict__ mask, long long mask_w, float *__restrict__ dS, int Q, long long N,
+    long long c_first, long long c_count, int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
   const int wave = threadIdx.x >> 6, i = threadIdx.x & 15;
   const int qt = (blockIdx.x % q_blocks) * 128;
   const long long ct = c_first + (long long)(blockIdx.x / q_blocks) * 128;
-  const float *ga[2], *gb[2];
-  stage_rows(q, qt, Q, dm.d, ga);
+  const typename Tile::elem *ga[2], *gb[2];
+  stage_rows(q, qt, Q, Tile::q_stride(dm), ga);
   stage_rows(nodes, ct, N, dm.d, gb);
   f32x4 acc[4][4];
-  TileF32::product<VEC>(ga, gb, dm, slabs, acc);
+  Tile::template product<VEC>(ga, gb, dm, slabs, acc);
   const long long c0 = ct + (wave & 1) * 64;
   tile_epilogue(acc, qt + (wave >> 1) * 64, c0, Q, c_first + c_count, qb, head,
                 [&](int, int qrow) {
@@ -1356,14 +1357,15 @@ int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore
   return RGCN_OK;
 }
 
-// the workspace of a gradient-cell call: query vectors | query-side bias terms | the filter bits of the chunk [Q][ceil(c_count / 32)]
+// the workspace of a gradient-cell call: query vectors (fp32 [Q][d], or the three bf16 terms [3][Q][k_pad32(d)]) | query-side bias terms |
+// the filter bits of the chunk [Q][ceil(c_count / 32)]
 struct GradLayout { int64_t qv, qb, mask, total, mask_w; };
 
-inline GradLayout grad_layout(int64_t Q, int64_t c_count, int32_t d) {
+inline GradLayout grad_layout(int64_t Q, int64_t c_count, int32_t d, bool bf16) {
   GradLayout L;
   L.mask_w = (c_count + 31) / 32;
   L.qv = 0;
-  L.qb = L.qv + align16(Q * (int64_t)d * (int64_t)sizeof(float));
+  L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
   L.mask = L.qb + align16(2 * Q * (int64_t)sizeof(float));
   L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
   return L;
@@ -1412,13 +1414,18 @@ extern "C" int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int
 }
 
 extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
-  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d).total;
+  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d, false).total;
+}
+
+extern "C" int64_t rgcn_distmult_softmax_grad_bf16_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
+  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d, true).total;
 }
 
 namespace {
 
 // what the list form and the index form of the gradient-cell entry share: a.F fills the chunk's mask from the lists, a.ix.K from the index
-int softmax_grad(const StripArgs<float> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
+template <class Tile>
+int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
                  int64_t c_count, float *dS) {
   const int64_t Q = a.Q, n_nodes = a.n_nodes;
   const int32_t head = a.head, d = a.d;
@@ -1428,9 +1435,10 @@ int softmax_grad(const StripArgs<float> &a, const float *lse, const float *gscal
   if (Q == 0) return RGCN_OK;
   const int64_t qbl = (Q + 127) / 128, nwg = ((c_count + 127) / 128) * qbl;
   if (nwg > INT32_MAX) { rgcn_set_error("%s: too many cells in one call; take a smaller chunk", a.name); return RGCN_EUNSUPPORTED; }
-  const GradLayout L = grad_layout(Q, c_count, d);
+  const GradLayout L = grad_layout(Q, c_count, d, is_bf16<Tile>);
   char *ws = static_cast<char *>(a.workspace);
-  float *qv = reinterpret_cast<float *>(ws + L.qv), *qb = reinterpret_cast<float *>(ws + L.qb);
+  typename Tile::elem *qv = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
+  float *qb = reinterpret_cast<float *>(ws + L.qb);
   unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
   hipStream_t st = (hipStream_t)a.stream;
   const long long *b = reinterpret_cast<const long long *>(a.batch);
@@ -1439,11 +1447,11 @@ int softmax_grad(const StripArgs<float> &a, const float *lse, const float *gscal
     hipLaunchKernelGGL(chunk_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
                        (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, b, head, (long long)c_first, (long long)(c_first + c_count));
   if (a.ix.K) launch_index_mask(st, mask, L.mask_w, a.ix, b, Q, head, n_nodes, 0, c_first, c_first + c_count);
-  launch_query<TileF32>(st, b, Q, head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, qv, qb, d);
+  launch_query<Tile>(st, b, Q, head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, qv, qb, d);
   const float *qb1 = a.sbias ? qb : nullptr, *cb1 = a.sbias ? (head ? a.sbias : a.obias) : nullptr;
-  with_vec<TileF32>(a.nodes, d, [&](auto vec) {
-    hipLaunchKernelGGL((softmax_grad_kernel<decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const float *)qv, a.nodes,
-                       tile_dims<TileF32>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
+  with_vec<Tile>(a.nodes, d, [&](auto vec) {
+    hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const typename Tile::elem *)qv, a.nodes,
+                       tile_dims<Tile>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
                        (int)Q, (long long)n_nodes, (long long)c_first, (long long)c_count, head, (int)qbl);
   });
   HIP_TRY(hipGetLastError());
@@ -1458,7 +1466,7 @@ extern "C" int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, i
                                               int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
                                               int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return softmax_grad({"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes, d,
+  return softmax_grad<TileF32>({"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes, d,
                        stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
 }
 
@@ -1468,8 +1476,29 @@ extern "C" int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_
                                                     int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
                                                     float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return softmax_grad({"distmult_softmax_grad_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0, workspace, n_nodes,
+  return softmax_grad<TileF32>({"distmult_softmax_grad_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0, workspace, n_nodes,
                        d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                               const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                               const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
+                                               int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                               int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileBf16>({"distmult_softmax_grad_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace,
+                                 n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                     const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                     const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                     int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
+                                                     float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileBf16>({"distmult_softmax_grad_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
+                                 workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
+                                 c_first, c_count, dS);
 }
 
 // ------------------------------------------------------------------ device-resident filter index: the mask and the materialised route

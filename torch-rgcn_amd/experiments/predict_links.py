@@ -9,6 +9,8 @@ training.objective (an extension, absent in the reference): "negative-sampling" 
 (softmax cross-entropy of every sampled positive against ALL entities, tails and heads; configs/rgcn/lp-WN18-1n.yaml);
 training.filtered (1-n only, default false; configs/rgcn/lp-WN18-1n-filtered.yaml): the other known completions of a query -- from the
 TRAINING triples only -- are left out of its softmax, looked up in a device-resident FilterIndex, so the step is captured all the same
+training.bf16 (1-n only, default false; configs/rgcn/lp-WN18-1n-bf16.yaml): the model is put into bf16 (model.bfloat16()) before the
+optimiser is built and both softmax terms run the native bf16 backward -- no fp32 image of the entity table exists during training
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""
@@ -49,6 +51,9 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     train_filtered = bool(training.get("filtered", False))
     if train_filtered and not one_to_n:
         raise ValueError("training.filtered needs training.objective: 1-n (sampled negatives are not filtered)")
+    train_bf16 = bool(training.get("bf16", False))
+    if train_bf16 and not one_to_n:
+        raise ValueError("training.bf16 needs training.objective: 1-n (the native bf16 backward is the 1-N softmax loss's)")
     max_epochs = epochs or training.get("epochs", 5000)
     graph_batch_size = training.get("graph_batch_size")
     sampling_function = select_sampling(training.get("sampling_method", "uniform"))
@@ -95,6 +100,9 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     else:
         raise NotImplementedError(f"'{encoder['model']}' encoder has not been implemented!")
     model = kind(nnodes=num_nodes, nrel=num_relations, encoder_config=encoder, decoder_config=decoder).to(device)
+    if train_bf16:
+        model = model.bfloat16()
+    loss_kw = {"bf16_backward": "native"} if train_bf16 else {}
     opt_cfg = training.get("optimiser", {"algorithm": "adam", "learn_rate": 0.01, "weight_decay": 0.0})
     if opt_cfg["algorithm"] not in OPTIMISERS:
         raise NotImplementedError(f"'{opt_cfg['algorithm']}' optimiser has not been implemented!")
@@ -153,8 +161,8 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
         if one_to_n:      # 1-N softmax: half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
             x = model.encode(graph)
             decoder_ = model.scoring_function
-            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False, filt=train_filter) +
-                          decoder_.softmax_loss(batch_idx, x, head=True, filt=train_filter))
+            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False, filt=train_filter, **loss_kw) +
+                          decoder_.softmax_loss(batch_idx, x, head=True, filt=train_filter, **loss_kw))
             return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
         predictions, penalty = model(graph, batch_idx)
         return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty

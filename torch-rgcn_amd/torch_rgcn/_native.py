@@ -2665,11 +2665,11 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
                           filt=None):
     """dS fp32 [Q, c_count]: the gradient cells of the 1-N softmax loss on the candidate columns [c_first, c_first + c_count),
     scale_q (exp(s[q, c] - lse[q]) - [c == target_q]), filtered cells 0; scale_q = gscale / mean_over with gscale a device float [1] or
-    [Q] (never read back).  fp32 only.  lse: distmult_lse's of the same arguments.  The caller has range-checked the triples and the
-    lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to write into.  filt: a functional.FilterIndex in
-    place of the lists -- the chunk's mask is filled from it (profile tag softmax_grad_index)."""
+    [Q] (never read back).  fp32 or bf16 nodes (rel and biases fp32; dS is fp32 either way).  lse: distmult_lse's of the same arguments.
+    The caller has range-checked the triples and the lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to
+    write into.  filt: a functional.FilterIndex in place of the lists -- the chunk's mask is filled from it.  Profile tags:
+    softmax_grad[_index][_bf16]."""
     bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n)
-    assert not bf16, "distmult_softmax_grad is fp32 only"
     _req(lse, "lse"); _req(gscale, "gscale")
     assert lse.shape == (Q,) and gscale.numel() in (1, Q), "lse [Q]; gscale [1] or [Q]"
     assert c_first % 128 == 0 and c_count >= 1 and 0 <= c_first and c_first + c_count <= N, "a chunk starts on a multiple of 128 inside [0, N)"
@@ -2679,19 +2679,33 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     _req(out, "out")
     assert out.numel() >= Q * c_count
     dS = out.view(-1)[:Q * c_count].view(Q, c_count)
-    ws = torch.empty(max(int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d)), 16), device=dev, dtype=torch.uint8)
+    ws_bytes = lib().rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d) if bf16 else \
+        lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d)
+    ws = torch.empty(max(int(ws_bytes), 16), device=dev, dtype=torch.uint8)
     per_query = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0
     if filt is not None:
         ix = _index_args(filt, head, N, dev, filt_q)
-        with _on(dev), _timed("softmax_grad_index"):
-            _check(lib().rgcn_distmult_softmax_grad_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                              _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
-                                                              int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
-                                                              _stream(dev)), "distmult_softmax_grad_index")
+        with _on(dev), _timed("softmax_grad_index_bf16" if bf16 else "softmax_grad_index"):
+            if bf16:
+                _check(lib().rgcn_distmult_softmax_grad_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                                   _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
+                                                                   int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
+                                                                   _stream(dev)), "distmult_softmax_grad_index_bf16")
+            else:
+                _check(lib().rgcn_distmult_softmax_grad_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
+                                                                  _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
+                                                                  int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
+                                                                  _stream(dev)), "distmult_softmax_grad_index")
         return dS
-    with _on(dev), _timed("softmax_grad"):
-        _check(lib().rgcn_distmult_softmax_grad_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                                    _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
-                                                    per_query, int(mean_over), c_first, c_count,
-                                                    _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad")
+    with _on(dev), _timed("softmax_grad_bf16" if bf16 else "softmax_grad"):
+        if bf16:
+            _check(lib().rgcn_distmult_softmax_grad_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                                         _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
+                                                         per_query, int(mean_over), c_first, c_count,
+                                                         _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad_bf16")
+        else:
+            _check(lib().rgcn_distmult_softmax_grad_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
+                                                        _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
+                                                        per_query, int(mean_over), c_first, c_count,
+                                                        _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad")
     return dS

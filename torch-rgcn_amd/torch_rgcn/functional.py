@@ -1400,8 +1400,10 @@ def softmax_chunk_plan(Q, N, chunk_bytes):
 
 
 class _DistMultSoftmaxLoss(torch.autograd.Function):
-    """loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q] on fp32 tables (bf16 tables: forward only).  Saves lse [Q] and the
-    inputs; the backward recomputes the product chunk by chunk (softmax_chunk_plan) into one reused [Q, c_count] buffer.  filt: a
+    """loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q] on an fp32 or a bf16 table (relations and biases fp32).  Saves lse [Q]
+    and the inputs; the backward recomputes the product chunk by chunk (softmax_chunk_plan) into one reused [Q, c_count] buffer.  A bf16
+    table is saved as it is and never widened as a whole: the gradient cells come from the bf16 kernel, the two contractions stay fp32
+    (the chunk's rows are widened into one reused buffer), dnodes is summed in fp32 and rounded to bf16 once at the end.  filt: a
     FilterIndex in place of the lists; it is not a tensor input and is kept by reference on ctx (never written, needs no grad), so the
     head and the tail loss of a step share one index."""
 
@@ -1429,8 +1431,11 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
             if not _is_unit(g):
                 g = dense(g.to(torch.float32))
             anchor, p = batch[:, 2 if ctx.head else 0], batch[:, 1]
-            qv = nodes[anchor] * rel[p]                                       # the query vectors, as the query kernel forms them
+            bf16 = nodes.dtype == torch.bfloat16
+            qv = nodes[anchor].float() * rel[p]                               # the query vectors, as the query kernel forms them (.float(): bf16 rows)
             plan = softmax_chunk_plan(Q, N, ctx.chunk_bytes)
+            # bf16 table: the rows of a chunk widened for the query-side product, one buffer for every chunk (the first chunk is the widest)
+            wide = torch.empty(plan[0][1], d, device=dev, dtype=torch.float32) if bf16 and (need_n or need_r) else None
             buf = torch.empty(Q * plan[0][1], device=dev, dtype=torch.float32)
             dn = torch.empty(N, d, device=dev, dtype=torch.float32) if need_n else None
             # the candidate-side bias gradient is dS^T times a column of ones: a product of its own into its own [N, 1] column (beside qv
@@ -1448,12 +1453,17 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
                 if cand is not None:
                     _native.gemm(dS, ones, trans_a=True, split_k=_split_k(Q, c_count, 1), out=cand[c_first:c_first + c_count])
                 if need_n or need_r:                                          # query side: the chunks' partials added in chunk order
-                    part = _native.gemm(dS, nodes[c_first:c_first + c_count], split_k=_split_k(c_count, Q, d))
+                    rows = nodes[c_first:c_first + c_count]
+                    if wide is not None:
+                        rows = wide[:c_count].copy_(rows)
+                    part = _native.gemm(dS, rows, split_k=_split_k(c_count, Q, d))
                     dqv = part if dqv is None else dqv.add_(part)
             if need_n:
                 dn.index_add_(0, anchor, dqv * rel[p])
+                if bf16:
+                    dn = dn.to(torch.bfloat16)                                # fp32 sums, one rounding
             if need_r:
-                dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor])
+                dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor].float())
             if need_b:
                 cand = cand.view(N)
                 zeros = torch.zeros(N, device=dev)
@@ -1468,7 +1478,7 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
 
 
 def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
-                          reduction="mean", strips=0, chunk_bytes=None, filt=None):
+                          reduction="mean", strips=0, chunk_bytes=None, filt=None, bf16_backward="upcast"):
     """1-N softmax cross-entropy of DistMult (an extension: the reference trains on sampled negatives only).  For each triple of `batch`
     (int64 [Q, 3]) every entity is scored as its head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- and
         loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q],
@@ -1483,11 +1493,19 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     dnodes[anchor_q] += dqv[q] * rel[p_q] and drel[p_q] += dqv[q] * nodes[anchor_q] are index_add_ (fp32 atomics over Q rows), so two
     runs may differ in the last bits of those rows.  The query-side bias gradients (pbias, and obias if head else sbias) are
     sum_n dS[q, n] = 0 in exact arithmetic and are returned as zeros.  strips: as in distmult_rank_all.
-    bf16 nodes (DESIGN.md 4.6): with nothing that requires grad the bf16 kernels run on the bf16 table -- a test-set cross-entropy --;
-    otherwise the table is widened to fp32 here, the fp32 route runs and autograd rounds dnodes once on the way back: the upcast policy,
-    CORRECTNESS ONLY (there is no native bf16 backward).  Relations and biases are fp32, or bf16 with bf16 nodes (widened here)."""
+    bf16 nodes: with nothing that requires grad the bf16 kernels run on the bf16 table -- a test-set cross-entropy.
+    When something requires grad, bf16_backward chooses the route.  "upcast" (the default): the table is widened to fp32 here, the fp32
+    route runs and autograd rounds dnodes once on the way back -- an fp32 copy of the whole table lives from the forward to the backward.
+    "native": the table is never widened.  The forward is the bf16 strip kernel and saves the bf16 table itself; the backward takes the
+    gradient cells of each chunk from the bf16 kernel (the product on the bf16 matrix instructions, from the three bf16 terms of the fp32
+    query vector nodes[anchor].float() * rel[p]), contracts them in fp32 as above -- only the chunk's rows of the table are widened, into
+    one reused [c_count, d] buffer --, accumulates dnodes in fp32, the anchor rows' index_add_ included, and rounds it to bf16 once.
+    drel and the bias gradients are fp32.  With fp32 nodes the keyword has no effect.  Relations and biases are fp32, or bf16 with bf16
+    nodes (widened here: they are small)."""
     if reduction not in ("mean", "none"):
         raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    if bf16_backward not in ("upcast", "native"):
+        raise ValueError(f"bf16_backward must be 'upcast' or 'native', got {bf16_backward!r}")
     if chunk_bytes is None:
         chunk_bytes = SOFTMAX_CHUNK_BYTES
     assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
@@ -1499,7 +1517,7 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
                 raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
         widen = lambda t: None if t is None else t.float()     # noqa: E731  (a no-op on fp32)
         relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
+        if bf16_backward == "upcast" and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
             nodes = nodes.float()
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
                                       chunk_bytes, filt)
