@@ -1063,16 +1063,18 @@ inline int64_t fused_default_strips(int64_t Q, int64_t n_nodes, int64_t n_cu) {
   return std::max<int64_t>(1, std::min(n_tiles, (2 * std::min(n_cu, FUSED_CU_CAP) + qbl - 1) / qbl));
 }
 
-// The workspace of a strip route: query vectors | query-side bias terms | the strips' partials | filter bits.  bytes_per_cell: what a
-// (strip half, query) cell of the partials holds -- the (greater, equal) pair of the evaluator, k keys of the top-k.
+// The workspace of a query call: query vectors (fp32 [Q][d], or the three bf16 terms [3][Q][k_pad32(d)]) | query-side bias terms | the
+// strips' partials | the filter bits of its n_cols candidate columns, [Q][ceil(n_cols / 32)].  bytes_per_cell: what a (strip half, query)
+// cell of the partials holds -- the (greater, equal) pair of the evaluator, k keys of the top-k; 0 for the gradient cells, which have no
+// strips and mask one chunk of columns.
 // strips = 0: room for the default of any device up to FUSED_CU_CAP units, by a bound that grows with Q and with N:
 // strips * Q <= min(n_tiles * Q, 2 * CAP * 128 + Q)
 struct StripLayout { int64_t qv, qb, part, mask, total, mask_w; };
 
-inline StripLayout strip_layout(int64_t Q, int64_t n_nodes, int32_t d, int64_t strips, bool bf16, int64_t bytes_per_cell) {
+inline StripLayout strip_layout(int64_t Q, int64_t n_cols, int32_t d, int64_t strips, bool bf16, int64_t bytes_per_cell) {
   StripLayout L;
-  L.mask_w = (n_nodes + 31) / 32;
-  const int64_t n_tiles = (n_nodes + 127) / 128;
+  L.mask_w = (n_cols + 31) / 32;
+  const int64_t n_tiles = (n_cols + 127) / 128;
   const int64_t cells = strips > 0 ? strips * Q : std::min(n_tiles * Q, 2 * FUSED_CU_CAP * 128 + Q);
   L.qv = 0;
   L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
@@ -1132,10 +1134,10 @@ int strip_check(const StripArgs<E> &a, bool bad_own, const char *hint) {
   return RGCN_OK;
 }
 
-// a strip call that passed its checks (Q > 0): the grid, the carved workspace and the operands of its kernels
+// a query call that passed its checks (Q > 0): the grid, the carved workspace and the operands of its kernels
 template <class Tile>
 struct StripCall {
-  int dev;
+  int dev;                        // dev, n_strips, part: the strip roles only
   int64_t qbl, n_strips, mask_w;
   hipStream_t st;
   const long long *b;
@@ -1146,24 +1148,18 @@ struct StripCall {
   const unsigned *mask;           // NULL without a filter
 };
 
-// The rest of the preamble: the strips (too_many(n_strips): the caller's bound on them, `what` names it in the message), the workspace
-// carved, the filter bits built and the query kernel of the storage launched.
-template <class Tile, class TooMany>
-int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, TooMany too_many, const char *what,
+// What every role does before its own kernels: the workspace carved (strip_layout over the columns [c_first, c_first + c_count)), the
+// operand fields of `c` filled, the filter bits of those columns built and the query kernel of the storage launched.  chunk: the mask is
+// a chunk's (the gradient cells) and chunk_mask_kernel fills it from the lists; else it spans the table and rank_mask_kernel does.
+template <class Tile>
+int query_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, bool chunk, int64_t c_first, int64_t c_count,
                 StripCall<Tile> &c) {
-  int n_cu = 0;
-  HIP_TRY(launch_device(&c.dev, &n_cu));
-  c.qbl = (a.Q + 127) / 128;
-  c.n_strips = a.strips > 0 ? a.strips : fused_default_strips(a.Q, a.n_nodes, n_cu);
-  if (c.n_strips * c.qbl > INT32_MAX || too_many(c.n_strips)) {
-    rgcn_set_error("%s: too many %s in one call; split the batch", a.name, what);
-    return RGCN_EUNSUPPORTED;
-  }
-  const StripLayout L = strip_layout(a.Q, a.n_nodes, a.d, a.strips, is_bf16<Tile>, bytes_per_cell);
+  const StripLayout L = strip_layout(a.Q, c_count, a.d, a.strips, is_bf16<Tile>, bytes_per_cell);
   char *ws = static_cast<char *>(a.workspace);
   typename Tile::elem *q = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
   float *qb = reinterpret_cast<float *>(ws + L.qb);
   unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  c.qbl = (a.Q + 127) / 128;
   c.mask_w = L.mask_w;
   c.st = (hipStream_t)a.stream;
   c.b = reinterpret_cast<const long long *>(a.batch);
@@ -1174,12 +1170,32 @@ int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
   c.part = ws + L.part;
   c.mask = mask;
   if (mask) HIP_TRY(zero_async(mask, (size_t)(a.Q * L.mask_w) * sizeof(unsigned), c.st));
-  if (a.F)
-    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, c.st, mask,
-                       (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head, keep_target);
-  if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.head, a.n_nodes, keep_target, 0, a.n_nodes);
+  const dim3 list_grid((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16));
+  if (a.F && chunk)
+    hipLaunchKernelGGL(chunk_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
+                       (long long)c_first, (long long)(c_first + c_count));
+  else if (a.F)
+    hipLaunchKernelGGL(rank_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
+                       keep_target);
+  if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.head, a.n_nodes, keep_target, c_first, c_first + c_count);
   launch_query<Tile>(c.st, c.b, a.Q, a.head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, q, qb, a.d);
   return RGCN_OK;
+}
+
+// The preamble of a strip role: the strips (too_many(n_strips): the caller's bound on them, `what` names it in the message), then
+// query_begin over the whole table.
+template <class Tile, class TooMany>
+int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, TooMany too_many, const char *what,
+                StripCall<Tile> &c) {
+  int n_cu = 0;
+  HIP_TRY(launch_device(&c.dev, &n_cu));
+  const int64_t qbl = (a.Q + 127) / 128;
+  c.n_strips = a.strips > 0 ? a.strips : fused_default_strips(a.Q, a.n_nodes, n_cu);
+  if (c.n_strips * qbl > INT32_MAX || too_many(c.n_strips)) {
+    rgcn_set_error("%s: too many %s in one call; split the batch", a.name, what);
+    return RGCN_EUNSUPPORTED;
+  }
+  return query_begin<Tile>(a, bytes_per_cell, keep_target, false, 0, a.n_nodes, c);
 }
 
 template <class Tile>
@@ -1357,18 +1373,9 @@ int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore
   return RGCN_OK;
 }
 
-// the workspace of a gradient-cell call: query vectors (fp32 [Q][d], or the three bf16 terms [3][Q][k_pad32(d)]) | query-side bias terms |
-// the filter bits of the chunk [Q][ceil(c_count / 32)]
-struct GradLayout { int64_t qv, qb, mask, total, mask_w; };
-
-inline GradLayout grad_layout(int64_t Q, int64_t c_count, int32_t d, bool bf16) {
-  GradLayout L;
-  L.mask_w = (c_count + 31) / 32;
-  L.qv = 0;
-  L.qb = L.qv + align16(bf16 ? 3 * Q * k_pad32(d) * (int64_t)sizeof(uint16_t) : Q * (int64_t)d * (int64_t)sizeof(float));
-  L.mask = L.qb + align16(2 * Q * (int64_t)sizeof(float));
-  L.total = L.mask + align16(Q * L.mask_w * (int64_t)sizeof(unsigned));
-  return L;
+// the workspace of a gradient-cell call: strip_layout without partials, the mask as wide as the chunk
+inline int64_t softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d, bool bf16) {
+  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : strip_layout(Q, c_count, d, 0, bf16, 0).total;
 }
 
 }  // namespace
@@ -1414,11 +1421,11 @@ extern "C" int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int
 }
 
 extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
-  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d, false).total;
+  return softmax_grad_workspace_bytes(Q, c_count, d, false);
 }
 
 extern "C" int64_t rgcn_distmult_softmax_grad_bf16_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
-  return (Q < 0 || c_count <= 0 || d <= 0) ? 0 : grad_layout(Q, c_count, d, true).total;
+  return softmax_grad_workspace_bytes(Q, c_count, d, true);
 }
 
 namespace {
@@ -1427,32 +1434,18 @@ namespace {
 template <class Tile>
 int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
                  int64_t c_count, float *dS) {
-  const int64_t Q = a.Q, n_nodes = a.n_nodes;
-  const int32_t head = a.head, d = a.d;
-  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > n_nodes - c_count || mean_over < 1;
+  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > a.n_nodes - c_count || mean_over < 1;
   const float inv_q = 1.0f / (float)mean_over;
-  if (int rc = strip_check(a, bad_chunk || (Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
-  if (Q == 0) return RGCN_OK;
-  const int64_t qbl = (Q + 127) / 128, nwg = ((c_count + 127) / 128) * qbl;
+  if (int rc = strip_check(a, bad_chunk || (a.Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
+  if (a.Q == 0) return RGCN_OK;
+  const int64_t nwg = ((c_count + 127) / 128) * ((a.Q + 127) / 128);
   if (nwg > INT32_MAX) { rgcn_set_error("%s: too many cells in one call; take a smaller chunk", a.name); return RGCN_EUNSUPPORTED; }
-  const GradLayout L = grad_layout(Q, c_count, d, is_bf16<Tile>);
-  char *ws = static_cast<char *>(a.workspace);
-  typename Tile::elem *qv = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
-  float *qb = reinterpret_cast<float *>(ws + L.qb);
-  unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
-  hipStream_t st = (hipStream_t)a.stream;
-  const long long *b = reinterpret_cast<const long long *>(a.batch);
-  if (mask) HIP_TRY(zero_async(mask, (size_t)(Q * L.mask_w) * sizeof(unsigned), st));
-  if (a.F)
-    hipLaunchKernelGGL(chunk_mask_kernel, dim3((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16)), dim3(WG), 0, st, mask,
-                       (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, b, head, (long long)c_first, (long long)(c_first + c_count));
-  if (a.ix.K) launch_index_mask(st, mask, L.mask_w, a.ix, b, Q, head, n_nodes, 0, c_first, c_first + c_count);
-  launch_query<Tile>(st, b, Q, head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, qv, qb, d);
-  const float *qb1 = a.sbias ? qb : nullptr, *cb1 = a.sbias ? (head ? a.sbias : a.obias) : nullptr;
-  with_vec<Tile>(a.nodes, d, [&](auto vec) {
-    hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const typename Tile::elem *)qv, a.nodes,
-                       tile_dims<Tile>(Q, d), qb1, cb1, b, lse, gscale, (int)per_query, inv_q, (const unsigned *)mask, (long long)L.mask_w, dS,
-                       (int)Q, (long long)n_nodes, (long long)c_first, (long long)c_count, head, (int)qbl);
+  StripCall<Tile> c;
+  if (int rc = query_begin<Tile>(a, 0, 0, true, c_first, c_count, c)) return rc;       // no partials, keep_target = 0, the chunk's own mask
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b,
+                       lse, gscale, (int)per_query, inv_q, c.mask, (long long)c.mask_w, dS, (int)a.Q, (long long)a.n_nodes, (long long)c_first,
+                       (long long)c_count, a.head, (int)c.qbl);
   });
   HIP_TRY(hipGetLastError());
   return RGCN_OK;

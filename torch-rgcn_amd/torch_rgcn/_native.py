@@ -2137,12 +2137,59 @@ def bce_head(scores, labels):
     return loss, ds
 
 
+def _req_params(nodes, rel, sbias, pbias, obias, bf16=False):
+    """what every DistMult entry requires of its parameters: the entity table fp32, or bf16 with bf16=True, the relation
+    table and the biases fp32 (_req: on the device, contiguous, aligned); the biases all set or all None; two tables of one width"""
+    _req(nodes, "nodes", torch.bfloat16 if bf16 else torch.float32); _req(rel, "relations")
+    for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
+        _req(b, n)
+    assert (sbias is None) == (pbias is None) == (obias is None), "DistMult biases must be all set or all None"
+    assert nodes.dim() == 2 and rel.dim() == 2 and rel.shape[1] == nodes.shape[1], "relation and node embeddings differ in width"
+
+
+def _triples_in_range(batch, N, n_rel, bf16):
+    """the immediate range check of the triples of `batch` (int64 [Q, 3]) against N entities and n_rel relations, read back at once: the
+    kernels that score all candidates index the tables with them unchecked.  Raises as the storage's scoring route does: fp32
+    AssertionError, bf16 IndexError.  Needs no device tensor (_req states that requirement)."""
+    if not batch.shape[0]:
+        return
+    lo, hi = batch.amin(0), batch.amax(0)
+    if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < n_rel):
+        raise (IndexError if bf16 else AssertionError)("triple index out of range")
+
+
+def _filter_lists_in_range(filt_q, filt_n, Q, N):
+    """the immediate range check of the filter lists (int32, None or empty = no filter): an entry out of range would set a bit outside
+    the [Q][ceil(N / 32)] mask"""
+    if filt_q is None or not filt_q.shape[0]:
+        return
+    if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
+        raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+
+
+def _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q=None, filt_n=None, strips=0):
+    """what a call that scores every entity for the queries of `batch` requires, stated once for score_all, rank_fused, topk, lse and
+    softmax_grad: the parameters of the storage (_req_params), batch int64 [Q, 3], the filter lists int32, both or neither and of one
+    length, strips a non-negative int.  _req comes first: a CPU tensor raises RuntimeError before any assert.  -> (Q, N, d, F)"""
+    _req_params(nodes, rel, sbias, pbias, obias, bf16)
+    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
+    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
+    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
+        "filt_q and filt_n: two int32 lists of one length, or neither"
+    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
+    return batch.shape[0], nodes.shape[0], nodes.shape[1], (0 if filt_q is None else filt_q.shape[0])
+
+
+def _query_prefix(batch, head, nodes, rel, sbias, pbias, obias):
+    """what the argument lists of those entry points share, bound once per call: the pointers of batch, nodes, rel and the three biases,
+    head as 0 / 1, the relation count and the stream -> (batch, head, nodes, rel, sbias, pbias, obias, n_rel, stream)"""
+    return _dp(batch), 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), rel.shape[0], _stream(nodes.device)
+
+
 def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
     """scores [T]; ranks=True: (scores, [row sizes, ranks]) -- the counting pass of the backward's two CSRs done by the scoring kernel
     (see distmult_csrs; the list is consumed by it)"""
-    _req(nodes, "nodes"); _req(rel, "relations"); _req(triples, "triples", torch.int64)
-    for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-        _req(b, n)
+    _req_params(nodes, rel, sbias, pbias, obias); _req(triples, "triples", torch.int64)
     T = triples.shape[0]
     scores = torch.empty(T, device=nodes.device, dtype=torch.float32)
     err = _i32(1, nodes.device)
@@ -2161,24 +2208,15 @@ def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
 def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None):
     """scores [Q, N] of every entity as head (head=True) or tail of each triple of `batch` (int64 [Q,3], device);
     utils/misc.py:71-88 without the [bn, N, 3] candidate tensor."""
-    _req(nodes, "nodes"); _req(rel, "relations"); _req(batch, "batch", torch.int64)
-    for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-        _req(b, n)
-    Q, (N, d) = batch.shape[0], nodes.shape
-    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
-    assert rel.shape[1] == d, "relation and node embeddings differ in width"
-    if Q:
-        lo, hi = batch.amin(0), batch.amax(0)
-        assert int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0], \
-            "triple index out of range"
+    Q, N, d, _ = _req_queries(batch, nodes, rel, sbias, pbias, obias, False)
+    _triples_in_range(batch, N, rel.shape[0], False)
     scores = out if out is not None else torch.empty(Q, N, device=nodes.device, dtype=torch.float32)
     assert scores.shape == (Q, N) and scores.is_contiguous() and scores.dtype == torch.float32
     qvec = torch.empty(Q, d, device=nodes.device, dtype=torch.float32)
     qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     with _on(nodes.device), _timed("score_all"):
-        _check(lib().rgcn_distmult_score_all_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias),
-                                                 _dp(pbias), _dp(obias), _dp(qvec), _dp(qb), _dp(scores), N,
-                                                 rel.shape[0], d, _stream(nodes.device)), "distmult_score_all")
+        _check(lib().rgcn_distmult_score_all_f32(b, Q, h, nd, rl, sb, pb, ob, _dp(qvec), _dp(qb), _dp(scores), N, R, d, st), "distmult_score_all")
     return scores
 
 
@@ -2279,18 +2317,9 @@ def distmult_bwd_nodes(triples, ranks, nodes, rel, gs):
 # once per call); dnodes bf16, an fp32 sum per entity rounded once.
 
 
-def _req_distmult_bf16(nodes, rel, sbias, pbias, obias):
-    _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
-    if (sbias is None) != (pbias is None) or (sbias is None) != (obias is None):
-        raise AssertionError("DistMult biases must be all set or all None")
-    for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-        _req(b, n)
-    assert nodes.dim() == 2 and rel.dim() == 2 and rel.shape[1] == nodes.shape[1], "relation and node embeddings differ in width"
-
-
 def distmult_fwd_bf16(triples, nodes, rel, sbias, pbias, obias, ranks=False):
     """distmult_fwd for bf16 nodes: fp32 scores [T]; ranks=True as there (the CSR counting pass rides along)"""
-    _req_distmult_bf16(nodes, rel, sbias, pbias, obias); _req(triples, "triples", torch.int64)
+    _req_params(nodes, rel, sbias, pbias, obias, bf16=True); _req(triples, "triples", torch.int64)
     T = triples.shape[0]
     scores = torch.empty(T, device=nodes.device, dtype=torch.float32)
     err = _i32(1, nodes.device)
@@ -2357,21 +2386,16 @@ def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obi
     query vectors carried as three bf16 terms -- the sums of the fp32 evaluator on the widened table, in another order.  The C entry does not
     range-check the triples on the device (neither does the fp32 one): this wrapper does, and raises IndexError; whoever calls
     rgcn_distmult_score_all_bf16 directly passes entities in [0, N) and predicates in [0, n_rel)"""
-    _req_distmult_bf16(nodes, rel, sbias, pbias, obias); _req(batch, "batch", torch.int64)
-    Q, (N, d) = batch.shape[0], nodes.shape
-    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
-    if Q:
-        lo, hi = batch.amin(0), batch.amax(0)
-        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
-            raise IndexError("triple index out of range")
+    Q, N, d, _ = _req_queries(batch, nodes, rel, sbias, pbias, obias, True)
+    _triples_in_range(batch, N, rel.shape[0], True)
     scores = out if out is not None else torch.empty(Q, N, device=nodes.device, dtype=torch.float32)
     assert scores.shape == (Q, N) and scores.is_contiguous() and scores.dtype == torch.float32
     qsplit = torch.empty(max(int(lib().rgcn_distmult_score_all_bf16_workspace_bytes(Q, d)), 16), device=nodes.device, dtype=torch.uint8)
     qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     with _on(nodes.device), _timed("distmult_score_all_bf16"):
-        _check(lib().rgcn_distmult_score_all_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias),
-                                                  _dp(pbias), _dp(obias), _dp(qsplit), _dp(qb), _dp(scores), N,
-                                                  rel.shape[0], d, _stream(nodes.device)), "distmult_score_all_bf16")
+        _check(lib().rgcn_distmult_score_all_bf16(b, Q, h, nd, rl, sb, pb, ob, _dp(qsplit), _dp(qb), _dp(scores), N, R, d, st),
+               "distmult_score_all_bf16")
     return scores
 
 
@@ -2384,6 +2408,11 @@ def _index_args(filt, head, N, device, filt_q=None):
     keys, ptr, vals = filt.tables[0 if head else 1]
     K = keys.shape[0]
     return (_dp(keys), _dp(ptr), _dp(vals), K) if K else (None, None, None, 0)
+
+
+def _list_args(filt_q, filt_n, F):
+    """the (filt_q, filt_n) arguments of a list entry point: NULLs for no lists or empty ones (F = 0)"""
+    return (_dp(filt_q), _dp(filt_n)) if F else (None, None)
 
 
 def filter_mask_index(batch, head, filt, keep_target=False, c_first=0, c_count=None, out=None):
@@ -2431,59 +2460,33 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     (0 = the library's choice).  A filter entry on a query's own target is ignored.  filt: a functional.FilterIndex in place of the
     lists -- the mask is filled on the device from the index, the same counts (its own profile tags: rank_fused_index[_bf16])."""
     bf16 = nodes.dtype == torch.bfloat16
-    if bf16:
-        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
-    else:
-        _req(nodes, "nodes"); _req(rel, "relations")
-        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-            _req(b, n)
-    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
-    Q, (N, d) = batch.shape[0], nodes.shape
-    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
-    assert rel.shape[1] == d, "relation and node embeddings differ in width"
-    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
-        "filt_q and filt_n: two int32 lists of one length, or neither"
-    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
-    F = 0 if filt_q is None else filt_q.shape[0]
-    if Q:
-        lo, hi = batch.amin(0), batch.amax(0)
-        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
-            if bf16:
-                raise IndexError("triple index out of range")
-            raise AssertionError("triple index out of range")
-    if F:       # an entry out of range would set a bit outside the mask
-        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
-            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n, strips)
+    _triples_in_range(batch, N, rel.shape[0], bf16)
+    _filter_lists_in_range(filt_q, filt_n, Q, N)
     dev = nodes.device
     greater = torch.empty(Q, device=dev, dtype=torch.int64)
     ties = torch.empty(Q, device=dev, dtype=torch.int64)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     if filt is not None:
-        ix = _index_args(filt, head, N, dev, filt_q)
+        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("rank_fused_index_bf16" if bf16 else "rank_fused_index"):
             if bf16:
-                _check(lib().rgcn_distmult_rank_fused_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                                 _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(greater),
-                                                                 _dp(ties), _dp(tscore), N, rel.shape[0], d, _stream(dev)),
-                       "distmult_rank_fused_index_bf16")
+                _check(lib().rgcn_distmult_rank_fused_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
+                                                                 _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_index_bf16")
             else:
-                _check(lib().rgcn_distmult_rank_fused_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                                _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(greater),
-                                                                _dp(ties), _dp(tscore), N, rel.shape[0], d, _stream(dev)),
-                       "distmult_rank_fused_index")
-        return greater, ties, tscore
-    with _on(dev), _timed("rank_fused_bf16" if bf16 else "rank_fused"):
-        if bf16:
-            _check(lib().rgcn_distmult_rank_fused_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                       _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips,
-                                                       _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, rel.shape[0], d,
-                                                       _stream(dev)), "distmult_rank_fused_bf16")
-        else:
-            _check(lib().rgcn_distmult_rank_fused_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                      _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips,
-                                                      _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, rel.shape[0], d,
-                                                      _stream(dev)), "distmult_rank_fused")
+                _check(lib().rgcn_distmult_rank_fused_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
+                                                                _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_index")
+    else:
+        fq, fn = _list_args(filt_q, filt_n, F)
+        with _on(dev), _timed("rank_fused_bf16" if bf16 else "rank_fused"):
+            if bf16:
+                _check(lib().rgcn_distmult_rank_fused_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(greater),
+                                                           _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_bf16")
+            else:
+                _check(lib().rgcn_distmult_rank_fused_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(greater),
+                                                          _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused")
     return greater, ties, tscore
 
 
@@ -2516,55 +2519,33 @@ def distmult_topk_index(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
 def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
     """distmult_topk and distmult_topk_index: the filter as lists, as an index, or none"""
     bf16 = nodes.dtype == torch.bfloat16
-    if bf16:
-        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
-    else:
-        _req(nodes, "nodes"); _req(rel, "relations")
-        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-            _req(b, n)
-    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
-    Q, (N, d) = batch.shape[0], nodes.shape
-    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
-    assert rel.shape[1] == d, "relation and node embeddings differ in width"
-    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
-        "filt_q and filt_n: two int32 lists of one length, or neither"
-    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n, strips)
     assert isinstance(k, int) and k >= 1, "k must be a positive int"
-    F = 0 if filt_q is None else filt_q.shape[0]
-    if Q:
-        lo, hi = batch.amin(0), batch.amax(0)
-        if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < rel.shape[0]):
-            if bf16:
-                raise IndexError("triple index out of range")
-            raise AssertionError("triple index out of range")
-    if F:       # an entry out of range would set a bit outside the mask
-        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
-            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    _triples_in_range(batch, N, rel.shape[0], bf16)
+    _filter_lists_in_range(filt_q, filt_n, Q, N)
     dev = nodes.device
     ids = torch.empty(Q, k, device=dev, dtype=torch.int64)
     scores = torch.empty(Q, k, device=dev, dtype=torch.float32)
     ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     if filt is not None:
-        ix = _index_args(filt, head, N, dev, filt_q)
+        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("topk_fused_index_bf16" if bf16 else "topk_fused_index"):
             if bf16:
-                _check(lib().rgcn_distmult_topk_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                           _dp(obias), ix[0], ix[1], ix[2], ix[3], k, strips, _dp(ws), _dp(ids), _dp(scores),
-                                                           N, rel.shape[0], d, _stream(dev)), "distmult_topk_index_bf16")
+                _check(lib().rgcn_distmult_topk_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
+                                                           _dp(scores), N, R, d, st), "distmult_topk_index_bf16")
             else:
-                _check(lib().rgcn_distmult_topk_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                          _dp(obias), ix[0], ix[1], ix[2], ix[3], k, strips, _dp(ws), _dp(ids), _dp(scores),
-                                                          N, rel.shape[0], d, _stream(dev)), "distmult_topk_index")
-        return ids, scores
-    with _on(dev), _timed("topk_fused_bf16" if bf16 else "topk_fused"):
-        if bf16:
-            _check(lib().rgcn_distmult_topk_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                 _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, k, strips,
-                                                 _dp(ws), _dp(ids), _dp(scores), N, rel.shape[0], d, _stream(dev)), "distmult_topk_bf16")
-        else:
-            _check(lib().rgcn_distmult_topk_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                _dp(obias), _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, k, strips,
-                                                _dp(ws), _dp(ids), _dp(scores), N, rel.shape[0], d, _stream(dev)), "distmult_topk")
+                _check(lib().rgcn_distmult_topk_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
+                                                          _dp(scores), N, R, d, st), "distmult_topk_index")
+    else:
+        fq, fn = _list_args(filt_q, filt_n, F)
+        with _on(dev), _timed("topk_fused_bf16" if bf16 else "topk_fused"):
+            if bf16:
+                _check(lib().rgcn_distmult_topk_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, k, strips, _dp(ws), _dp(ids), _dp(scores),
+                                                     N, R, d, st), "distmult_topk_bf16")
+            else:
+                _check(lib().rgcn_distmult_topk_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, k, strips, _dp(ws), _dp(ids), _dp(scores),
+                                                    N, R, d, st), "distmult_topk")
     return ids, scores
 
 
@@ -2577,12 +2558,9 @@ def checked_queries(batch, N, n_rel, filt_q, filt_n, bf16):
     was validated before.  Filter LISTS are always checked at once: a step filtered by lists is an eager one.  A functional.FilterIndex
     was validated when it was built and needs no check here: its callers pass no lists and take the unfiltered path."""
     Q = batch.shape[0]
-    F = 0 if filt_q is None else filt_q.shape[0]
     if not Q:
         return batch
-    if F:
-        if not (int(filt_q.amin()) >= 0 and int(filt_q.amax()) < Q and int(filt_n.amin()) >= 0 and int(filt_n.amax()) < N):
-            raise IndexError("filter entry out of range (0 <= filt_q < Q, 0 <= filt_n < N)")
+    _filter_lists_in_range(filt_q, filt_n, Q, N)
     if _deferred_mode():
         if torch.cuda.is_current_stream_capturing():
             return batch
@@ -2590,32 +2568,8 @@ def checked_queries(batch, N, n_rel, filt_q, filt_n, bf16):
         bad = (batch.amin() < 0) | (s.amax() >= N) | (o.amax() >= N) | (p.amax() >= n_rel)
         dev_check_err(bad.to(torch.int32).reshape(1), "1-N softmax loss triples (s, o < num_nodes, p < num_relations)", IndexError)
         return torch.stack([s.clamp(0, N - 1), p.clamp(0, n_rel - 1), o.clamp(0, N - 1)], 1)
-    lo, hi = batch.amin(0), batch.amax(0)
-    if not (int(lo.min()) >= 0 and int(hi[0]) < N and int(hi[2]) < N and int(hi[1]) < n_rel):
-        if bf16:
-            raise IndexError("triple index out of range")
-        raise AssertionError("triple index out of range")
+    _triples_in_range(batch, N, n_rel, bf16)
     return batch
-
-
-def _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, strips=0):
-    """the argument requirements of distmult_lse and distmult_softmax_grad (those distmult_rank_fused and distmult_topk state inline) -> (bf16, Q, N, d, F)"""
-    bf16 = nodes.dtype == torch.bfloat16
-    if bf16:
-        _req_distmult_bf16(nodes, rel, sbias, pbias, obias)
-    else:
-        _req(nodes, "nodes"); _req(rel, "relations")
-        for b, n in ((sbias, "sbias"), (pbias, "pbias"), (obias, "obias")):
-            _req(b, n)
-    _req(batch, "batch", torch.int64); _req(filt_q, "filt_q", torch.int32); _req(filt_n, "filt_n", torch.int32)
-    Q, (N, d) = batch.shape[0], nodes.shape
-    assert batch.dim() == 2 and batch.shape[1] == 3, "batch must be [Q, 3]"
-    assert rel.shape[1] == d, "relation and node embeddings differ in width"
-    assert (sbias is None) == (pbias is None) == (obias is None), "biases must be all set or all None"
-    assert (filt_q is None) == (filt_n is None) and (filt_q is None or (filt_q.dim() == 1 and filt_q.shape == filt_n.shape)), \
-        "filt_q and filt_n: two int32 lists of one length, or neither"
-    assert isinstance(strips, int) and strips >= 0, "strips must be a non-negative int"
-    return bf16, Q, N, d, (0 if filt_q is None else filt_q.shape[0])
 
 
 def lse_workspace_bytes(Q, N, d, strips=0, bf16=False):
@@ -2630,35 +2584,42 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     cell, without the [Q, N] score matrix.  The 1-N softmax loss of a query is lse - tscore.  fp32 or bf16 nodes (rel and biases fp32).
     strips: as in distmult_rank_fused.  checked: `batch` went through checked_queries already (a caller that uses it again afterwards).
     filt: a functional.FilterIndex in place of the lists (profile tags lse_fused_index[_bf16])."""
-    bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, strips)
+    bf16 = nodes.dtype == torch.bfloat16
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n, strips)
     if not checked:
-        batch = checked_queries(batch, N, rel.shape[0], filt_q if F else None, filt_n if F else None, bf16)
+        batch = checked_queries(batch, N, rel.shape[0], filt_q, filt_n, bf16)
     dev = nodes.device
     lse = torch.empty(Q, device=dev, dtype=torch.float32)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     if filt is not None:
-        ix = _index_args(filt, head, N, dev, filt_q)
+        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("lse_fused_index_bf16" if bf16 else "lse_fused_index"):
             if bf16:
-                _check(lib().rgcn_distmult_lse_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                          _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(lse), _dp(tscore), N,
-                                                          rel.shape[0], d, _stream(dev)), "distmult_lse_index_bf16")
+                _check(lib().rgcn_distmult_lse_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                          N, R, d, st), "distmult_lse_index_bf16")
             else:
-                _check(lib().rgcn_distmult_lse_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                         _dp(obias), ix[0], ix[1], ix[2], ix[3], strips, _dp(ws), _dp(lse), _dp(tscore), N,
-                                                         rel.shape[0], d, _stream(dev)), "distmult_lse_index")
-        return lse, tscore
-    with _on(dev), _timed("lse_fused_bf16" if bf16 else "lse_fused"):
-        if bf16:
-            _check(lib().rgcn_distmult_lse_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                                _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips, _dp(ws), _dp(lse),
-                                                _dp(tscore), N, rel.shape[0], d, _stream(dev)), "distmult_lse_bf16")
-        else:
-            _check(lib().rgcn_distmult_lse_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                               _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, strips, _dp(ws), _dp(lse),
-                                               _dp(tscore), N, rel.shape[0], d, _stream(dev)), "distmult_lse")
+                _check(lib().rgcn_distmult_lse_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                         N, R, d, st), "distmult_lse_index")
+    else:
+        fq, fn = _list_args(filt_q, filt_n, F)
+        with _on(dev), _timed("lse_fused_bf16" if bf16 else "lse_fused"):
+            if bf16:
+                _check(lib().rgcn_distmult_lse_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                    N, R, d, st), "distmult_lse_bf16")
+            else:
+                _check(lib().rgcn_distmult_lse_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                   N, R, d, st), "distmult_lse")
     return lse, tscore
+
+
+def softmax_grad_workspace_bytes(Q, c_count, d, bf16=False):
+    """bytes of a gradient-cell call's workspace (query vectors, query-side bias terms, the chunk's [Q][ceil(c_count / 32)] filter mask);
+    needs no device; 0 for arguments the call refuses"""
+    if bf16:
+        return int(lib().rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d))
+    return int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d))
 
 
 def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None,
@@ -2669,7 +2630,8 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     The caller has range-checked the triples and the lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to
     write into.  filt: a functional.FilterIndex in place of the lists -- the chunk's mask is filled from it.  Profile tags:
     softmax_grad[_index][_bf16]."""
-    bf16, Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n)
+    bf16 = nodes.dtype == torch.bfloat16
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n)
     _req(lse, "lse"); _req(gscale, "gscale")
     assert lse.shape == (Q,) and gscale.numel() in (1, Q), "lse [Q]; gscale [1] or [Q]"
     assert c_first % 128 == 0 and c_count >= 1 and 0 <= c_first and c_first + c_count <= N, "a chunk starts on a multiple of 128 inside [0, N)"
@@ -2679,33 +2641,27 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     _req(out, "out")
     assert out.numel() >= Q * c_count
     dS = out.view(-1)[:Q * c_count].view(Q, c_count)
-    ws_bytes = lib().rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d) if bf16 else \
-        lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d)
-    ws = torch.empty(max(int(ws_bytes), 16), device=dev, dtype=torch.uint8)
-    per_query = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0
+    ws = torch.empty(max(softmax_grad_workspace_bytes(Q, c_count, d, bf16), 16), device=dev, dtype=torch.uint8)
+    per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     if filt is not None:
-        ix = _index_args(filt, head, N, dev, filt_q)
+        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("softmax_grad_index_bf16" if bf16 else "softmax_grad_index"):
             if bf16:
-                _check(lib().rgcn_distmult_softmax_grad_index_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                                   _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
-                                                                   int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
-                                                                   _stream(dev)), "distmult_softmax_grad_index_bf16")
+                _check(lib().rgcn_distmult_softmax_grad_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale), per_query,
+                                                                   over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
+                       "distmult_softmax_grad_index_bf16")
             else:
-                _check(lib().rgcn_distmult_softmax_grad_index_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias),
-                                                                  _dp(obias), ix[0], ix[1], ix[2], ix[3], _dp(lse), _dp(gscale), per_query,
-                                                                  int(mean_over), c_first, c_count, _dp(ws), _dp(dS), N, rel.shape[0], d,
-                                                                  _stream(dev)), "distmult_softmax_grad_index")
-        return dS
-    with _on(dev), _timed("softmax_grad_bf16" if bf16 else "softmax_grad"):
-        if bf16:
-            _check(lib().rgcn_distmult_softmax_grad_bf16(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                                         _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
-                                                         per_query, int(mean_over), c_first, c_count,
-                                                         _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad_bf16")
-        else:
-            _check(lib().rgcn_distmult_softmax_grad_f32(_dp(batch), Q, 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                                        _dp(filt_q) if F else None, _dp(filt_n) if F else None, F, _dp(lse), _dp(gscale),
-                                                        per_query, int(mean_over), c_first, c_count,
-                                                        _dp(ws), _dp(dS), N, rel.shape[0], d, _stream(dev)), "distmult_softmax_grad")
+                _check(lib().rgcn_distmult_softmax_grad_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale), per_query,
+                                                                  over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
+                       "distmult_softmax_grad_index")
+    else:
+        fq, fn = _list_args(filt_q, filt_n, F)
+        with _on(dev), _timed("softmax_grad_bf16" if bf16 else "softmax_grad"):
+            if bf16:
+                _check(lib().rgcn_distmult_softmax_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,
+                                                             c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_softmax_grad_bf16")
+            else:
+                _check(lib().rgcn_distmult_softmax_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,
+                                                            c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_softmax_grad")
     return dS

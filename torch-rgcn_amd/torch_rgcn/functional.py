@@ -1224,29 +1224,30 @@ class _DistMultScoreBF16(torch.autograd.Function):
         return None, dn, dr, dsb, dpb, dob
 
 
+def _widen_query_params(nodes, relations, sbias, pbias, obias):
+    """-> (relations, sbias, pbias, obias) as the native DistMult calls take them.  fp32 nodes: as they are.  bf16 nodes:
+    each fp32 or bf16, else TypeError; bf16 ones widened to fp32, once per call (.float() is a no-op on fp32; they are small)"""
+    if nodes.dtype != torch.bfloat16:
+        return relations, sbias, pbias, obias
+    for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
+        if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
+    return tuple(None if t is None else t.float() for t in (relations, sbias, pbias, obias))
+
+
 def distmult_score(triples, nodes, relations, sbias=None, pbias=None, obias=None):
     """DistMult scores of `triples` [..., 3].  fp32 nodes: everything fp32.  bf16 nodes: relations and biases fp32 or bf16
     -- bf16 parameters are widened here, once per call, and autograd carries the cast back --, scores fp32, dnodes bf16."""
-    if nodes.dtype == torch.bfloat16:
-        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
-            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
-        widen = lambda t: None if t is None else t.float()     # noqa: E731  (a no-op on fp32)
-        return _DistMultScoreBF16.apply(triples, nodes, widen(relations), widen(sbias), widen(pbias), widen(obias))
-    return _DistMultScore.apply(triples, nodes, relations, sbias, pbias, obias)
+    score = _DistMultScoreBF16 if nodes.dtype == torch.bfloat16 else _DistMultScore
+    return score.apply(triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
 
 
 def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, out=None):
     """fp32 scores [Q, N] of every entity as the head (head=True) or the tail of each triple of `batch` (int64 [Q, 3] on the device), no
     autograd: the ranking evaluator's product (utils/misc.py:71-88).  fp32 nodes run the fp32 matrix instructions; bf16 nodes (DESIGN.md
     4.6) the bf16 ones on the bf16 table, with relations and biases fp32 or bf16 (widened here) -- same sums, another order."""
-    if nodes.dtype == torch.bfloat16:
-        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
-            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
-        widen = lambda t: None if t is None else t.float()     # noqa: E731
-        return _native.distmult_score_all_bf16(batch, head, nodes, widen(relations), widen(sbias), widen(pbias), widen(obias), out=out)
-    return _native.distmult_score_all(batch, head, nodes, relations, sbias, pbias, obias, out=out)
+    score_all = _native.distmult_score_all_bf16 if nodes.dtype == torch.bfloat16 else _native.distmult_score_all
+    return score_all(batch, head, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias), out=out)
 
 
 class FilterIndex:
@@ -1317,12 +1318,7 @@ def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obi
     (utils/misc.py:40-58, 71-99).  No autograd.  fp32 or bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16
     (widened here), as in distmult_score_all.  filt: a FilterIndex in place of the lists (not both: ValueError) -- the same counts."""
     _filter_args(filt, filt_q, filt_n, nodes)
-    if nodes.dtype == torch.bfloat16:
-        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
-            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
-        widen = lambda t: None if t is None else t.float()     # noqa: E731
-        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+    relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
     return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, filt=filt)
 
 
@@ -1347,12 +1343,7 @@ def distmult_topk_all_index(batch, head, nodes, relations, sbias=None, pbias=Non
 
 
 def _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
-    if nodes.dtype == torch.bfloat16:
-        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
-            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
-        widen = lambda t: None if t is None else t.float()     # noqa: E731
-        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
+    relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
     if filt is not None:
         return _native.distmult_topk_index(batch, head, nodes, relations, sbias, pbias, obias, k, filt, strips)
     return _native.distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips)
@@ -1511,14 +1502,10 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
     _filter_args(filt, filt_q, filt_n, nodes)
     params = (nodes, relations, sbias, pbias, obias)
-    if nodes.dtype == torch.bfloat16:
-        for name, t in (("relations", relations), ("sbias", sbias), ("pbias", pbias), ("obias", obias)):
-            if t is not None and t.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"{name} must be torch.float32 or torch.bfloat16, got {t.dtype}")
-        widen = lambda t: None if t is None else t.float()     # noqa: E731  (a no-op on fp32)
-        relations, sbias, pbias, obias = widen(relations), widen(sbias), widen(pbias), widen(obias)
-        if bf16_backward == "upcast" and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
-            nodes = nodes.float()
+    relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
+    if nodes.dtype == torch.bfloat16 and bf16_backward == "upcast" and torch.is_grad_enabled() and \
+            any(t is not None and t.requires_grad for t in params):
+        nodes = nodes.float()
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
                                       chunk_bytes, filt)
 

@@ -105,11 +105,9 @@ class DistMult(Module):
         on fp32 embeddings)."""
         _require_gpu(nodes, "DistMult node embeddings")
         triples = triples.to(nodes.device)
-        if self.b_init:
-            return F_.distmult_softmax_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias,
-                                            filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward)
-        return F_.distmult_softmax_loss(triples, head, nodes, self.relations, filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt,
-                                        bf16_backward=bf16_backward)
+        # (without b_init the three biases are registered as None: one call serves both)
+        return F_.distmult_softmax_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias,
+                                        filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward)
 
 
 class _RGCBase(Module):
