@@ -975,6 +975,71 @@ RGCN_API int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t
                                                    const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
                                                    int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
                                                    float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* 1-N softmax loss with label smoothing (an extension with no reference counterpart, as the 1-N entries above), forward.  With A_q the
+ * allowed set of query q as in rgcn_distmult_lse_* (every n < n_nodes whose mask bit is clear; an entry on the query's own target is
+ * ignored, so the target is in A_q and |A_q| >= 1), the four rgcn_distmult_lse_* forms again with two more outputs behind tscore:
+ *   ssum[q] = sum_{n in A_q} s[q, n]   (float [Q])        and        cnt[q] = |A_q|   (int32 [Q]),
+ * from which the caller composes, for a smoothing eps in [0, 1),
+ *   loss[q] = lse[q] - (1 - eps) tscore[q] - (eps / cnt[q]) ssum[q]
+ * -- the cross-entropy against (1 - eps) on the target plus eps spread evenly over the ALLOWED candidates.  lse and tscore are bit for
+ * bit those of the unsmoothed form with the same arguments and the same `strips`: the strip pass updates (m, l) by the same statements
+ * and keeps, beside them, the row's running sum of the allowed scores (a masked cell or a column >= n_nodes adds 0; reduced over the
+ * row's 16 lanes once per tile) and its count of allowed cells (the clear bits of the mask words the epilogue holds already).  One
+ * (m, l, sum, count) per strip half and query, (-inf, 0, 0, 0) for a strip without a tile; the merge pass folds them in index order,
+ * so one `strips` gives one answer, run after run.  Passes, stream discipline (no host synchronisation, no memset) and errors are the
+ * unsmoothed forms'; NULL ssum or cnt is RGCN_EINVAL, n_nodes > INT32_MAX RGCN_EUNSUPPORTED (cnt is 32-bit).
+ * workspace: rgcn_distmult_lse_smooth_workspace_bytes(Q, n_nodes, d, strips, bf16) bytes, 16-byte aligned -- the layout of
+ * rgcn_distmult_lse_workspace_bytes with four floats per cell of the partials where that has two; no device is asked, 0 for arguments
+ * the call refuses. */
+RGCN_API int64_t rgcn_distmult_lse_smooth_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
+RGCN_API int rgcn_distmult_lse_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                          const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                          float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                           const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                           float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
+                                                int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                 const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                 const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                 float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
+                                                 int32_t d, void *stream);
+/* 1-N softmax loss with label smoothing, gradient cells (an extension with no reference counterpart): the four
+ * rgcn_distmult_softmax_grad_* forms again with two more inputs behind gscale,
+ *   dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - keep[0] [c == target_q] - uni[q]),   a filtered cell 0,
+ * keep a DEVICE float [1] holding 1 - eps and uni a DEVICE float [Q] holding eps / cnt[q] (the ABI passes no float by value; neither is
+ * read back).  The sum of a row of dS is still 0.  lse: what the smoothed or the unsmoothed forward returned for the same arguments (the
+ * same bits).  Chunk contract, scale_q, workspace (rgcn_distmult_softmax_grad[_bf16]_workspace_bytes), passes and errors are those of
+ * the unsmoothed forms; NULL keep or uni is RGCN_EINVAL.  A row whose only allowed cell is its target gets exp(0) - keep - uni, which is
+ * 0 exactly when keep + uni is 1 exactly (eps = 0.25: 0.75 and 0.25). */
+RGCN_API int rgcn_distmult_softmax_grad_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                   const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                                   const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
+                                                   const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
+                                                   void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_softmax_grad_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                    const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                                    const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
+                                                    const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
+                                                    void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_softmax_grad_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                         const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                         const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
+                                                         const float *gscale, const float *keep, const float *uni, int32_t per_query,
+                                                         int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                                         int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                          const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
+                                                          const float *gscale, const float *keep, const float *uni, int32_t per_query,
+                                                          int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

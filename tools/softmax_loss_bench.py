@@ -13,7 +13,13 @@ of --steps after --warmup.  Peak memory: the rise of torch.cuda.max_memory_alloc
 cache.  No figure is a threshold: the fused forward recomputes nothing but writes nothing either, the fused backward computes the
 product a second time -- what is bought is memory.
 
+  --smooth EPS  the label-smoothing leg INSTEAD of the above: at both sizes, fp32 and bf16 (native route), the forward and forward +
+           backward with label_smoothing=EPS against the same call without it, the two alternating launch by launch; the measurement is
+           repeated five times and the median of the five medians is reported with their spread (min .. max), plus the per-kernel times
+           of one launch of each (lse_fused against lse_smooth, softmax_grad against softmax_grad_smooth).
+
     python tools/softmax_loss_bench.py [--steps 10 --warmup 3 --out DIR]   -> DIR/softmax_loss_bench_<csrc_sha>.json (DIR: profiles/)
+    python tools/softmax_loss_bench.py --smooth 0.1 [...]                  -> DIR/softmax_loss_smooth_bench_<csrc_sha>.json
 """
 import argparse
 import json
@@ -137,6 +143,44 @@ def bf16_leg(nodes, rel, batch, steps, warmup):
     return res
 
 
+def smooth_leg(N, eps, steps, warmup, repeats=5):
+    """smoothed against unsmoothed at one size: {storage: {forward | forward_backward: {plain | smoothed: medians of `repeats`
+    alternating measurements, their median and spread, kernels_ms}, smoothed_over_plain}}"""
+    from torch_rgcn import functional
+    nodes, rel, batch = case(N)
+    res = {"shape": {"N": N, "d": nodes.shape[1], "Q": batch.shape[0]}, "label_smoothing": eps, "repeats": repeats}
+    for storage in ("fp32", "bf16"):
+        nt = nodes if storage == "fp32" else nodes.detach().to(torch.bfloat16).requires_grad_(True)
+        nd, rd = nt.detach(), rel.detach()
+        kw = {} if storage == "fp32" else {"bf16_backward": "native"}
+
+        def fwd_of(e):
+            return lambda: functional.distmult_softmax_loss(batch, False, nd, rd, reduction="none", label_smoothing=e)
+
+        def step_of(e):
+            def run():
+                nt.grad = rel.grad = None
+                loss = functional.distmult_softmax_loss(batch, False, nt, rel, label_smoothing=e, **kw)
+                loss.backward(gradient=functional.unit_gradient(loss.device))
+                return loss
+            return run
+        res[storage] = {}
+        for what, make in (("forward", fwd_of), ("forward_backward", step_of)):
+            variants = {"plain": make(0.0), "smoothed": make(eps)}
+            medians = {k: [] for k in variants}
+            for r in range(repeats):
+                one = alternate(variants, steps, warmup if r == 0 else 1)
+                for k in variants:
+                    medians[k].append(one[k]["ms_median"])
+            leg = {k: {"ms_medians": m, "ms_median": round(statistics.median(m), 4), "ms_spread": [min(m), max(m)],
+                       "kernels_ms": kernels_of(variants[k])} for k, m in medians.items()}
+            leg["smoothed_over_plain"] = round(leg["smoothed"]["ms_median"] / leg["plain"]["ms_median"], 4)
+            res[storage][what] = leg
+        res[storage]["loss"] = {"plain": float(step_of(0.0)().detach()), "smoothed": float(step_of(eps)().detach())}
+        nt.grad = rel.grad = None
+    return res
+
+
 def aten_step(nodes, rel, batch):
     def run():
         nodes.grad = rel.grad = None
@@ -200,6 +244,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--skip-million", action="store_true")
+    ap.add_argument("--smooth", type=float, default=None, metavar="EPS", help="run the label-smoothing leg (smoothed against unsmoothed) instead")
     ap.add_argument("--wn18-n", type=int, default=40_943, help="entities of the WN18-sized case (a multiple of 4 gives the products 16-byte loads of dS)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -207,6 +252,20 @@ def main():
     from torch_rgcn import _native
     out = {"tool": "tools/softmax_loss_bench.py", "csrc_sha": _native.csrc_sha(), "steps": args.steps, "warmup": args.warmup,
            "device": torch.cuda.get_device_name(0)}
+    if args.smooth is not None:
+        out["wn18"] = smooth_leg(args.wn18_n, args.smooth, args.steps, args.warmup)
+        print(json.dumps({"wn18": out["wn18"]}), flush=True)
+        if not args.skip_million:
+            steps = max(3, args.steps // 2)
+            out["million"] = dict(smooth_leg(1_000_000, args.smooth, steps, max(1, args.warmup // 2)), steps=steps)
+            print(json.dumps({"million": out["million"]}), flush=True)
+        os.makedirs(args.out, exist_ok=True)
+        path = os.path.join(args.out, f"softmax_loss_smooth_bench_{_native.csrc_sha()}.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print("wrote", path)
+        return
     out["wn18"] = wn18(args.steps, args.warmup, args.wn18_n)
     print(json.dumps({"wn18": out["wn18"]}), flush=True)
     if not args.skip_million:

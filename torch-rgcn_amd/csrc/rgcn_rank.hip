@@ -13,10 +13,11 @@
 // Second route (rgcn_distmult_rank_fused_*, utils/misc.py:40-58, 71-99): the same tile product with an epilogue that compares every score
 // with the target's instead of storing it -- greater / ties per query without a [Q, N] buffer.  Third (rgcn_distmult_topk_*):
 // an epilogue that selects the k best.  Fourth (rgcn_distmult_lse_*, rgcn_distmult_softmax_grad_*; an extension, the reference trains on
-// sampled negatives only): an epilogue that adds exp(score) for the 1-N softmax loss, and the gradient cells of that loss in column chunks.
+// sampled negatives only): an epilogue that adds exp(score) for the 1-N softmax loss, and the gradient cells of that loss in column chunks;
+// with label smoothing (rgcn_distmult_lse_smooth_*, rgcn_distmult_softmax_grad_smooth_*) the epilogue also sums and counts the allowed scores.
 // Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select, add) first; then a tile-precision trait
 // (TileF32 / TileBf16) and the kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel,
-// strip_lse_kernel, softmax_grad_kernel -- each written once over <Tile, VEC>; then the entry points.
+// strip_lse_kernel, strip_lse_smooth_kernel, softmax_grad_kernel -- each written once over <Tile, VEC>; then the entry points.
 #include <cmath>
 #include <cstdlib>
 
@@ -514,14 +515,25 @@ __device__ __forceinline__ void lse_merge(float &m, float &l, float m2, float l2
 // lanes of a row stay together; a column past N is clamped for its bias and counts as filtered), the mask words read as tile_count reads
 // them.  A row's four cells per lane wait in p[]; at the fourth the row's maximum and then its sum go over the 16 lanes, and lane
 // i = row keeps the tile's pair of that row -- merged into the wave's running (m, l) once per tile: two registers across the product.
+// SMOOTH (label smoothing): beside the pair, the row's sum of the allowed scores -- the same cells as they go into p[], a masked cell
+// or a column >= N adding 0 -- and the row's count of allowed cells: the clear bits of the row's two mask words among the columns of
+// this half that exist, which every lane of the row holds already (no exchange).  Lane i = row keeps both over the tile's epilogue and
+// then adds them, once per tile, into ITS OWN slot of the workgroup's LDS (t: the sums, c: the counts): no lane reads another's slot, so
+// nothing synchronises, and no register more than the pair lives across the product.  m and l are formed by the same statements either
+// way.
 struct LseRow { unsigned w[2]; };
 
+template <bool SMOOTH>
 __device__ __forceinline__ void tile_lse(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long N, const float *__restrict__ qb,
                                          const float *__restrict__ cbias, int head, const unsigned *__restrict__ mask, long long mask_w,
-                                         float &m, float &l) {
+                                         float &m, float &l, float *__restrict__ t, int *__restrict__ c) {
   const int i = threadIdx.x & 15;
   float p[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  float tm = -INFINITY, tl = 0.f;
+  float tm = -INFINITY, tl = 0.f, ts = 0.f, rs = 0.f;
+  int tc = 0;
+  const long long left = N - c0;                              // the columns of this half below N: bits [0, left) of the row's two words
+  const unsigned long long valid = left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1;
+  const unsigned valid0 = (unsigned)valid, valid1 = (unsigned)(valid >> 32);
   tile_epilogue(acc, q0, c0, Q, c0 + 64, qb, head,
                 [&](int, int qrow) {
                   LseRow st{{0u, 0u}};
@@ -537,15 +549,22 @@ __device__ __forceinline__ void tile_lse(const f32x4 (&acc)[4][4], int q0, long 
                 [&](const LseRow &st, int row, int b, long long col, float sc_) {
                   const bool out = col >= N || ((st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u);
                   p[b] = out ? -INFINITY : sc_;
+                  if constexpr (SMOOTH) rs = (b == 0 ? 0.f : rs) + (out ? 0.f : sc_);     // the decision p[] takes, 0 where p[] takes -inf
                   if (b == 3) {
                     const float rm = row16_max_f(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])));
                     const float ref = rm == -INFINITY ? 0.f : rm;
                     const float rl = row16_sum_f((__expf(p[0] - ref) + __expf(p[1] - ref)) + (__expf(p[2] - ref) + __expf(p[3] - ref)));
                     tm = i == row ? rm : tm;
                     tl = i == row ? rl : tl;
+                    if constexpr (SMOOTH) {
+                      const float sum = row16_sum_f(rs);
+                      ts = i == row ? sum : ts;
+                      tc = i == row ? __popc(valid0 & ~st.w[0]) + __popc(valid1 & ~st.w[1]) : tc;
+                    }
                   }
                 });
   lse_merge(m, l, tm, tl);
+  if constexpr (SMOOTH) { *t += ts; *c += tc; }               // (a row past Q: 0 + 0)
 }
 
 // a wave's pairs -> partial[2 strip + candidate half of the wave][q] = (m, l); the rows as strip_store maps them
@@ -553,6 +572,12 @@ __device__ __forceinline__ void lse_store(float m, float l, int q0, int Q, float
   const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
   const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
   if (qrow < Q) part[qrow] = float2{m, l};
+}
+// the smoothed role's four: (m, l, t, the bits of the count c) -- one 16-byte store
+__device__ __forceinline__ void lse_smooth_store(float m, float l, float t, int c, int q0, int Q, float4 *__restrict__ part) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
+  const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
+  if (qrow < Q) part[qrow] = float4{m, l, t, __int_as_float(c)};
 }
 
 // ------------------------------------------------------------------ the tile precision and the kernel roles
@@ -571,6 +596,7 @@ struct TileDims {
 struct TileF32 {
   using elem = float;         // queries: fp32 [Q][d]
   struct Slabs { float a[2][128 * LDS_LD], b[2][128 * LDS_LD]; };             // 40,960 bytes
+  static constexpr int strip_waves = 3;                                       // workgroups per CU = waves per SIMD that the slabs allow
   static __device__ __forceinline__ int q_stride(const TileDims &dm) { return dm.d; }
   template <bool VEC>
   static __device__ __forceinline__ void product(const float *const (&ga)[2], const float *const (&gb)[2], const TileDims &dm, Slabs &s,
@@ -582,6 +608,7 @@ struct TileF32 {
 struct TileBf16 {
   using elem = uint16_t;      // queries: the hi term of bf16 [3][Q][dpad]
   struct Slabs { uint16_t a[2][3][SLAB], b[2][SLAB]; };                       // 65,536 bytes
+  static constexpr int strip_waves = 2;
   static __device__ __forceinline__ int q_stride(const TileDims &dm) { return dm.dpad; }
   template <bool VEC>
   static __device__ __forceinline__ void product(const uint16_t *const (&ga)[2], const uint16_t *const (&gb)[2], const TileDims &dm, Slabs &s,
@@ -712,9 +739,30 @@ __global__ __launch_bounds__(WG) void strip_lse_kernel(
   __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
   float m = -INFINITY, l = 0.f;
   const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
-    tile_lse(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, m, l);
+    tile_lse<false>(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, m, l, nullptr, nullptr);
   });
   lse_store(m, l, w.q0, Q, partial + (size_t)w.part * Q);
+}
+
+// The smoothed role of the strip pass (label smoothing): beside (m, l) the wave keeps t = the sum of the allowed scores and c = their
+// count per query row -- in LDS, one slot per lane (2 KB beside the slabs: the workgroups per CU stay what the slabs allow), because
+// two more registers across the product cost the fp32 element-load instantiation a workgroup per CU or a spill; the launch bound states
+// the occupancy of strip_lse_kernel of the same <Tile, VEC>.  A strip without a tile writes (-inf, 0, 0, 0).
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG, Tile::strip_waves) void strip_lse_smooth_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const unsigned *__restrict__ mask, long long mask_w, float4 *__restrict__ partial, int Q, long long N,
+    int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  __shared__ float t[WG];
+  __shared__ int c[WG];
+  t[threadIdx.x] = 0.f;
+  c[threadIdx.x] = 0;
+  float m = -INFINITY, l = 0.f;
+  const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
+    tile_lse<true>(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, m, l, t + threadIdx.x, c + threadIdx.x);
+  });
+  lse_smooth_store(m, l, t[threadIdx.x], c[threadIdx.x], w.q0, Q, partial + (size_t)w.part * Q);
 }
 
 // the strips' pairs [n_part][Q] merged in index order (one answer for one `strips`); accurate expf / logf: Q values
@@ -732,20 +780,43 @@ __global__ __launch_bounds__(WG) void lse_merge_kernel(const float2 *__restrict_
   lse[q] = m == -INFINITY ? -INFINITY : m + logf(l);
 }
 
+// the smoothed role's merge: (m, l) folded by the statements above -- the same lse bits --, t and c added in the same index order
+__global__ __launch_bounds__(WG) void lse_smooth_merge_kernel(const float4 *__restrict__ partial, int n_part, int Q, float *__restrict__ lse,
+                                                              float *__restrict__ ssum, int *__restrict__ cnt) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= Q) return;
+  float m = -INFINITY, l = 0.f, t = 0.f;
+  int c = 0;
+  for (int p = 0; p < n_part; ++p) {
+    const float4 v = partial[(size_t)p * Q + q];
+    t += v.z;
+    c += __float_as_int(v.w);
+    const float mn = fmaxf(m, v.x);
+    if (mn == -INFINITY) continue;                           // both empty: -inf - -inf would be NaN
+    l = l * expf(m - mn) + v.y * expf(v.x - mn);
+    m = mn;
+  }
+  lse[q] = m == -INFINITY ? -INFINITY : m + logf(l);
+  ssum[q] = t;
+  cnt[q] = c;
+}
+
 // Gradient cells of the 1-N softmax loss, on the score-all grid cut to the candidate columns [c_first, c_first + c_count) (c_first a
 // multiple of 128: tiles and mask words align as in tile_count): dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),
 // a filtered cell 0; scale_q = gscale[per_query ? q : 0] * inv_q -- the upstream gradient is read on the device.  mask: the filter
 // bits of THIS chunk, [Q][mask_w] with bit 0 of word 0 = column c_first.  The product is recomputed by the product loop of the
 // storage: s is bit for bit the cell the strip kernel of the same <Tile, VEC> added, so a row whose only cell is its target gets
 // exp(0) - 1 = 0.  dS is fp32 for both storages.
-struct GradRow { float lse, scale; long long tgt; unsigned w[2]; float *out; };
+// SMOOTH (label smoothing): dS = scale_q (exp(s - lse) - keep [c == target_q] - uni[q]) on an allowed cell, keep = keep[0] = 1 - eps and
+// uni[q] = eps / (the allowed count of q) read on the device; without it keep is the constant 1 and nothing else is subtracted.
+struct GradRow { float lse, scale, keep, uni; long long tgt; unsigned w[2]; float *out; };
 
-template <class Tile, bool VEC>
+template <class Tile, bool VEC, bool SMOOTH>
 __global__ __launch_bounds__(WG) void softmax_grad_kernel(
     const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
     const float *__restrict__ cbias, const long long *__restrict__ batch, const float *__restrict__ lse, const float *__restrict__ gscale,
-    int per_query, float inv_q, const unsigned *__restrict__ mask, long long mask_w, float *__restrict__ dS, int Q, long long N,
-    long long c_first, long long c_count, int head, int q_blocks) {
+    int per_query, float inv_q, const float *__restrict__ keep, const float *__restrict__ uni, const unsigned *__restrict__ mask,
+    long long mask_w, float *__restrict__ dS, int Q, long long N, long long c_first, long long c_count, int head, int q_blocks) {
   __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
   const int wave = threadIdx.x >> 6, i = threadIdx.x & 15;
   const int qt = (blockIdx.x % q_blocks) * 128;
@@ -758,8 +829,8 @@ __global__ __launch_bounds__(WG) void softmax_grad_kernel(
   const long long c0 = ct + (wave & 1) * 64;
   tile_epilogue(acc, qt + (wave >> 1) * 64, c0, Q, c_first + c_count, qb, head,
                 [&](int, int qrow) {
-                  GradRow st{lse[qrow], gscale[per_query ? qrow : 0] * inv_q, rank_target(batch, qrow, head), {0u, 0u},
-                             dS + (size_t)qrow * c_count - c_first};
+                  GradRow st{lse[qrow], gscale[per_query ? qrow : 0] * inv_q, SMOOTH ? keep[0] : 1.f, SMOOTH ? uni[qrow] : 0.f,
+                             rank_target(batch, qrow, head), {0u, 0u}, dS + (size_t)qrow * c_count - c_first};
                   if (mask) {
                     const long long w0 = (c0 - c_first) >> 5;
                     const unsigned *mrow = mask + (size_t)qrow * mask_w;
@@ -771,7 +842,8 @@ __global__ __launch_bounds__(WG) void softmax_grad_kernel(
                 [&](long long col) { return cbias[col]; },
                 [&](const GradRow &st, int, int b, long long col, float sc_) {
                   const bool out = (st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u;
-                  const float p = __expf(sc_ - st.lse) - (col == st.tgt ? 1.f : 0.f);
+                  float p = __expf(sc_ - st.lse) - (col == st.tgt ? st.keep : 0.f);
+                  if constexpr (SMOOTH) p -= st.uni;
                   st.out[col] = out ? 0.f : st.scale * p;
                 });
 }
@@ -1352,15 +1424,32 @@ extern "C" int rgcn_distmult_topk_index_bf16(const int64_t *batch, int64_t Q, in
 // ------------------------------------------------------------------ 1-N softmax loss: entry points
 namespace {
 
+// smooth: the smoothed role -- ssum [Q] and cnt [Q] beside lse and tscore, four floats per cell of the partials
 template <class Tile>
-int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore) {
-  if (int rc = strip_check(a, a.Q && (!lse || !tscore), "")) return rc;
+int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore, bool smooth = false, float *ssum = nullptr,
+              int32_t *cnt = nullptr) {
+  if (int rc = strip_check(a, a.Q && (!lse || !tscore || (smooth && (!ssum || !cnt))), "")) return rc;
   if (a.Q == 0) return RGCN_OK;
   StripCall<Tile> c;
-  auto too_many = [](int64_t) { return false; };            // the pairs are floats: no counter to overflow
-  if (int rc = strip_begin<Tile>(a, sizeof(float2), 0, too_many, "strips", c)) return rc;
-  float2 *part = static_cast<float2 *>(c.part);
+  // the pairs are floats: no counter to overflow; the smoothed role counts a query's allowed entities in 32 bits
+  auto too_many = [&](int64_t) { return smooth && a.n_nodes > INT32_MAX; };
+  if (int rc = strip_begin<Tile>(a, smooth ? sizeof(float4) : sizeof(float2), 0, too_many, smooth ? "entities" : "strips", c)) return rc;
   const int Q = (int)a.Q;
+  if (smooth) {
+    float4 *part = static_cast<float4 *>(c.part);
+    with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+      constexpr bool V = decltype(vec)::value;
+      hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
+                         a.head);
+      hipLaunchKernelGGL((strip_lse_smooth_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb,
+                         c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+    });
+    hipLaunchKernelGGL(lse_smooth_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float4 *)part,
+                       (int)(2 * c.n_strips), Q, lse, ssum, (int *)cnt);
+    HIP_TRY(hipGetLastError());
+    return RGCN_OK;
+  }
+  float2 *part = static_cast<float2 *>(c.part);
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     constexpr bool V = decltype(vec)::value;
     hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
@@ -1420,6 +1509,49 @@ extern "C" int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int
                               n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
 }
 
+// label smoothing: the four forms again with ssum and cnt behind tscore, four floats per cell of the partials
+extern "C" int64_t rgcn_distmult_lse_smooth_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, sizeof(float4)).total;
+}
+
+extern "C" int rgcn_distmult_lse_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                            float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileF32>({"distmult_lse_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes,
+                             d, stream}, lse, tscore, true, ssum, cnt);
+}
+
+extern "C" int rgcn_distmult_lse_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                             const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                             float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileBf16>({"distmult_lse_smooth_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                              n_nodes, d, stream}, lse, tscore, true, ssum, cnt);
+}
+
+extern "C" int rgcn_distmult_lse_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                  float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
+                                                  int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileF32>({"distmult_lse_smooth_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
+                             n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore, true, ssum, cnt);
+}
+
+extern "C" int rgcn_distmult_lse_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
+                                                   float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
+                                                   int32_t d, void *stream) {
+  (void)n_rel;
+  return lse_fused<TileBf16>({"distmult_lse_smooth_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
+                              workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore, true, ssum, cnt);
+}
+
 extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
   return softmax_grad_workspace_bytes(Q, c_count, d, false);
 }
@@ -1433,19 +1565,23 @@ namespace {
 // what the list form and the index form of the gradient-cell entry share: a.F fills the chunk's mask from the lists, a.ix.K from the index
 template <class Tile>
 int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
-                 int64_t c_count, float *dS) {
+                 int64_t c_count, float *dS, bool smooth = false, const float *keep = nullptr, const float *uni = nullptr) {
   const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > a.n_nodes - c_count || mean_over < 1;
   const float inv_q = 1.0f / (float)mean_over;
+  if (smooth && (!keep || !uni)) { rgcn_set_error("%s: keep [1] and uni [Q] must be device pointers, not NULL", a.name); return RGCN_EINVAL; }
   if (int rc = strip_check(a, bad_chunk || (a.Q && (!lse || !gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
   if (a.Q == 0) return RGCN_OK;
   const int64_t nwg = ((c_count + 127) / 128) * ((a.Q + 127) / 128);
   if (nwg > INT32_MAX) { rgcn_set_error("%s: too many cells in one call; take a smaller chunk", a.name); return RGCN_EUNSUPPORTED; }
   StripCall<Tile> c;
   if (int rc = query_begin<Tile>(a, 0, 0, true, c_first, c_count, c)) return rc;       // no partials, keep_target = 0, the chunk's own mask
+  auto launch = [&](auto vec, auto sm) {
+    hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value, decltype(sm)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes,
+                       c.dm, c.qb, c.cbias, c.b, lse, gscale, (int)per_query, inv_q, keep, uni, c.mask, (long long)c.mask_w, dS, (int)a.Q,
+                       (long long)a.n_nodes, (long long)c_first, (long long)c_count, a.head, (int)c.qbl);
+  };
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
-    hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b,
-                       lse, gscale, (int)per_query, inv_q, c.mask, (long long)c.mask_w, dS, (int)a.Q, (long long)a.n_nodes, (long long)c_first,
-                       (long long)c_count, a.head, (int)c.qbl);
+    if (smooth) launch(vec, std::true_type{}); else launch(vec, std::false_type{});
   });
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -1492,6 +1628,51 @@ extern "C" int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64
   return softmax_grad<TileBf16>({"distmult_softmax_grad_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
                                  workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
                                  c_first, c_count, dS);
+}
+
+// label smoothing: the four forms again with keep [1] and uni [Q] behind gscale, the smoothed instantiation of the cell kernel
+extern "C" int rgcn_distmult_softmax_grad_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                     const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                                     const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
+                                                     const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
+                                                     void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileF32>({"distmult_softmax_grad_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace,
+                                n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS, true, keep, uni);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                                      const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
+                                                      const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
+                                                      void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileBf16>({"distmult_softmax_grad_smooth_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0,
+                                 workspace, n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS, true, keep, uni);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                           const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
+                                                           const float *gscale, const float *keep, const float *uni, int32_t per_query,
+                                                           int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                                           int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileF32>({"distmult_softmax_grad_smooth_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
+                                workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first,
+                               c_count, dS, true, keep, uni);
+}
+
+extern "C" int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
+                                                            const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
+                                                            const float *gscale, const float *keep, const float *uni, int32_t per_query,
+                                                            int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                                            int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return softmax_grad<TileBf16>({"distmult_softmax_grad_smooth_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
+                                 workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
+                                 c_first, c_count, dS, true, keep, uni);
 }
 
 // ------------------------------------------------------------------ device-resident filter index: the mask and the materialised route

@@ -11,6 +11,8 @@ training.filtered (1-n only, default false; configs/rgcn/lp-WN18-1n-filtered.yam
 TRAINING triples only -- are left out of its softmax, looked up in a device-resident FilterIndex, so the step is captured all the same
 training.bf16 (1-n only, default false; configs/rgcn/lp-WN18-1n-bf16.yaml): the model is put into bf16 (model.bfloat16()) before the
 optimiser is built and both softmax terms run the native bf16 backward -- no fp32 image of the entity table exists during training
+training.label_smoothing (1-n only, default 0; configs/rgcn/lp-WN18-1n-smoothed.yaml): epsilon in [0, 1) of both softmax terms, spread
+evenly over the candidates that are not filtered; combines with training.filtered and training.bf16, and the step is captured all the same
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""
@@ -54,6 +56,9 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     train_bf16 = bool(training.get("bf16", False))
     if train_bf16 and not one_to_n:
         raise ValueError("training.bf16 needs training.objective: 1-n (the native bf16 backward is the 1-N softmax loss's)")
+    label_smoothing = training.get("label_smoothing", 0)
+    if label_smoothing and not one_to_n:
+        raise ValueError("training.label_smoothing needs training.objective: 1-n (the sampled-negative objective has no smoothing)")
     max_epochs = epochs or training.get("epochs", 5000)
     graph_batch_size = training.get("graph_batch_size")
     sampling_function = select_sampling(training.get("sampling_method", "uniform"))
@@ -103,6 +108,8 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     if train_bf16:
         model = model.bfloat16()
     loss_kw = {"bf16_backward": "native"} if train_bf16 else {}
+    if label_smoothing:
+        loss_kw["label_smoothing"] = label_smoothing
     opt_cfg = training.get("optimiser", {"algorithm": "adam", "learn_rate": 0.01, "weight_decay": 0.0})
     if opt_cfg["algorithm"] not in OPTIMISERS:
         raise NotImplementedError(f"'{opt_cfg['algorithm']}' optimiser has not been implemented!")

@@ -2614,6 +2614,49 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     return lse, tscore
 
 
+def lse_smooth_workspace_bytes(Q, N, d, strips=0, bf16=False):
+    """bytes of the smoothed log-sum-exp route's workspace (lse_workspace_bytes' layout with four floats per cell of the strip partials);
+    needs no device; 0 for arguments the call refuses"""
+    return int(lib().rgcn_distmult_lse_smooth_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
+
+
+def distmult_lse_smooth(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False,
+                        filt=None):
+    """(lse, tscore, ssum, cnt): distmult_lse's lse and tscore, bit for bit, and beside them per query ssum fp32 [Q] = the sum of the
+    allowed scores and cnt int32 [Q] = how many are allowed -- what label smoothing over the allowed candidates needs:
+    loss = lse - (1 - eps) tscore - (eps / cnt) ssum.  Arguments as distmult_lse.  Profile tags lse_smooth[_index][_bf16]."""
+    bf16 = nodes.dtype == torch.bfloat16
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n, strips)
+    if not checked:
+        batch = checked_queries(batch, N, rel.shape[0], filt_q, filt_n, bf16)
+    dev = nodes.device
+    lse = torch.empty(Q, device=dev, dtype=torch.float32)
+    tscore = torch.empty(Q, device=dev, dtype=torch.float32)
+    ssum = torch.empty(Q, device=dev, dtype=torch.float32)
+    cnt = torch.empty(Q, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(lse_smooth_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    if filt is not None:
+        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
+        with _on(dev), _timed("lse_smooth_index_bf16" if bf16 else "lse_smooth_index"):
+            if bf16:
+                _check(lib().rgcn_distmult_lse_smooth_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
+                                                                 _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_index_bf16")
+            else:
+                _check(lib().rgcn_distmult_lse_smooth_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
+                                                                _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_index")
+    else:
+        fq, fn = _list_args(filt_q, filt_n, F)
+        with _on(dev), _timed("lse_smooth_bf16" if bf16 else "lse_smooth"):
+            if bf16:
+                _check(lib().rgcn_distmult_lse_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                           _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_bf16")
+            else:
+                _check(lib().rgcn_distmult_lse_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                          _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth")
+    return lse, tscore, ssum, cnt
+
+
 def softmax_grad_workspace_bytes(Q, c_count, d, bf16=False):
     """bytes of a gradient-cell call's workspace (query vectors, query-side bias terms, the chunk's [Q][ceil(c_count / 32)] filter mask);
     needs no device; 0 for arguments the call refuses"""
@@ -2623,17 +2666,24 @@ def softmax_grad_workspace_bytes(Q, c_count, d, bf16=False):
 
 
 def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None,
-                          filt=None):
+                          filt=None, keep=None, uni=None):
     """dS fp32 [Q, c_count]: the gradient cells of the 1-N softmax loss on the candidate columns [c_first, c_first + c_count),
     scale_q (exp(s[q, c] - lse[q]) - [c == target_q]), filtered cells 0; scale_q = gscale / mean_over with gscale a device float [1] or
     [Q] (never read back).  fp32 or bf16 nodes (rel and biases fp32; dS is fp32 either way).  lse: distmult_lse's of the same arguments.
     The caller has range-checked the triples and the lists (distmult_lse did).  out: a float32 buffer of at least Q * c_count elements to
     write into.  filt: a functional.FilterIndex in place of the lists -- the chunk's mask is filled from it.  Profile tags:
-    softmax_grad[_index][_bf16]."""
+    softmax_grad[_index][_bf16].
+    keep, uni (both or neither): label smoothing -- device floats, keep [1] = 1 - eps and uni [Q] = eps / cnt[q] of distmult_lse_smooth;
+    the cells are scale_q (exp(s - lse) - keep [c == target_q] - uni[q]).  Profile tags softmax_grad_smooth[_index][_bf16]."""
     bf16 = nodes.dtype == torch.bfloat16
     Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n)
     _req(lse, "lse"); _req(gscale, "gscale")
     assert lse.shape == (Q,) and gscale.numel() in (1, Q), "lse [Q]; gscale [1] or [Q]"
+    smooth = keep is not None or uni is not None
+    if smooth:
+        assert keep is not None and uni is not None, "keep and uni: both or neither"
+        _req(keep, "keep"); _req(uni, "uni")
+        assert keep.numel() == 1 and uni.shape == (Q,), "keep [1]; uni [Q]"
     assert c_first % 128 == 0 and c_count >= 1 and 0 <= c_first and c_first + c_count <= N, "a chunk starts on a multiple of 128 inside [0, N)"
     dev = nodes.device
     if out is None:
@@ -2646,6 +2696,17 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
+        if smooth:
+            with _on(dev), _timed("softmax_grad_smooth_index_bf16" if bf16 else "softmax_grad_smooth_index"):
+                if bf16:
+                    _check(lib().rgcn_distmult_softmax_grad_smooth_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                                              _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws),
+                                                                              _dp(dS), N, R, d, st), "distmult_softmax_grad_smooth_index_bf16")
+                else:
+                    _check(lib().rgcn_distmult_softmax_grad_smooth_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                                             _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws),
+                                                                             _dp(dS), N, R, d, st), "distmult_softmax_grad_smooth_index")
+            return dS
         with _on(dev), _timed("softmax_grad_index_bf16" if bf16 else "softmax_grad_index"):
             if bf16:
                 _check(lib().rgcn_distmult_softmax_grad_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale), per_query,
@@ -2657,6 +2718,17 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
                        "distmult_softmax_grad_index")
     else:
         fq, fn = _list_args(filt_q, filt_n, F)
+        if smooth:
+            with _on(dev), _timed("softmax_grad_smooth_bf16" if bf16 else "softmax_grad_smooth"):
+                if bf16:
+                    _check(lib().rgcn_distmult_softmax_grad_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), _dp(keep),
+                                                                        _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d,
+                                                                        st), "distmult_softmax_grad_smooth_bf16")
+                else:
+                    _check(lib().rgcn_distmult_softmax_grad_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), _dp(keep),
+                                                                       _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d,
+                                                                       st), "distmult_softmax_grad_smooth")
+            return dS
         with _on(dev), _timed("softmax_grad_bf16" if bf16 else "softmax_grad"):
             if bf16:
                 _check(lib().rgcn_distmult_softmax_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,

@@ -8,6 +8,8 @@ Both are the custom-Function form of what the reference leaves to autograd
 autograd engine's thread and launches on that thread's current HIP stream; it uses
 nothing but the tensors saved on ctx and the immutable RelGraph.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -1396,24 +1398,36 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
     table is saved as it is and never widened as a whole: the gradient cells come from the bf16 kernel, the two contractions stay fp32
     (the chunk's rows are widened into one reused buffer), dnodes is summed in fp32 and rounded to bf16 once at the end.  filt: a
     FilterIndex in place of the lists; it is not a tensor input and is kept by reference on ctx (never written, needs no grad), so the
-    head and the tail loss of a step share one index."""
+    head and the tail loss of a step share one index.
+    smoothing = eps > 0 (label smoothing over the allowed candidates): loss[q] = lse - (1 - eps) s[q, target_q] - (eps / n_q) sum_allowed s,
+    from the smoothed strip pass (lse, tscore, ssum, cnt) composed here with torch ops on the device; keep = 1 - eps [1] and
+    uni = eps / cnt [Q] are saved as device floats and the backward's cells subtract them -- same chunk plan, same contractions."""
 
     @staticmethod
-    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes, filt=None):
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes, filt=None, smoothing=0.0):
         batch = batch.reshape(-1, 3).contiguous()
         nodes, relations = dense(nodes), dense(relations)
         # range-checked here, once, for the forward and the backward (under deferred checks: clamped, the error queued)
         batch = _native.checked_queries(batch, nodes.shape[0], relations.shape[0], filt_q, filt_n, nodes.dtype == torch.bfloat16)
         # (with a FilterIndex there are no lists: checked_queries takes its unfiltered path -- no read-back under deferred checks)
+        ctx.head, ctx.mean, ctx.chunk_bytes, ctx.filt = bool(head), mean, chunk_bytes, filt
+        if smoothing:
+            lse, tscore, ssum, cnt = _native.distmult_lse_smooth(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips,
+                                                                 checked=True, filt=filt)
+            keep = torch.full((1,), 1.0 - smoothing, device=lse.device, dtype=torch.float32)
+            uni = smoothing / cnt.to(torch.float32)                           # cnt >= 1: the target is always allowed
+            ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse, keep, uni)
+            loss = lse - keep * tscore - uni * ssum
+            return loss.mean() if mean else loss
         lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True, filt=filt)
         ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse)
-        ctx.head, ctx.mean, ctx.chunk_bytes, ctx.filt = bool(head), mean, chunk_bytes, filt
         loss = lse - tscore
         return loss.mean() if mean else loss
 
     @staticmethod
     def backward(ctx, g):
-        batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse = ctx.saved_tensors
+        batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, *smooth = ctx.saved_tensors
+        keep, uni = smooth if smooth else (None, None)
         need_n, need_r = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         need_b = sbias is not None and any(ctx.needs_input_grad[4:7])
         Q, (N, d), dev = batch.shape[0], nodes.shape, nodes.device
@@ -1436,7 +1450,7 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
             dqv = None
             for c_first, c_count in plan:
                 dS = _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
-                                                   Q if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt)
+                                                   Q if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt, keep=keep, uni=uni)
                 # both products are skinny (d wide): K is cut into slices, summed in a fixed order, where the output tiles alone would
                 # leave most of the chip idle
                 if dn is not None:                                            # candidate side: every row written once, nothing accumulated
@@ -1465,11 +1479,11 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
             dr = torch.zeros_like(rel) if need_r else None
             if need_b:
                 dsb, dpb, dob = torch.zeros_like(sbias), torch.zeros_like(pbias), torch.zeros_like(obias)
-        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None, None
+        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None, None, None
 
 
 def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
-                          reduction="mean", strips=0, chunk_bytes=None, filt=None, bf16_backward="upcast"):
+                          reduction="mean", strips=0, chunk_bytes=None, filt=None, bf16_backward="upcast", label_smoothing=0.0):
     """1-N softmax cross-entropy of DistMult (an extension: the reference trains on sampled negatives only).  For each triple of `batch`
     (int64 [Q, 3]) every entity is scored as its head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- and
         loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q],
@@ -1492,7 +1506,17 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     query vector nodes[anchor].float() * rel[p]), contracts them in fp32 as above -- only the chunk's rows of the table are widened, into
     one reused [c_count, d] buffer --, accumulates dnodes in fp32, the anchor rows' index_add_ included, and rounds it to bf16 once.
     drel and the bias gradients are fp32.  With fp32 nodes the keyword has no effect.  Relations and biases are fp32, or bf16 with bf16
-    nodes (widened here: they are small)."""
+    nodes (widened here: they are small).
+    label_smoothing = eps, a real number in [0, 1) (else ValueError): the target distribution is 1 - eps on the target plus eps spread
+    evenly over the n_q ALLOWED candidates of the query (filtered entities are out of the problem and get no mass),
+        loss[q] = lse[q] - (1 - eps) s[q, target_q] - (eps / n_q) sum_{n allowed} s[q, n],
+    which without a filter is torch.nn.functional.cross_entropy(logits, target, label_smoothing=eps).  The strip pass carries the sum and
+    the count of the allowed scores beside (max, sum exp) -- lse and the target score keep their bits --, the loss is composed from the
+    four [Q] vectors on the device, and the gradient cells become scale_q (exp(s - lse) - (1 - eps) [n == target_q] - eps / n_q): their
+    row sums are still 0, so the query-side bias gradients stay zeros.  Nothing is read back; bf16 tables go the routes above.  0 takes
+    the unsmoothed path, call for call."""
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, numbers.Real) or not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be a real number in [0, 1), got {label_smoothing!r}")
     if reduction not in ("mean", "none"):
         raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
     if bf16_backward not in ("upcast", "native"):
@@ -1507,7 +1531,7 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
             any(t is not None and t.requires_grad for t in params):
         nodes = nodes.float()
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
-                                      chunk_bytes, filt)
+                                      chunk_bytes, filt, float(label_smoothing))
 
 
 class _MaskedCE(torch.autograd.Function):

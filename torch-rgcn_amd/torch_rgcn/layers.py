@@ -96,18 +96,20 @@ class DistMult(Module):
             return F_.distmult_score(triples, nodes, self.relations, self.sbias, self.pbias, self.obias)
         return F_.distmult_score(triples, nodes, self.relations)
 
-    def softmax_loss(self, triples, nodes, head=False, filt_q=None, filt_n=None, reduction="mean", filt=None, bf16_backward="upcast"):
+    def softmax_loss(self, triples, nodes, head=False, filt_q=None, filt_n=None, reduction="mean", filt=None, bf16_backward="upcast",
+                     label_smoothing=0.0):
         """1-N softmax cross-entropy of `triples` [Q, 3] against every entity as the head (head=True) or the tail, with this decoder's
         relations and biases (functional.distmult_softmax_loss: no [Q, N] logits; an extension, the reference has no counterpart).
         filt_q / filt_n: int32 device lists of (query, entity) cells left out of the denominator; filt: a functional.FilterIndex in
         their place (the known completions of every query, looked up on the device: the filtered step stays capturable).
         bf16_backward: "upcast" or "native", the route of a bf16 embedding table that trains (functional.distmult_softmax_loss; no effect
-        on fp32 embeddings)."""
+        on fp32 embeddings).  label_smoothing: eps in [0, 1), spread evenly over the candidates that are not filtered (0: none)."""
         _require_gpu(nodes, "DistMult node embeddings")
         triples = triples.to(nodes.device)
         # (without b_init the three biases are registered as None: one call serves both)
         return F_.distmult_softmax_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias,
-                                        filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward)
+                                        filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward,
+                                        label_smoothing=label_smoothing)
 
 
 class _RGCBase(Module):
