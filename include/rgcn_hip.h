@@ -1040,6 +1040,67 @@ RGCN_API int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, 
                                                           const float *gscale, const float *keep, const float *uni, int32_t per_query,
                                                           int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
                                                           int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+/* 1-N multi-label binary cross-entropy of DistMult ("K-vs-All"; an extension -- the reference's sampled-negative BCE,
+ * experiments/predict_links.py:160-176 with utils/misc.py negative_sampling, is this loss on a sample of the cells), forward sums.
+ * Replaces: distmult_score_all into a [Q, n_nodes] logit matrix, a dense [Q, n_nodes] label matrix and
+ * torch.nn.functional.binary_cross_entropy_with_logits on the two.  With s[q, n] the cell of rgcn_distmult_score_all_* and
+ *   y[q, n] = 1  if n is the query's own target (batch[q, 0] for head queries, batch[q, 2] for tail queries), or (q, n) is on the lists
+ *                (filt_q, filt_n, F), or n is a completion of the query's key in the index (fkeys, fptr, fvals, K);  0 otherwise,
+ * the call returns per query, without the score matrix,
+ *   sp[q] = sum_n softplus(s[q, n])  (float [Q])     ps[q] = sum_{n: y = 1} s[q, n]  (float [Q])     npos[q] = |{n: y = 1}|  (int32 [Q]),
+ * from which the caller composes, for a smoothing eps in [0, 1) (ConvE's form, y' = (1 - eps) y + eps / n_nodes),
+ *   loss[q] = (sp[q] - (1 - eps) ps[q] - (eps / n_nodes) sum_n s[q, n]) / n_nodes .
+ * Three rules differ from the rgcn_distmult_lse_* forms.  (1) The mask bits are labels: a listed cell on the query's own target STAYS
+ * set, and the target's bit is set whether it is listed or not (duplicates are harmless: integer OR).  (2) Nothing is filtered out:
+ * every n < n_nodes adds to sp, whatever its bit; only the columns of the ragged last tile at or beyond n_nodes are out of all three
+ * sums.  (3) (the gradient entry below) the rows of dS do not sum to zero.  The lists and the index are two ways to name the positives:
+ * at most ONE of F and K may be non-zero (RGCN_EINVAL); both zero is 1-vs-All, the target alone positive.  The mask
+ * [Q][ceil(n_nodes / 32)] of the workspace is filled on every call.  softplus(s) = max(s, 0) + log(1 + exp(-|s|)): finite for every
+ * finite fp32 score.  Passes: mask (zero, lists or index, targets) | query vectors | one strip pass (rgcn_distmult_lse_smooth_*'s walk,
+ * strips and occupancy: one 16-byte partial per strip half and query, zeros for a strip without a tile) | a merge in index order -- one
+ * `strips`, one answer, run after run.  ps and npos are exact whenever the scores and their partial sums are exact fp32 integers.
+ * _bf16: nodes bf16, the product of rgcn_distmult_score_all_bf16.  No host synchronisation, no memset.  Errors as
+ * rgcn_distmult_lse_smooth_*: NULL sp / ps / npos is RGCN_EINVAL, n_nodes > INT32_MAX RGCN_EUNSUPPORTED (npos is 32-bit); Q == 0
+ * launches nothing.
+ * workspace: rgcn_distmult_bce_sums_workspace_bytes(Q, n_nodes, d, strips, bf16) bytes, 16-byte aligned -- the layout of
+ * rgcn_distmult_lse_smooth_workspace_bytes; no device is asked, 0 for arguments the call refuses. */
+RGCN_API int64_t rgcn_distmult_bce_sums_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
+RGCN_API int rgcn_distmult_bce_sums_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                        const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                        const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                        int64_t K, int32_t strips, void *workspace, float *sp, float *ps, int32_t *npos, int64_t n_nodes,
+                                        int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_bce_sums_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                         const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                         const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                         int64_t K, int32_t strips, void *workspace, float *sp, float *ps, int32_t *npos, int64_t n_nodes,
+                                         int32_t n_rel, int32_t d, void *stream);
+/* 1-N multi-label BCE loss, gradient cells on the candidate columns [c_first, c_first + c_count) (the chunk contract of
+ * rgcn_distmult_softmax_grad_*: c_first a multiple of 128, the chunk inside [0, n_nodes)).  Replaces: autograd through the dense
+ * binary_cross_entropy_with_logits above, a [Q, n_nodes] gradient matrix.
+ *   dS[q, c - c_first] = scale_q (sigmoid(s[q, c]) - keep y[q, c] - uni),     scale_q = gscale[per_query ? q : 0] / (n_nodes * mean_over),
+ * gscale a DEVICE float [1] or [Q] (the upstream gradient, never read back), mean_over = Q for the mean over the queries and 1 for the
+ * loss vector.  smooth: a HOST pointer to two floats {keep, uni} = {1 - eps, eps / n_nodes}, read before the launch and passed to the
+ * kernel as arguments (the ABI passes no float by value); NULL = {1, 0}, no smoothing -- one kernel either way.  y as above, from the
+ * lists or the index (at most one) plus the targets, in the chunk's own mask.  EVERY cell of the chunk is written, and a row of dS does
+ * not sum to zero: the caller owes the query-side biases dS times a column of ones.  sigmoid is formed from exp(-|s|) and cannot
+ * overflow.  dS fp32 row-major [Q, c_count] for both storages; s is bit for bit the cell the sums call added.  No host synchronisation,
+ * no memset.  Errors as rgcn_distmult_softmax_grad_*.
+ * workspace: rgcn_distmult_bce_grad_workspace_bytes(Q, c_count, d, bf16) bytes, 16-byte aligned (query vectors or terms, 2 Q bias
+ * terms, the chunk's mask [Q][ceil(c_count / 32)]); no device is asked, 0 for arguments the call refuses. */
+RGCN_API int64_t rgcn_distmult_bce_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d, int32_t bf16);
+RGCN_API int rgcn_distmult_bce_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                        const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                        const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                        int64_t K, const float *gscale, int32_t per_query, int64_t mean_over, const float *smooth,
+                                        int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes, int32_t n_rel,
+                                        int32_t d, void *stream);
+RGCN_API int rgcn_distmult_bce_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                         const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                         const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                         int64_t K, const float *gscale, int32_t per_query, int64_t mean_over, const float *smooth,
+                                         int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes, int32_t n_rel,
+                                         int32_t d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,9 +15,12 @@
 // an epilogue that selects the k best.  Fourth (rgcn_distmult_lse_*, rgcn_distmult_softmax_grad_*; an extension, the reference trains on
 // sampled negatives only): an epilogue that adds exp(score) for the 1-N softmax loss, and the gradient cells of that loss in column chunks;
 // with label smoothing (rgcn_distmult_lse_smooth_*, rgcn_distmult_softmax_grad_smooth_*) the epilogue also sums and counts the allowed scores.
+// Fifth (rgcn_distmult_bce_sums_*, rgcn_distmult_bce_grad_*; an extension too): the K-vs-All binary cross-entropy -- the mask bits are
+// LABELS, the epilogue sums softplus(score) over every cell and the scores of the positive ones, the gradient cells are sigmoid - label.
 // Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select, add) first; then a tile-precision trait
 // (TileF32 / TileBf16) and the kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel,
-// strip_lse_kernel, strip_lse_smooth_kernel, softmax_grad_kernel -- each written once over <Tile, VEC>; then the entry points.
+// strip_lse_kernel, strip_lse_smooth_kernel, strip_bce_kernel, softmax_grad_kernel, bce_grad_kernel -- each written once over
+// <Tile, VEC>; then the entry points.
 #include <cmath>
 #include <cstdlib>
 
@@ -580,6 +583,73 @@ __device__ __forceinline__ void lse_smooth_store(float m, float l, float t, int 
   if (qrow < Q) part[qrow] = float4{m, l, t, __int_as_float(c)};
 }
 
+// ------------------------------------------------------------------ 1-N multi-label BCE loss: sums per query
+// The K-vs-All binary cross-entropy: loss[q] = (1 / N) sum_n (softplus(s[q, n]) - y'[q, n] s[q, n]).  The mask bits are LABELS here -- a
+// set bit is a positive cell (a known completion, or the query's own target: label_target_kernel) --, and no cell is left out: every
+// column below N is in the sum, whatever its bit.  softplus(s) = max(s, 0) + log(1 + e) with e = exp(-|s|) in (0, 1]: nothing overflows
+// for any finite score, and there is no running maximum to carry.  e is __expf (an argument <= 0, as in tile_lse).  The logarithm is
+// taken once per FOUR cells (a lane's cells of one query row): sum log(1 + e_j) = log(1 + S) with S = prod (1 + e_j) - 1 <= 15, built
+// as S <- S + e + S e, so that terms far below 1 keep their bits instead of vanishing in 1 + e.  log(1 + S) is __logf of a number in
+// (1, 16], except below S = 2^-10, where 1 + S has lost S's low bits and the series S - S^2 / 2 (error S^3 / 3, 3e-7 of S there) is
+// the better value.
+__device__ __forceinline__ float bce_exp(float s) { return __expf(-fabsf(s)); }
+__device__ __forceinline__ float bce_log1p(float S) { return S < 0x1p-10f ? S - 0.5f * S * S : __logf(1.f + S); }
+// sigmoid(s) from the same e: 1 / (1 + e) for s >= 0, e / (1 + e) below -- no exp of a positive number
+__device__ __forceinline__ float bce_sigmoid(float s) {
+  const float e = bce_exp(s), r = __builtin_amdgcn_rcpf(1.f + e);
+  return s >= 0.f ? r : e * r;
+}
+
+// The summing epilogue of one tile, run as tile_lse runs (n_cols = c0 + 64: the 16 lanes of a row stay together; a column past N is
+// clamped for its bias and adds nothing).  Per query row three sums over the columns below N: sp += softplus(s) on every cell, ps += s
+// on the cells whose label bit is set, and the count of those bits -- the set bits of the row's two mask words among the columns of this
+// half that exist, which every lane of the row holds already.  A row's four cells per lane are added in the lane, then over the row's 16
+// lanes, and lane i = row keeps the tile's sums: sp and ps go into the wave's two running registers once per tile (the two that
+// strip_lse_kernel carries), the count into the lane's own LDS slot, as tile_lse<true> keeps its count.
+__device__ __forceinline__ void tile_bce(const f32x4 (&acc)[4][4], int q0, long long c0, int Q, long long N, const float *__restrict__ qb,
+                                         const float *__restrict__ cbias, int head, const unsigned *__restrict__ mask, long long mask_w,
+                                         float &sp, float &ps, int *__restrict__ c) {
+  const int i = threadIdx.x & 15;
+  float tsp = 0.f, tps = 0.f, rsp = 0.f, rps = 0.f, rS = 0.f;
+  int tc = 0;
+  const long long left = N - c0;                              // the columns of this half below N: bits [0, left) of the row's two words
+  const unsigned long long valid = left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1;
+  const unsigned valid0 = (unsigned)valid, valid1 = (unsigned)(valid >> 32);
+  tile_epilogue(acc, q0, c0, Q, c0 + 64, qb, head,
+                [&](int, int qrow) {
+                  LseRow st{{0u, 0u}};
+                  const long long w0 = c0 >> 5;
+                  const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                  if (w0 < mask_w) st.w[0] = mrow[w0];                    // (the right half of a ragged last tile may start past N)
+                  if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  return st;
+                },
+                [&](long long col) { return cbias[col < N ? col : N - 1]; },
+                [&](const LseRow &st, int row, int b, long long col, float sc_) {
+                  const bool in = col < N, pos = in && ((st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u);
+                  const float e = in ? bce_exp(sc_) : 0.f;                // (a column past N: the factor 1)
+                  rS = b == 0 ? e : fmaf(rS, e, rS + e);
+                  rsp = (b == 0 ? 0.f : rsp) + (in ? fmaxf(sc_, 0.f) : 0.f);
+                  rps = (b == 0 ? 0.f : rps) + (pos ? sc_ : 0.f);
+                  if (b == 3) {
+                    const float s1 = row16_sum_f(rsp + bce_log1p(rS)), s2 = row16_sum_f(rps);
+                    tsp = i == row ? s1 : tsp;
+                    tps = i == row ? s2 : tps;
+                    tc = i == row ? __popc(valid0 & st.w[0]) + __popc(valid1 & st.w[1]) : tc;
+                  }
+                });
+  sp += tsp;
+  ps += tps;
+  *c += tc;                                                   // (a row past Q: 0)
+}
+
+// a wave's sums -> partial[2 strip + candidate half of the wave][q] = (sp, ps, the bits of the count, 0): one 16-byte store
+__device__ __forceinline__ void bce_store(float sp, float ps, int c, int q0, int Q, float4 *__restrict__ part) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
+  const int qrow = q0 + 16 * (i >> 2) + 4 * kq + (i & 3);
+  if (qrow < Q) part[qrow] = float4{sp, ps, __int_as_float(c), 0.f};
+}
+
 // ------------------------------------------------------------------ the tile precision and the kernel roles
 // What a kernel has to know about the storage of the entity table: the operand element type, the static LDS slabs of a workgroup, the
 // stride of the query rows and which product loop runs.  Every role below is written once over <Tile, VEC> (VEC: 16-byte loads of the
@@ -801,6 +871,42 @@ __global__ __launch_bounds__(WG) void lse_smooth_merge_kernel(const float4 *__re
   cnt[q] = c;
 }
 
+// Strip sums (1-N BCE loss): sp and ps stay in registers over the strip -- the two that strip_lse_kernel carries --, the label count in
+// LDS, one slot per lane, owned by that lane (1 KB beside the slabs; nothing synchronises).  The launch bound states the occupancy of
+// strip_lse_kernel of the same <Tile, VEC>.  mask: the label bits, never NULL.  A strip without a tile writes zeros.
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG, Tile::strip_waves) void strip_bce_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const unsigned *__restrict__ mask, long long mask_w, float4 *__restrict__ partial, int Q, long long N,
+    int head, int q_blocks, int strips) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  __shared__ int c[WG];
+  c[threadIdx.x] = 0;
+  float sp = 0.f, ps = 0.f;
+  const StripWave w = strip_walk<Tile, VEC>(q, nodes, dm, slabs, Q, N, q_blocks, strips, [&](const f32x4 (&acc)[4][4], int q0, long long c0) {
+    tile_bce(acc, q0, c0, Q, N, qb, cbias, head, mask, mask_w, sp, ps, c + threadIdx.x);
+  });
+  bce_store(sp, ps, c[threadIdx.x], w.q0, Q, partial + (size_t)w.part * Q);
+}
+
+// the strips' sums [n_part][Q] added in index order (one answer for one `strips`)
+__global__ __launch_bounds__(WG) void bce_merge_kernel(const float4 *__restrict__ partial, int n_part, int Q, float *__restrict__ sp,
+                                                       float *__restrict__ ps, int *__restrict__ npos) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= Q) return;
+  float a = 0.f, b = 0.f;
+  int c = 0;
+  for (int p = 0; p < n_part; ++p) {
+    const float4 v = partial[(size_t)p * Q + q];
+    a += v.x;
+    b += v.y;
+    c += __float_as_int(v.z);
+  }
+  sp[q] = a;
+  ps[q] = b;
+  npos[q] = c;
+}
+
 // Gradient cells of the 1-N softmax loss, on the score-all grid cut to the candidate columns [c_first, c_first + c_count) (c_first a
 // multiple of 128: tiles and mask words align as in tile_count): dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),
 // a filtered cell 0; scale_q = gscale[per_query ? q : 0] * inv_q -- the upstream gradient is read on the device.  mask: the filter
@@ -848,13 +954,53 @@ __global__ __launch_bounds__(WG) void softmax_grad_kernel(
                 });
 }
 
-// the filter bits of one chunk of candidate columns (rank_mask_kernel with keep_target = 0, cut to [c_first, c_end))
+// Gradient cells of the 1-N BCE loss, on the grid of softmax_grad_kernel over the candidate columns [c_first, c_first + c_count):
+// dS[q, c - c_first] = scale_q (sigmoid(s[q, c]) - keep y[q, c] - uni), y the label bit of the cell in THIS chunk's mask (never NULL; the
+// query's own target is among the bits), keep = 1 - eps and uni = eps / N plain arguments (1 and 0 without smoothing: one kernel).
+// scale_q = gscale[per_query ? q : 0] * inv, read on the device.  EVERY cell of the chunk is written: a label is not a filter.  The
+// product is the storage's product loop, so s is the cell strip_bce_kernel of the same <Tile, VEC> added.
+struct BceRow { float scale; unsigned w[2]; float *out; };
+
+template <class Tile, bool VEC>
+__global__ __launch_bounds__(WG) void bce_grad_kernel(
+    const typename Tile::elem *__restrict__ q, const typename Tile::elem *__restrict__ nodes, TileDims dm, const float *__restrict__ qb,
+    const float *__restrict__ cbias, const float *__restrict__ gscale, int per_query, float inv, float keep, float uni,
+    const unsigned *__restrict__ mask, long long mask_w, float *__restrict__ dS, int Q, long long N, long long c_first, long long c_count,
+    int head, int q_blocks) {
+  __shared__ __attribute__((aligned(16))) typename Tile::Slabs slabs;
+  const int wave = threadIdx.x >> 6, i = threadIdx.x & 15;
+  const int qt = (blockIdx.x % q_blocks) * 128;
+  const long long ct = c_first + (long long)(blockIdx.x / q_blocks) * 128;
+  const typename Tile::elem *ga[2], *gb[2];
+  stage_rows(q, qt, Q, Tile::q_stride(dm), ga);
+  stage_rows(nodes, ct, N, dm.d, gb);
+  f32x4 acc[4][4];
+  Tile::template product<VEC>(ga, gb, dm, slabs, acc);
+  const long long c0 = ct + (wave & 1) * 64;
+  tile_epilogue(acc, qt + (wave >> 1) * 64, c0, Q, c_first + c_count, qb, head,
+                [&](int, int qrow) {
+                  BceRow st{gscale[per_query ? qrow : 0] * inv, {0u, 0u}, dS + (size_t)qrow * c_count - c_first};
+                  const long long w0 = (c0 - c_first) >> 5;
+                  const unsigned *mrow = mask + (size_t)qrow * mask_w;
+                  if (w0 < mask_w) st.w[0] = mrow[w0];
+                  if (w0 + 1 < mask_w) st.w[1] = mrow[w0 + 1];
+                  return st;
+                },
+                [&](long long col) { return cbias[col]; },
+                [&](const BceRow &st, int, int b, long long col, float sc_) {
+                  const bool pos = (st.w[b >> 1] >> (16 * (b & 1) + i)) & 1u;
+                  st.out[col] = st.scale * ((bce_sigmoid(sc_) - (pos ? keep : 0.f)) - uni);
+                });
+}
+
+// the filter bits of one chunk of candidate columns (rank_mask_kernel cut to [c_first, c_end); keep_target as there)
 __global__ void chunk_mask_kernel(unsigned *__restrict__ mask, long long mask_w, const int *__restrict__ fq, const int *__restrict__ fn,
-                                  long long F, const long long *__restrict__ batch, int head, long long c_first, long long c_end) {
+                                  long long F, const long long *__restrict__ batch, int head, int keep_target, long long c_first,
+                                  long long c_end) {
   for (long long e = (long long)blockIdx.x * WG + threadIdx.x; e < F; e += (long long)gridDim.x * WG) {
     const int q = fq[e];
     const long long n = fn[e];
-    if (n >= c_first && n < c_end && n != rank_target(batch, q, head))
+    if (n >= c_first && n < c_end && (keep_target || n != rank_target(batch, q, head)))
       atomicOr(mask + (size_t)q * mask_w + ((n - c_first) >> 5), 1u << ((n - c_first) & 31));
   }
 }
@@ -899,6 +1045,16 @@ __global__ void rank_mask_kernel(unsigned *__restrict__ mask, long long mask_w, 
     const int q = fq[e], n = fn[e];
     if (keep_target || n != rank_target(batch, q, head)) atomicOr(mask + (size_t)q * mask_w + (n >> 5), 1u << (n & 31));
   }
+}
+
+// label bits (1-N BCE loss): a query's own target is a positive label whether it is listed or not -- one thread per query sets its bit
+// in the mask of the columns [c_first, c_end), when the target lies inside them.  After this the mask IS the label matrix.
+__global__ __launch_bounds__(WG) void label_target_kernel(unsigned *__restrict__ mask, long long mask_w, const long long *__restrict__ batch,
+                                                          int Q, int head, long long c_first, long long c_end) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= Q) return;
+  const long long n = rank_target(batch, q, head);
+  if (n >= c_first && n < c_end) atomicOr(mask + (size_t)q * mask_w + ((n - c_first) >> 5), 1u << ((n - c_first) & 31));
 }
 
 // ------------------------------------------------------------------ device-resident filter index
@@ -1223,14 +1379,16 @@ struct StripCall {
 // What every role does before its own kernels: the workspace carved (strip_layout over the columns [c_first, c_first + c_count)), the
 // operand fields of `c` filled, the filter bits of those columns built and the query kernel of the storage launched.  chunk: the mask is
 // a chunk's (the gradient cells) and chunk_mask_kernel fills it from the lists; else it spans the table and rank_mask_kernel does.
+// labels (the 1-N BCE loss): the bits are labels, not a filter -- the mask exists whatever the lists or the index hold, and
+// label_target_kernel sets every query's own target in it.
 template <class Tile>
 int query_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, bool chunk, int64_t c_first, int64_t c_count,
-                StripCall<Tile> &c) {
+                StripCall<Tile> &c, bool labels = false) {
   const StripLayout L = strip_layout(a.Q, c_count, a.d, a.strips, is_bf16<Tile>, bytes_per_cell);
   char *ws = static_cast<char *>(a.workspace);
   typename Tile::elem *q = reinterpret_cast<typename Tile::elem *>(ws + L.qv);
   float *qb = reinterpret_cast<float *>(ws + L.qb);
-  unsigned *mask = (a.F || a.ix.K) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
+  unsigned *mask = (a.F || a.ix.K || labels) ? reinterpret_cast<unsigned *>(ws + L.mask) : nullptr;
   c.qbl = (a.Q + 127) / 128;
   c.mask_w = L.mask_w;
   c.st = (hipStream_t)a.stream;
@@ -1245,11 +1403,14 @@ int query_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
   const dim3 list_grid((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16));
   if (a.F && chunk)
     hipLaunchKernelGGL(chunk_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
-                       (long long)c_first, (long long)(c_first + c_count));
+                       keep_target, (long long)c_first, (long long)(c_first + c_count));
   else if (a.F)
     hipLaunchKernelGGL(rank_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
                        keep_target);
   if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.head, a.n_nodes, keep_target, c_first, c_first + c_count);
+  if (labels)
+    hipLaunchKernelGGL(label_target_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, mask, (long long)L.mask_w, c.b, (int)a.Q,
+                       a.head, (long long)c_first, (long long)(c_first + c_count));
   launch_query<Tile>(c.st, c.b, a.Q, a.head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, q, qb, a.d);
   return RGCN_OK;
 }
@@ -1258,7 +1419,7 @@ int query_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
 // query_begin over the whole table.
 template <class Tile, class TooMany>
 int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell, int keep_target, TooMany too_many, const char *what,
-                StripCall<Tile> &c) {
+                StripCall<Tile> &c, bool labels = false) {
   int n_cu = 0;
   HIP_TRY(launch_device(&c.dev, &n_cu));
   const int64_t qbl = (a.Q + 127) / 128;
@@ -1267,7 +1428,7 @@ int strip_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
     rgcn_set_error("%s: too many %s in one call; split the batch", a.name, what);
     return RGCN_EUNSUPPORTED;
   }
-  return query_begin<Tile>(a, bytes_per_cell, keep_target, false, 0, a.n_nodes, c);
+  return query_begin<Tile>(a, bytes_per_cell, keep_target, false, 0, a.n_nodes, c, labels);
 }
 
 template <class Tile>
@@ -1673,6 +1834,104 @@ extern "C" int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch
   return softmax_grad<TileBf16>({"distmult_softmax_grad_smooth_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
                                  workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
                                  c_first, c_count, dS, true, keep, uni);
+}
+
+// ------------------------------------------------------------------ 1-N multi-label BCE loss: entry points
+namespace {
+
+// the mask is the label matrix: keep_target = 1 (a listed target stays set) and labels = true (the mask always exists, every query's own
+// target set in it) -- whether the lists, the index or neither names the positives
+template <class Tile>
+int bce_sums(const StripArgs<typename Tile::elem> &a, float *sp, float *ps, int32_t *npos) {
+  if (int rc = strip_check(a, a.Q && (!sp || !ps || !npos), "")) return rc;
+  if (a.Q == 0) return RGCN_OK;
+  StripCall<Tile> c;
+  auto too_many = [&](int64_t) { return a.n_nodes > INT32_MAX; };     // npos counts a query's positive entities in 32 bits
+  if (int rc = strip_begin<Tile>(a, sizeof(float4), 1, too_many, "entities", c, true)) return rc;
+  float4 *part = static_cast<float4 *>(c.part);
+  const int Q = (int)a.Q;
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    hipLaunchKernelGGL((strip_bce_kernel<Tile, decltype(vec)::value>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm,
+                       c.qb, c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+  });
+  hipLaunchKernelGGL(bce_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float4 *)part, (int)(2 * c.n_strips), Q,
+                     sp, ps, (int *)npos);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+// smooth: HOST floats {keep, uni} = {1 - eps, eps / n_nodes}, NULL = {1, 0}; they travel as kernel arguments
+template <class Tile>
+int bce_grad(const StripArgs<typename Tile::elem> &a, const float *gscale, int32_t per_query, int64_t mean_over, const float *smooth,
+             int64_t c_first, int64_t c_count, float *dS) {
+  const bool bad_chunk = c_first < 0 || c_first % 128 || c_count <= 0 || c_first > a.n_nodes - c_count || mean_over < 1;
+  if (int rc = strip_check(a, bad_chunk || (a.Q && (!gscale || !dS)), "c_first a multiple of 128, the chunk inside [0, n_nodes), mean_over >= 1; ")) return rc;
+  if (a.Q == 0) return RGCN_OK;
+  const int64_t nwg = ((c_count + 127) / 128) * ((a.Q + 127) / 128);
+  if (nwg > INT32_MAX) { rgcn_set_error("%s: too many cells in one call; take a smaller chunk", a.name); return RGCN_EUNSUPPORTED; }
+  const float inv = (float)(1.0 / ((double)a.n_nodes * (double)mean_over));
+  const float keep = smooth ? smooth[0] : 1.f, uni = smooth ? smooth[1] : 0.f;
+  StripCall<Tile> c;
+  if (int rc = query_begin<Tile>(a, 0, 1, true, c_first, c_count, c, true)) return rc;  // no partials, the chunk's own label mask
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    hipLaunchKernelGGL((bce_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
+                       gscale, (int)per_query, inv, keep, uni, c.mask, (long long)c.mask_w, dS, (int)a.Q, (long long)a.n_nodes,
+                       (long long)c_first, (long long)c_count, a.head, (int)c.qbl);
+  });
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rgcn_distmult_bce_sums_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
+  return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, sizeof(float4)).total;
+}
+
+extern "C" int64_t rgcn_distmult_bce_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d, int32_t bf16) {
+  return softmax_grad_workspace_bytes(Q, c_count, d, bf16 != 0);
+}
+
+extern "C" int rgcn_distmult_bce_sums_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                          const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                          int64_t K, int32_t strips, void *workspace, float *sp, float *ps, int32_t *npos, int64_t n_nodes,
+                                          int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return bce_sums<TileF32>({"distmult_bce_sums", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes, d,
+                            stream, filter_index(fkeys, fptr, fvals, K)}, sp, ps, npos);
+}
+
+extern "C" int rgcn_distmult_bce_sums_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                           const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                           int64_t K, int32_t strips, void *workspace, float *sp, float *ps, int32_t *npos, int64_t n_nodes,
+                                           int32_t n_rel, int32_t d, void *stream) {
+  (void)n_rel;
+  return bce_sums<TileBf16>({"distmult_bce_sums_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                             n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, sp, ps, npos);
+}
+
+extern "C" int rgcn_distmult_bce_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
+                                          const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                          const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                          int64_t K, const float *gscale, int32_t per_query, int64_t mean_over, const float *smooth,
+                                          int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes, int32_t n_rel,
+                                          int32_t d, void *stream) {
+  (void)n_rel;
+  return bce_grad<TileF32>({"distmult_bce_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes, d,
+                            stream, filter_index(fkeys, fptr, fvals, K)}, gscale, per_query, mean_over, smooth, c_first, c_count, dS);
+}
+
+extern "C" int rgcn_distmult_bce_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
+                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
+                                           const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                           int64_t K, const float *gscale, int32_t per_query, int64_t mean_over, const float *smooth,
+                                           int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes, int32_t n_rel,
+                                           int32_t d, void *stream) {
+  (void)n_rel;
+  return bce_grad<TileBf16>({"distmult_bce_grad_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes,
+                             d, stream, filter_index(fkeys, fptr, fvals, K)}, gscale, per_query, mean_over, smooth, c_first, c_count, dS);
 }
 
 // ------------------------------------------------------------------ device-resident filter index: the mask and the materialised route

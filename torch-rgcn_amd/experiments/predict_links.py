@@ -13,6 +13,10 @@ training.bf16 (1-n only, default false; configs/rgcn/lp-WN18-1n-bf16.yaml): the 
 optimiser is built and both softmax terms run the native bf16 backward -- no fp32 image of the entity table exists during training
 training.label_smoothing (1-n only, default 0; configs/rgcn/lp-WN18-1n-smoothed.yaml): epsilon in [0, 1) of both softmax terms, spread
 evenly over the candidates that are not filtered; combines with training.filtered and training.bf16, and the step is captured all the same
+training.objective "1-n-bce" (configs/rgcn/lp-WN18-1n-bce.yaml): the K-vs-All binary cross-entropy -- every sampled positive against ALL
+entities, tails and heads, every known completion of a query among the TRAINING triples a positive label and everything else a negative;
+the labels come from a device-resident FilterIndex, built once and always on (that is what K-vs-All means), so training.filtered with it
+raises ValueError; training.bf16 and training.label_smoothing (here eps / N over all entities) combine with it, the step is captured
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""
@@ -47,18 +51,21 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     dataset, training, encoder = cfg["dataset"], cfg["training"], cfg["encoder"]
     decoder, evaluation = cfg.get("decoder", {}), cfg.get("evaluation", {})
     objective = training.get("objective", "negative-sampling")
-    if objective not in ("negative-sampling", "1-n"):
+    if objective not in ("negative-sampling", "1-n", "1-n-bce"):
         raise NotImplementedError(f"'{objective}' training objective has not been implemented!")
-    one_to_n = objective == "1-n"
+    k_vs_all = objective == "1-n-bce"
+    one_to_n = objective == "1-n" or k_vs_all          # every entity is a candidate of every positive
     train_filtered = bool(training.get("filtered", False))
+    if train_filtered and k_vs_all:
+        raise ValueError("training.filtered does not combine with training.objective: 1-n-bce (the known completions are its positive labels)")
     if train_filtered and not one_to_n:
         raise ValueError("training.filtered needs training.objective: 1-n (sampled negatives are not filtered)")
     train_bf16 = bool(training.get("bf16", False))
     if train_bf16 and not one_to_n:
-        raise ValueError("training.bf16 needs training.objective: 1-n (the native bf16 backward is the 1-N softmax loss's)")
+        raise ValueError("training.bf16 needs training.objective: 1-n or 1-n-bce (the native bf16 backward is the 1-N losses')")
     label_smoothing = training.get("label_smoothing", 0)
     if label_smoothing and not one_to_n:
-        raise ValueError("training.label_smoothing needs training.objective: 1-n (the sampled-negative objective has no smoothing)")
+        raise ValueError("training.label_smoothing needs training.objective: 1-n or 1-n-bce (the sampled-negative objective has no smoothing)")
     max_epochs = epochs or training.get("epochs", 5000)
     graph_batch_size = training.get("graph_batch_size")
     sampling_function = select_sampling(training.get("sampling_method", "uniform"))
@@ -97,7 +104,8 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
     train = np.asarray(train, dtype=np.int64)          # sampled from every epoch: keep it an array
     train_graph = torch.from_numpy(train)
     # the filter of the 1-N loss: the TRAINING triples alone (validation and test triples must not reach the loss), indexed once
-    train_filter = FilterIndex(generate_true_dict(train), num_nodes, device) if train_filtered else None
+    # (1-n-bce: the same index holds the positive labels, always)
+    train_filter = FilterIndex(generate_true_dict(train), num_nodes, device) if train_filtered or k_vs_all else None
     if encoder["model"] == "rgcn":
         kind = LinkPredictor
     elif encoder["model"] == "c-rgcn":
@@ -165,11 +173,14 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
         return batch_idx, train_lbl
 
     def step_loss(graph, batch_idx, train_lbl):
-        if one_to_n:      # 1-N softmax: half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
+        if one_to_n:      # 1-N softmax or BCE: half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
             x = model.encode(graph)
             decoder_ = model.scoring_function
-            loss = 0.5 * (decoder_.softmax_loss(batch_idx, x, head=False, filt=train_filter, **loss_kw) +
-                          decoder_.softmax_loss(batch_idx, x, head=True, filt=train_filter, **loss_kw))
+            if k_vs_all:  # the index holds the positive labels
+                term = lambda head: decoder_.bce_loss(batch_idx, x, head=head, labels=train_filter, **loss_kw)  # noqa: E731
+            else:         # the index (if any) holds the cells left out
+                term = lambda head: decoder_.softmax_loss(batch_idx, x, head=head, filt=train_filter, **loss_kw)  # noqa: E731
+            loss = 0.5 * (term(False) + term(True))
             return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
         predictions, penalty = model(graph, batch_idx)
         return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty

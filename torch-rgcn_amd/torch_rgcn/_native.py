@@ -2566,7 +2566,7 @@ def checked_queries(batch, N, n_rel, filt_q, filt_n, bf16):
             return batch
         s, p, o = batch[:, 0], batch[:, 1], batch[:, 2]
         bad = (batch.amin() < 0) | (s.amax() >= N) | (o.amax() >= N) | (p.amax() >= n_rel)
-        dev_check_err(bad.to(torch.int32).reshape(1), "1-N softmax loss triples (s, o < num_nodes, p < num_relations)", IndexError)
+        dev_check_err(bad.to(torch.int32).reshape(1), "1-N loss triples (s, o < num_nodes, p < num_relations)", IndexError)
         return torch.stack([s.clamp(0, N - 1), p.clamp(0, n_rel - 1), o.clamp(0, N - 1)], 1)
     _triples_in_range(batch, N, n_rel, bf16)
     return batch
@@ -2736,4 +2736,88 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
             else:
                 _check(lib().rgcn_distmult_softmax_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,
                                                             c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_softmax_grad")
+    return dS
+
+
+# ----------------------------------------------------------------------------- 1-N multi-label BCE loss (an extension)
+def bce_sums_workspace_bytes(Q, N, d, strips=0, bf16=False):
+    """bytes of the BCE strip pass's workspace (lse_smooth_workspace_bytes' layout: query vectors, four floats per cell of the strip
+    partials, the [Q][ceil(N / 32)] LABEL mask, which this route always fills); needs no device; 0 for arguments the call refuses"""
+    return int(lib().rgcn_distmult_bce_sums_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
+
+
+def bce_grad_workspace_bytes(Q, c_count, d, bf16=False):
+    """bytes of a BCE gradient-cell call's workspace (query vectors, query-side bias terms, the chunk's [Q][ceil(c_count / 32)] label
+    mask); needs no device; 0 for arguments the call refuses"""
+    return int(lib().rgcn_distmult_bce_grad_workspace_bytes(Q, c_count, d, 1 if bf16 else 0))
+
+
+def _label_args(lab_q, lab_n, F, labels, head, N, dev):
+    """the (filt_q, filt_n, F, fkeys, fptr, fvals, K) arguments of a BCE entry point: the positive cells as lists, as a
+    functional.FilterIndex, or neither (the targets alone)"""
+    if labels is not None:
+        return (None, None, 0) + _index_args(labels, head, N, dev, lab_q)
+    return _list_args(lab_q, lab_n, F) + (F, None, None, None, 0)
+
+
+def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, strips=0, checked=False,
+                      labels=None):
+    """(sp, ps, npos): per query of `batch` (int64 [Q, 3], device) sp fp32 [Q] = sum_n softplus(s[q, n]) over EVERY entity, ps fp32 [Q] =
+    the sum of s over the positive cells and npos int32 [Q] = their number, s the cells of distmult_score_all[_bf16], without the [Q, N]
+    matrix.  A cell is positive if it is the query's own target, or on the int32 device lists (lab_q, lab_n), or a completion of the
+    query in `labels` (a functional.FilterIndex; not both).  The 1-N BCE loss of a query is (sp - ps) / N.  fp32 or bf16 nodes (rel and
+    biases fp32).  strips, checked: as in distmult_lse.  Profile tags bce_sums[_bf16]."""
+    bf16 = nodes.dtype == torch.bfloat16
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, lab_q, lab_n, strips)
+    if not checked:
+        batch = checked_queries(batch, N, rel.shape[0], lab_q, lab_n, bf16)
+    dev = nodes.device
+    sp = torch.empty(Q, device=dev, dtype=torch.float32)
+    ps = torch.empty(Q, device=dev, dtype=torch.float32)
+    npos = torch.empty(Q, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(bce_sums_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
+    with _on(dev), _timed("bce_sums_bf16" if bf16 else "bce_sums"):
+        if bf16:
+            _check(lib().rgcn_distmult_bce_sums_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps),
+                                                     _dp(npos), N, R, d, st), "distmult_bce_sums_bf16")
+        else:
+            _check(lib().rgcn_distmult_bce_sums_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps),
+                                                    _dp(npos), N, R, d, st), "distmult_bce_sums")
+    return sp, ps, npos
+
+
+def distmult_bce_grad(batch, head, nodes, rel, sbias, pbias, obias, lab_q, lab_n, gscale, mean_over, c_first, c_count, out=None, labels=None,
+                      label_smoothing=0.0):
+    """dS fp32 [Q, c_count]: the gradient cells of the 1-N BCE loss on the candidate columns [c_first, c_first + c_count),
+    scale_q (sigmoid(s[q, c]) - (1 - eps) y[q, c] - eps / N) with eps = label_smoothing and y the labels of distmult_bce_sums; EVERY
+    cell is written.  scale_q = gscale / (N * mean_over) with gscale a device float [1] or [Q] (never read back).  fp32 or bf16 nodes
+    (rel and biases fp32; dS is fp32 either way).  The caller has range-checked the triples and the lists (distmult_bce_sums did).
+    out: a float32 buffer of at least Q * c_count elements to write into.  Profile tags bce_grad[_bf16]."""
+    bf16 = nodes.dtype == torch.bfloat16
+    Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, lab_q, lab_n)
+    _req(gscale, "gscale")
+    assert gscale.numel() in (1, Q), "gscale [1] or [Q]"
+    assert c_first % 128 == 0 and c_count >= 1 and 0 <= c_first and c_first + c_count <= N, "a chunk starts on a multiple of 128 inside [0, N)"
+    dev = nodes.device
+    if out is None:
+        out = torch.empty(Q * c_count, device=dev, dtype=torch.float32)
+    _req(out, "out")
+    assert out.numel() >= Q * c_count
+    dS = out.view(-1)[:Q * c_count].view(Q, c_count)
+    ws = torch.empty(max(bce_grad_workspace_bytes(Q, c_count, d, bf16), 16), device=dev, dtype=torch.uint8)
+    per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
+    # {keep, uni} as host floats: the library reads them before the launch and hands them to the kernel as arguments
+    smooth = (ctypes.c_float * 2)(1.0 - label_smoothing, label_smoothing / N) if label_smoothing else None
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
+    sm = None if smooth is None else ctypes.addressof(smooth)
+    with _on(dev), _timed("bce_grad_bf16" if bf16 else "bce_grad"):
+        if bf16:
+            _check(lib().rgcn_distmult_bce_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(gscale), per_query, over, sm,
+                                                     c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_bce_grad_bf16")
+        else:
+            _check(lib().rgcn_distmult_bce_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(gscale), per_query, over, sm,
+                                                    c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_bce_grad")
     return dS

@@ -1299,14 +1299,15 @@ class FilterIndex:
         return out
 
 
-def _filter_args(filt, filt_q, filt_n, nodes):
-    """the argument rules of `filt=`: a FilterIndex or the lists, built for this entity table, on its device"""
+def _filter_args(filt, filt_q, filt_n, nodes, name="filt", lists="filt_q / filt_n"):
+    """the argument rules of `filt=` (and of `labels=`, under its own names): a FilterIndex or the lists, built for this entity table,
+    on its device"""
     if filt is None:
         return
     if not isinstance(filt, FilterIndex):
-        raise TypeError(f"filt must be a FilterIndex, got {type(filt).__name__}")
+        raise TypeError(f"{name} must be a FilterIndex, got {type(filt).__name__}")
     if filt_q is not None or filt_n is not None:
-        raise ValueError("filt (a FilterIndex) and filt_q / filt_n (the lists) are mutually exclusive")
+        raise ValueError(f"{name} (a FilterIndex) and {lists} (the lists) are mutually exclusive")
     if filt.device != nodes.device:
         raise ValueError(f"the FilterIndex is on {filt.device}, the entity table on {nodes.device}")
     if filt.num_nodes != nodes.shape[0]:
@@ -1428,58 +1429,106 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
     def backward(ctx, g):
         batch, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, *smooth = ctx.saved_tensors
         keep, uni = smooth if smooth else (None, None)
-        need_n, need_r = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        need_b = sbias is not None and any(ctx.needs_input_grad[4:7])
-        Q, (N, d), dev = batch.shape[0], nodes.shape, nodes.device
-        dn = dr = dsb = dpb = dob = None
-        if Q and (need_n or need_r or need_b):
-            if not _is_unit(g):
-                g = dense(g.to(torch.float32))
-            anchor, p = batch[:, 2 if ctx.head else 0], batch[:, 1]
-            bf16 = nodes.dtype == torch.bfloat16
-            qv = nodes[anchor].float() * rel[p]                               # the query vectors, as the query kernel forms them (.float(): bf16 rows)
-            plan = softmax_chunk_plan(Q, N, ctx.chunk_bytes)
-            # bf16 table: the rows of a chunk widened for the query-side product, one buffer for every chunk (the first chunk is the widest)
-            wide = torch.empty(plan[0][1], d, device=dev, dtype=torch.float32) if bf16 and (need_n or need_r) else None
-            buf = torch.empty(Q * plan[0][1], device=dev, dtype=torch.float32)
-            dn = torch.empty(N, d, device=dev, dtype=torch.float32) if need_n else None
-            # the candidate-side bias gradient is dS^T times a column of ones: a product of its own into its own [N, 1] column (beside qv
-            # it would make the rows of dnodes d + 1 wide and cost a second [N, d] copy to take them apart)
-            ones = torch.ones(Q, 1, device=dev) if need_b else None
-            cand = torch.empty(N, 1, device=dev, dtype=torch.float32) if need_b else None
-            dqv = None
-            for c_first, c_count in plan:
-                dS = _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
-                                                   Q if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt, keep=keep, uni=uni)
-                # both products are skinny (d wide): K is cut into slices, summed in a fixed order, where the output tiles alone would
-                # leave most of the chip idle
-                if dn is not None:                                            # candidate side: every row written once, nothing accumulated
-                    _native.gemm(dS, qv, trans_a=True, split_k=_split_k(Q, c_count, d), out=dn[c_first:c_first + c_count])
-                if cand is not None:
-                    _native.gemm(dS, ones, trans_a=True, split_k=_split_k(Q, c_count, 1), out=cand[c_first:c_first + c_count])
-                if need_n or need_r:                                          # query side: the chunks' partials added in chunk order
-                    rows = nodes[c_first:c_first + c_count]
-                    if wide is not None:
-                        rows = wide[:c_count].copy_(rows)
-                    part = _native.gemm(dS, rows, split_k=_split_k(c_count, Q, d))
-                    dqv = part if dqv is None else dqv.add_(part)
-            if need_n:
-                dn.index_add_(0, anchor, dqv * rel[p])
-                if bf16:
-                    dn = dn.to(torch.bfloat16)                                # fp32 sums, one rounding
-            if need_r:
-                dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor].float())
-            if need_b:
-                cand = cand.view(N)
-                zeros = torch.zeros(N, device=dev)
-                dsb, dob = (cand, zeros) if ctx.head else (zeros, cand)
-                dpb = torch.zeros_like(pbias)
-        else:
-            dn = torch.zeros_like(nodes) if need_n else None
-            dr = torch.zeros_like(rel) if need_r else None
-            if need_b:
-                dsb, dpb, dob = torch.zeros_like(sbias), torch.zeros_like(pbias), torch.zeros_like(obias)
-        return None, None, dn, dr, dsb, dpb, dob, None, None, None, None, None, None, None
+
+        def cells(g, c_first, c_count, buf):
+            return _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
+                                                 batch.shape[0] if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt, keep=keep, uni=uni)
+        # sum_n dS[q, n] = 0: the query-side bias gradients are zeros
+        grads = _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias=False)
+        return (None, None) + grads + (None,) * 7
+
+
+def _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias):
+    """-> (dnodes, drel, dsbias, dpbias, dobias) of a loss over all candidates of every query of `batch`, from its gradient cells: the
+    chunk loop the 1-N softmax loss and the 1-N BCE loss share.  cells(g, c_first, c_count, buf) -> dS fp32 [Q, c_count], the cells of
+    the candidate columns [c_first, c_first + c_count) written into `buf`; ctx: head, chunk_bytes and needs_input_grad (inputs 2..6 are
+    nodes, relations and the three biases).  query_bias: the rows of dS do not sum to zero, so the query-side bias gradients are real --
+    dS times a column of ones per chunk, the chunks added in chunk order, then index_add_ into pbias[p] and into obias[anchor] (head) or
+    sbias[anchor] (tail); without it they are zeros."""
+    need_n, need_r = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+    need_b = sbias is not None and any(ctx.needs_input_grad[4:7])
+    Q, (N, d), dev = batch.shape[0], nodes.shape, nodes.device
+    dn = dr = dsb = dpb = dob = None
+    if Q and (need_n or need_r or need_b):
+        if not _is_unit(g):
+            g = dense(g.to(torch.float32))
+        anchor, p = batch[:, 2 if ctx.head else 0], batch[:, 1]
+        bf16 = nodes.dtype == torch.bfloat16
+        qv = nodes[anchor].float() * rel[p]                               # the query vectors, as the query kernel forms them (.float(): bf16 rows)
+        plan = softmax_chunk_plan(Q, N, ctx.chunk_bytes)
+        # bf16 table: the rows of a chunk widened for the query-side product, one buffer for every chunk (the first chunk is the widest)
+        wide = torch.empty(plan[0][1], d, device=dev, dtype=torch.float32) if bf16 and (need_n or need_r) else None
+        buf = torch.empty(Q * plan[0][1], device=dev, dtype=torch.float32)
+        dn = torch.empty(N, d, device=dev, dtype=torch.float32) if need_n else None
+        # the candidate-side bias gradient is dS^T times a column of ones: a product of its own into its own [N, 1] column (beside qv
+        # it would make the rows of dnodes d + 1 wide and cost a second [N, d] copy to take them apart)
+        ones = torch.ones(Q, 1, device=dev) if need_b else None
+        cand = torch.empty(N, 1, device=dev, dtype=torch.float32) if need_b else None
+        ones_c = torch.ones(plan[0][1], 1, device=dev) if need_b and query_bias else None
+        dqv = dqb = None
+        for c_first, c_count in plan:
+            dS = cells(g, c_first, c_count, buf)
+            # both products are skinny (d wide): K is cut into slices, summed in a fixed order, where the output tiles alone would
+            # leave most of the chip idle
+            if dn is not None:                                            # candidate side: every row written once, nothing accumulated
+                _native.gemm(dS, qv, trans_a=True, split_k=_split_k(Q, c_count, d), out=dn[c_first:c_first + c_count])
+            if cand is not None:
+                _native.gemm(dS, ones, trans_a=True, split_k=_split_k(Q, c_count, 1), out=cand[c_first:c_first + c_count])
+            if ones_c is not None:                                        # query-side biases: the rows' sums, added in chunk order
+                part = _native.gemm(dS, ones_c[:c_count], split_k=_split_k(c_count, Q, 1))
+                dqb = part if dqb is None else dqb.add_(part)
+            if need_n or need_r:                                          # query side: the chunks' partials added in chunk order
+                rows = nodes[c_first:c_first + c_count]
+                if wide is not None:
+                    rows = wide[:c_count].copy_(rows)
+                part = _native.gemm(dS, rows, split_k=_split_k(c_count, Q, d))
+                dqv = part if dqv is None else dqv.add_(part)
+        if need_n:
+            dn.index_add_(0, anchor, dqv * rel[p])
+            if bf16:
+                dn = dn.to(torch.bfloat16)                                # fp32 sums, one rounding (DESIGN.md 4.6)
+        if need_r:
+            dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor].float())
+        if need_b:
+            cand = cand.view(N)
+            zeros = torch.zeros(N, device=dev)
+            dpb = torch.zeros_like(pbias)
+            if dqb is not None:
+                dqb = dqb.view(Q)
+                zeros.index_add_(0, anchor, dqb)
+                dpb.index_add_(0, p, dqb)
+            dsb, dob = (cand, zeros) if ctx.head else (zeros, cand)
+    else:
+        dn = torch.zeros_like(nodes) if need_n else None
+        dr = torch.zeros_like(rel) if need_r else None
+        if need_b:
+            dsb, dpb, dob = torch.zeros_like(sbias), torch.zeros_like(pbias), torch.zeros_like(obias)
+    return dn, dr, dsb, dpb, dob
+
+
+def _loss_args(label_smoothing, reduction, bf16_backward, chunk_bytes):
+    """the keyword rules the all-candidate losses share, checked before anything touches a device -> chunk_bytes (None: the default)"""
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, numbers.Real) or not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be a real number in [0, 1), got {label_smoothing!r}")
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    if bf16_backward not in ("upcast", "native"):
+        raise ValueError(f"bf16_backward must be 'upcast' or 'native', got {bf16_backward!r}")
+    if chunk_bytes is None:
+        chunk_bytes = SOFTMAX_CHUNK_BYTES
+    assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
+    return chunk_bytes
+
+
+def _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward):
+    """-> (nodes, relations, sbias, pbias, obias) as the all-candidate losses' autograd functions take them: relations and biases widened
+    for a bf16 table (_widen_query_params), and the table itself widened when it trains on the "upcast" route"""
+    params = (nodes, relations, sbias, pbias, obias)
+    relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
+    if nodes.dtype == torch.bfloat16 and bf16_backward == "upcast" and torch.is_grad_enabled() and \
+            any(t is not None and t.requires_grad for t in params):
+        nodes = nodes.float()
+    return nodes, relations, sbias, pbias, obias
 
 
 def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
@@ -1515,23 +1564,77 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     four [Q] vectors on the device, and the gradient cells become scale_q (exp(s - lse) - (1 - eps) [n == target_q] - eps / n_q): their
     row sums are still 0, so the query-side bias gradients stay zeros.  Nothing is read back; bf16 tables go the routes above.  0 takes
     the unsmoothed path, call for call."""
-    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, numbers.Real) or not 0.0 <= label_smoothing < 1.0:
-        raise ValueError(f"label_smoothing must be a real number in [0, 1), got {label_smoothing!r}")
-    if reduction not in ("mean", "none"):
-        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
-    if bf16_backward not in ("upcast", "native"):
-        raise ValueError(f"bf16_backward must be 'upcast' or 'native', got {bf16_backward!r}")
-    if chunk_bytes is None:
-        chunk_bytes = SOFTMAX_CHUNK_BYTES
-    assert isinstance(chunk_bytes, int) and chunk_bytes >= 1, "chunk_bytes must be a positive int"
+    chunk_bytes = _loss_args(label_smoothing, reduction, bf16_backward, chunk_bytes)
     _filter_args(filt, filt_q, filt_n, nodes)
-    params = (nodes, relations, sbias, pbias, obias)
-    relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
-    if nodes.dtype == torch.bfloat16 and bf16_backward == "upcast" and torch.is_grad_enabled() and \
-            any(t is not None and t.requires_grad for t in params):
-        nodes = nodes.float()
+    nodes, relations, sbias, pbias, obias = _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward)
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
                                       chunk_bytes, filt, float(label_smoothing))
+
+
+class _DistMultBCELoss(torch.autograd.Function):
+    """loss[q] = (1 / N) sum_n (softplus(s[q, n]) - y'[q, n] s[q, n]), y' = (1 - eps) y + eps / N, on an fp32 or a bf16 table (relations
+    and biases fp32): composed from the strip pass's (sp, ps) and, with eps > 0, the sum of a row's scores, which needs no kernel --
+    AS[q] = qv[q] . colsum(nodes) + the bias terms.  Saves the inputs alone; the backward is the chunk loop of the 1-N softmax loss
+    (_all_candidate_backward) on this loss's gradient cells, with the query-side bias gradients it owes.  labels: a FilterIndex in place
+    of the lists, kept by reference on ctx as _DistMultSoftmaxLoss keeps its filter."""
+
+    @staticmethod
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, mean, strips, chunk_bytes, labels=None, smoothing=0.0):
+        batch = batch.reshape(-1, 3).contiguous()
+        nodes, relations = dense(nodes), dense(relations)
+        N = nodes.shape[0]
+        batch = _native.checked_queries(batch, N, relations.shape[0], lab_q, lab_n, nodes.dtype == torch.bfloat16)
+        ctx.head, ctx.mean, ctx.chunk_bytes, ctx.labels, ctx.smoothing = bool(head), mean, chunk_bytes, labels, smoothing
+        sp, ps, _ = _native.distmult_bce_sums(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, strips, checked=True, labels=labels)
+        ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, lab_q, lab_n)
+        if smoothing:
+            anchor, p = batch[:, 2 if head else 0], batch[:, 1]
+            rows = (nodes[anchor].float() * relations[p]) @ nodes.sum(0, dtype=torch.float32)     # (the bf16 table is never widened)
+            if sbias is not None:
+                cbias, abias = (sbias, obias) if head else (obias, sbias)
+                rows = rows + (cbias.sum() + N * (pbias[p] + abias[anchor]))
+            loss = (sp - (1.0 - smoothing) * ps - (smoothing / N) * rows) / N
+        else:
+            loss = (sp - ps) / N
+        return loss.mean() if mean else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        batch, nodes, rel, sbias, pbias, obias, lab_q, lab_n = ctx.saved_tensors
+
+        def cells(g, c_first, c_count, buf):
+            return _native.distmult_bce_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, lab_q, lab_n, g, batch.shape[0] if ctx.mean else 1,
+                                             c_first, c_count, out=buf, labels=ctx.labels, label_smoothing=ctx.smoothing)
+        grads = _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias=True)
+        return (None, None) + grads + (None,) * 7
+
+
+def distmult_bce_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, labels=None,
+                      reduction="mean", strips=0, chunk_bytes=None, bf16_backward="upcast", label_smoothing=0.0):
+    """1-N multi-label binary cross-entropy of DistMult ("K-vs-All", the objective ConvE introduced; an extension: the reference's
+    sampled-negative BCE is this loss on a sample of the cells).  For each triple of `batch` (int64 [Q, 3]) every entity is scored as its
+    head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- against the label
+        y[q, n] = 1 if n is the query's own target, or (q, n) is on the int32 device lists (lab_q, lab_n), or n is a known completion of
+                  the query in `labels`, a FilterIndex (lists and index are mutually exclusive: ValueError); 0 otherwise,
+        loss[q] = (1 / N) sum_n (softplus(s[q, n]) - y'[q, n] s[q, n]),        y' = (1 - eps) y + eps / N,    eps = label_smoothing,
+    which is torch.nn.functional.binary_cross_entropy_with_logits(s, y') row by row; the mean over the queries (its default reduction),
+    or the [Q] vector with reduction="none".  Without lists and index only the target is positive (1-vs-All).  Three rules differ from
+    distmult_softmax_loss: a listed target STAYS a label (there it is dropped from the filter); nothing is filtered out -- every entity
+    is in every query's sum and receives a gradient, and N in eps / N is the number of entities --; and the rows of the gradient cells
+    do not sum to zero, so the query-side bias gradients (pbias, and obias if head else sbias) are real.
+    The [Q, N] logits and labels never exist: the label matrix is the 1-bit-per-cell mask the routes above use as a filter, filled on
+    the device, and the forward is one strip pass that carries sum softplus(s) and the sum of the positive scores per query (DESIGN.md
+    4.5); with eps > 0 the sum of a row's scores is qv . colsum(nodes) plus the bias terms, no kernel.  The backward is
+    distmult_softmax_loss's: the product again in chunks of candidate columns (softmax_chunk_plan, chunk_bytes) into one reused buffer of
+    cells scale_q (sigmoid(s) - (1 - eps) y - eps / N), contracted on the matrix cores in the same order, the same index_add_ last; the
+    query-side bias gradients are dS times a column of ones, the chunks added in chunk order.  Nothing is read back: range checks go
+    through checked_queries, and under route deferred_checks = 1 the call does not synchronise and can be captured.
+    bf16 nodes, bf16_backward ("upcast" / "native"), strips: as in distmult_softmax_loss.  label_smoothing: a real number in [0, 1)."""
+    chunk_bytes = _loss_args(label_smoothing, reduction, bf16_backward, chunk_bytes)
+    _filter_args(labels, lab_q, lab_n, nodes, name="labels", lists="lab_q / lab_n")
+    nodes, relations, sbias, pbias, obias = _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward)
+    return _DistMultBCELoss.apply(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, reduction == "mean", strips, chunk_bytes,
+                                  labels, float(label_smoothing))
 
 
 class _MaskedCE(torch.autograd.Function):

@@ -111,6 +111,18 @@ class DistMult(Module):
                                         filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward,
                                         label_smoothing=label_smoothing)
 
+    def bce_loss(self, triples, nodes, head=False, lab_q=None, lab_n=None, labels=None, reduction="mean", bf16_backward="upcast",
+                 label_smoothing=0.0):
+        """1-N multi-label binary cross-entropy ("K-vs-All") of `triples` [Q, 3] against every entity as the head (head=True) or the
+        tail, with this decoder's relations and biases (functional.distmult_bce_loss: no [Q, N] logits or labels; an extension).
+        A query's own target is a positive label, and so is every cell on the int32 device lists lab_q / lab_n or every known
+        completion in `labels`, a functional.FilterIndex (not both); everything else is a negative.  bf16_backward: as in softmax_loss.
+        label_smoothing: eps in [0, 1), y' = (1 - eps) y + eps / N over ALL entities."""
+        _require_gpu(nodes, "DistMult node embeddings")
+        triples = triples.to(nodes.device)
+        return F_.distmult_bce_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias, lab_q=lab_q, lab_n=lab_n,
+                                    labels=labels, reduction=reduction, bf16_backward=bf16_backward, label_smoothing=label_smoothing)
+
 
 class _RGCBase(Module):
     """Parameter inventory shared by the NC and LP layers."""
