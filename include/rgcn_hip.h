@@ -350,6 +350,25 @@ RGCN_API int rgcn_bwd_blk_prepare_f32(const int32_t *p_pack, const int32_t *p_sr
 RGCN_API int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_packed, float *dX, float *dW, const void *rec,
                               const int32_t *run_ptr, int64_t n_tiles, int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags,
                               float *dbias, int64_t n_src, const int32_t *units, int64_t n_units, int64_t n_split, void *stream);
+/* PACKED chunk records, read by rgcn_spmm_blk_f32 / _bf16 and rgcn_bwd_own_f32 / _bf16 when their flags carry
+ * RGCN_F_PACKED_REC (rgcn_bwd_blk_f32 reads wide records only).  The buffer starts with the val DICTIONARY -- 256 x fp32 bit pattern,
+ * sorted as int32, unused entries 0 -- followed by 96 bytes per chunk:
+ *   [0, 64)   16 x u32   source row << 8 | code      (val = dictionary[code]; every decoded val equals the plan's bit for bit)
+ *   [64, 96)  16 x u16   tile row << 6, as in the wide record; the low 6 bits of rows 0 .. 3 carry bits 0-5, 6-11, 12-17, 18-23 of the
+ *                        header  relation | local << 16  (relation < 2^16, local < 16)
+ * Pads decode to +0.0f with the source and row of their chunk's first slot, as in the wide record.
+ *   rgcn_bwd_blk_packed_rec_bytes(n_chunks)   1024 + 96 n_chunks (no slack: a lane reads 4 or 8 bytes inside its chunk's 96)
+ *   rgcn_bwd_blk_packed_max_rows(owner)       tallest tile the kernels take with packed records: the forward's 1023 (owner = 0); the
+ *                                             relation-owner backward's LDS also holds the dictionary: 762 (owner != 0)
+ *   rgcn_bwd_blk_prepare_packed_f32           arguments as rgcn_bwd_blk_prepare_f32, plus dict [n_dict] (device; 1 <= n_dict <= 256; the
+ *                                             distinct int32 bit patterns of the vals the records decode to, pads' +0.0f included,
+ *                                             ascending) and n_src <= 2^24 */
+#define RGCN_F_PACKED_REC 128
+RGCN_API int64_t rgcn_bwd_blk_packed_rec_bytes(int64_t n_chunks);
+RGCN_API int32_t rgcn_bwd_blk_packed_max_rows(int32_t owner);
+RGCN_API int rgcn_bwd_blk_prepare_packed_f32(const int32_t *p_pack, const int32_t *p_src, const int32_t *p_dst, const float *p_val,
+                                             int32_t tile_rows, const int32_t *chunk_rel, int64_t n_chunks, const int32_t *dict,
+                                             int32_t n_dict, int64_t n_src, void *rec, void *stream);
 /* The same backward, RELATION-OWNER form (round 6; the default on large static graphs with dense buckets -- S1): tall tiles (up to
  * rgcn_bwd_own_max_rows() = 767 rows) walked in soft-window order.  LDS holds the dX tile (doubles, ds_add_f64), the X tile and 1 KiB of
  * scratch per wave, no weight-gradient table: every relation belongs to ONE of the workgroup's rgcn_bwd_own_waves() waves, which walks
@@ -363,7 +382,9 @@ RGCN_API int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_pa
  *             in their relation word): every wave whose last slot names shared_rel in unit_rel takes them, two at a time, from a counter in
  *             LDS after its own range; their sums leave the workgroup through one wave
  *   unit_rel  [units]: unit_rel[w * (units / waves) + local] = relation, -1 = unused slot
- * flags: RGCN_F_RELU; dbias as rgcn_bwd_blk_f32.  No hub pieces.  Sums in arrival order.  Same autograd duals of layers.py:293-301. */
+ * flags: RGCN_F_RELU; RGCN_F_PACKED_REC: rec holds the packed records of rgcn_bwd_blk_prepare_packed_f32 (tiles of up to
+ * rgcn_bwd_blk_packed_max_rows(1) rows); dbias as rgcn_bwd_blk_f32.  No hub pieces.  Sums in arrival order.  Same autograd duals of
+ * layers.py:293-301. */
 RGCN_API int32_t rgcn_bwd_own_waves(void);
 RGCN_API int32_t rgcn_bwd_own_units(void);
 RGCN_API int32_t rgcn_bwd_own_max_rows(void);
@@ -373,7 +394,7 @@ RGCN_API int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_pa
 /* rgcn_bwd_own_bf16: the same backward on bf16 storage (replaces layers.py:293-301's duals for a layer called with bf16 features):
  * G [n_src][16], X [n_dst][16] and dX [n_dst][16] are bf16 (uint16_t bit patterns).  G is gathered as 32-byte rows and widened; every product
  * and sum is fp32 (the dX tile fp64 in LDS), dX is rounded to bf16 once (round to nearest even, NaN stays NaN).  Wt_packed, dW and dbias stay
- * fp32.  Records, own_ptr, group_ptr / shared_rel, unit_rel and dbias as rgcn_bwd_own_f32; flags = 0 (no ReLU mask: the caller masks G); n_src < 2^26 (the records
+ * fp32.  Records, own_ptr, group_ptr / shared_rel, unit_rel and dbias as rgcn_bwd_own_f32; flags = 0 or RGCN_F_PACKED_REC (no ReLU mask: the caller masks G); n_src < 2^26 (the records
  * address rows as src << 6). */
 RGCN_API int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const float *Wt_packed, uint16_t *dX, float *dW, const void *rec,
                                const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
@@ -410,7 +431,8 @@ RGCN_API int rgcn_softwin_fill(const int32_t *dst, const int32_t *src, const flo
  * records of rgcn_bwd_blk_prepare_f32.  For layers whose (tile, relation) buckets on the wave-owned tiles of rgcn_spmm_f32 are mostly
  * padding and whose relations do not fit rgcn_spmm_csr_d16_f32's LDS (AM as shipped, layer 2: R = 267); one launch instead of
  * rgcn_spmm_scatter_f32 + rgcn_segment_gather_sum_f32.  W_packed: rgcn_pack_w16_f32 fragments; bias may be NULL; flags: RGCN_F_RELU
- * (the activation in the epilogue; not with hub pieces).  units / n_units / n_split as above (pieces add into a zeroed out; the
+ * (the activation in the epilogue; not with hub pieces), RGCN_F_PACKED_REC (rec holds packed records; also rgcn_spmm_blk_bf16).
+ * units / n_units / n_split as above (pieces add into a zeroed out; the
  * RGCN_U_FIRST piece adds the bias). */
 RGCN_API int32_t rgcn_spmm_blk_max_rows(void);
 RGCN_API int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const float *bias, float *out, const void *rec,

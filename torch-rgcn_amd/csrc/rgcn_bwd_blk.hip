@@ -24,6 +24,10 @@
 //     the sums are exact to fp64 before the one rounding to fp32 in the epilogue;
 //   * per chunk ONE 176-byte record (rgcn_bwd_blk_prepare_f32, made once per plan): 16 x {source row << 6, val}, the 16 tile
 //     rows (x 64) as 16-bit numbers (lane (k, m) reads the four of its quarter k with one 8-byte load), the relation.
+//     The forward kernel below and the relation-owner backward (rgcn_bwd_own.hip) also read a PACKED form of it, 96 bytes per chunk
+//     (rgcn_bwd_blk_prepare_packed_f32; layout in rgcn_device.h): 16 x (source row << 8 | code) with the val in
+//     a dictionary of at most 256 bit patterns that heads the buffer, the same 16 tile rows, the relation word in the low 6 bits of
+//     rows 0 .. 3 -- for static plans whose fields fit; this kernel reads the wide records only.
 // LDS: rows x 192 bytes + 16 KiB transposition scratch + R KiB (R / 4 KiB with RGCN_F_DIAG4): S1 (R = 101) -> tiles of up to
 // 227 rows (218 used: 18 tiles per CU); AM with 4 x 4 diagonal blocks (R = 267) -> up to 406 rows.
 //
@@ -68,7 +72,7 @@ constexpr int BLK_FWD_TQS = 16 / BLK_FWD_NW;   // a thread's share of the tile a
 #define RGCN_BLK_BWD_U 3
 #endif
 constexpr int BLK_BWD_U = RGCN_BLK_BWD_U;
-constexpr int BLK_REC = 176;          // bytes per chunk record: 16 x {source row << 6, val} | 16 x u16 tile row | relation | 12 spare
+constexpr int BLK_REC = 176;          // bytes per WIDE chunk record: 16 x {source row << 6, val} | 16 x u16 tile row | relation | 12 spare (packed: PK_REC, rgcn_device.h)
 constexpr int BLK_REC_ROWS = 128;
 constexpr int BLK_REC_HDR = 160;
 constexpr int BLK_LDS_MAX = 160 * 1024;
@@ -130,6 +134,60 @@ __global__ __launch_bounds__(WG) void bwd_blk_prep_kernel(const int2 *__restrict
     *reinterpret_cast<uint2 *>(r + s * 8) = uint2{(unsigned)src << 6, __builtin_bit_cast(unsigned, val)};
     *reinterpret_cast<unsigned short *>(r + BLK_REC_ROWS + s * 2) = (unsigned short)(dl << 6);     // tile row x 64: the LDS offset of its X row
     if (s == 0) *reinterpret_cast<int4 *>(r + BLK_REC_HDR) = int4{chunk_rel[c], 0, 0, 0};
+  }
+}
+
+// Slot e of the plan as a chunk record holds it (what bwd_blk_prep_kernel above computes, kept in ONE place for the packed form): source,
+// tile row and val, a pad (val forced to +0.0f) on the source and the row of its chunk's first slot.  Called by all 64 lanes of a wave.
+__device__ __forceinline__ void prep_slot(const int2 *__restrict__ p_pack, const int *__restrict__ p_src, const int *__restrict__ p_dst,
+                                          const float *__restrict__ p_val, int tile_rows, long long e, bool in, int &src, int &dl, float &val) {
+  src = 0; dl = -1; val = 0.f;
+  if (in) {
+    if (p_pack) {
+      const int2 pk = p_pack[e];
+      src = pk.x & 0xFFFFFF;
+      dl = (int)((unsigned)pk.x >> 24);
+      if (dl == 0xFF) dl = -1;
+      val = __builtin_bit_cast(float, pk.y);
+    } else {
+      const int gd = p_dst[e];
+      src = p_src[e];
+      dl = gd < 0 ? -1 : gd % tile_rows;
+      val = p_val[e];
+    }
+  }
+  const int lane0 = (threadIdx.x & 63) & ~15;
+  const int src0 = __shfl(src, lane0), dl0 = __shfl(dl, lane0);
+  if (dl < 0) { val = 0.f; src = dl0 < 0 ? 0 : src0; dl = dl0 < 0 ? 0 : dl0; }
+}
+
+// The same plan -> PACKED records (rgcn_device.h: the dictionary, then 96 bytes per chunk).  Every field the kernels decode equals the
+// wide record's: the val's bit pattern (its code found by binary search in the dictionary, sorted as int32), source, tile row, relation
+// word; pads decode to +0.0f with the source and the row of their chunk's first slot.  Block 0 also copies the dictionary in.
+__global__ __launch_bounds__(WG) void bwd_blk_prep_packed_kernel(const int2 *__restrict__ p_pack, const int *__restrict__ p_src,
+                                                                 const int *__restrict__ p_dst, const float *__restrict__ p_val, int tile_rows,
+                                                                 const int *__restrict__ chunk_rel, const int *__restrict__ dict, int n_dict,
+                                                                 char *__restrict__ rec, long long n_chunks) {
+  if (blockIdx.x == 0) reinterpret_cast<int *>(rec)[threadIdx.x] = (int)threadIdx.x < n_dict ? dict[threadIdx.x] : 0;      // (WG == PK_DICT)
+  const long long e = (long long)blockIdx.x * WG + threadIdx.x;          // slot index
+  const long long c = e >> 4;
+  const int s = (int)(e & 15);
+  const bool in = c < n_chunks;
+  int src, dl;
+  float val;
+  prep_slot(p_pack, p_src, p_dst, p_val, tile_rows, e, in, src, dl, val);
+  if (in) {
+    const int bits = __builtin_bit_cast(int, val);
+    int lo = 0, hi = n_dict - 1;                                         // the first entry >= bits (the dictionary holds every pattern of the plan)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (dict[mid] < bits) lo = mid + 1;
+      else hi = mid;
+    }
+    const unsigned hdr = (unsigned)chunk_rel[c] & 0xFFFFFu;              // relation (16 bits) | local unit (4 bits)
+    char *r = rec + PK_DICT_BYTES + (size_t)c * PK_REC;
+    *reinterpret_cast<unsigned *>(r + s * 4) = (unsigned)src << 8 | (unsigned)lo;
+    *reinterpret_cast<unsigned short *>(r + PK_REC_ROWS + s * 2) = (unsigned short)(dl << 6 | (s < 4 ? (int)((hdr >> (6 * s)) & 63u) : 0));
   }
 }
 
@@ -486,7 +544,9 @@ __global__ __launch_bounds__(64 * BLK_NW) void bwd_blk_d16_kernel(
 // BF (rgcn_spmm_blk_bf16): bit 1 = X holds bf16 rows (32 bytes: the record's byte offset src << 6 halved, an 8-byte gather per
 // lane, widened), bit 2 = out holds bf16 rows (rounded once, in the epilogue).  Pieces of hub tiles always add fp32 rows (the launcher hands
 // such plans an fp32 scratch and rounds it afterwards).  BF = 0 is the fp32 kernel as it was.
-template <bool RELU, int TQ, int BF = 0>
+// PK: the records are the packed ones (rgcn_bwd_blk_prepare_packed_f32: two record loads per lane and chunk instead of three, the val
+// from the dictionary's copy in LDS -- 1 KiB behind the counter); PK = false is the kernel on the wide records as it was.
+template <bool RELU, int TQ, int BF = 0, bool PK = false>
 __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
     const float *__restrict__ X, const float *__restrict__ Wp, const float *__restrict__ bias, float *__restrict__ out,
     const char *__restrict__ rec, const int *__restrict__ run_ptr, int n_tiles, int tile_rows, int n_dst, int R,
@@ -498,6 +558,7 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
   float4 *tz = reinterpret_cast<float4 *>(lds);                   // the tile [rows][16] doubles as 16-byte units (zeroing)
   const double2 *td2 = reinterpret_cast<const double2 *>(lds);
   int *ctl = reinterpret_cast<int *>(lds + (size_t)tile_rows * 128u);      // [0]: next quad of the tile
+  const float *dict = reinterpret_cast<const float *>(lds + (size_t)tile_rows * 128u + 64u);      // PK: the val dictionary
 
   auto unit_of = [&](int u) {
     if (units) return units[u];
@@ -514,6 +575,8 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
   int ns = static_quads(nq);
   for (int i = tid; i < tile_rows * 8; i += NT) tz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (tid == 0) ctl[0] = NW * (ns + 1);
+  if constexpr (PK)
+    for (int i = tid; i <= PK_DICT; i += NT) ctl[16 + i] = i < PK_DICT ? reinterpret_cast<const int *>(rec)[i] : 0;
   __syncthreads();
 
   const int m = lane & 15, k = lane >> 4;
@@ -531,10 +594,16 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       const int cc = min(c + j, last);                          // scalar: chunks past the tile re-read its last chunk (val forced to 0)
+      if constexpr (PK) {       // the slot word of slot m, the four row words of quarter k (lane 0's carry the header)
+        const char *r = rec + PK_DICT_BYTES + (size_t)cc * PK_REC;
+        sl_n[j].x = *reinterpret_cast<const unsigned *>(r + (unsigned)m * 4u);
+        rw_n[j] = *reinterpret_cast<const uint2 *>(r + ((unsigned)PK_REC_ROWS + (unsigned)k * 8u));
+      } else {
       const char *r = rec + (size_t)cc * BLK_REC;
       sl_n[j] = *reinterpret_cast<const uint2 *>(r + slot_lane);
       rw_n[j] = *reinterpret_cast<const uint2 *>(r + rows_lane);
       hd_n[j] = *reinterpret_cast<const int *>(r + BLK_REC_HDR);
+      }
     }
   };
   int q_cur = wave * ns, q_nxt = 1 < ns ? wave * ns + 1 : NW * ns + wave, q_pos = 2;
@@ -551,13 +620,25 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
       float4 g_[U], w_[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
+        if constexpr (PK) {       // src << 8 | code -> src << 6; the val's LDS read is issued here and awaited at the products
+          w0_[j] = (sl_n[j].x >> 2) & 0xFFFFFFC0u;
+          rw_[j] = rw_n[j];
+          v_[j] = dict[(c + j <= last) ? sl_n[j].x & 0xFFu : (unsigned)PK_DICT];      // (entry PK_DICT is 0.0f: chunks past the tile)
+          hd_[j] = pk_header(__builtin_amdgcn_readfirstlane(rw_n[j].x), __builtin_amdgcn_readfirstlane(rw_n[j].y)) & 0xFFFF;
+        } else {
         w0_[j] = sl_n[j].x;
         rw_[j] = rw_n[j];
         v_[j] = (c + j <= last) ? __builtin_bit_cast(float, sl_n[j].y) : 0.f;
         hd_[j] = __builtin_amdgcn_readfirstlane(hd_n[j]);
+        }
       }
+      if constexpr (PK) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) asm volatile("" : "+v"(w0_[j]));
+      } else {
 #pragma unroll
       for (int j = 0; j < U; ++j) asm volatile("" : "+v"(w0_[j]), "+v"(v_[j]));   // pin the index data here
+      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -593,7 +674,11 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
       // the tile update, one ds_add_f64 per slot quarter (the records hold a slot's tile row x 64; a tile row is 128 bytes of doubles)
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        const unsigned ro[4] = {rw_[j].x & 0xFFFFu, rw_[j].x >> 16, rw_[j].y & 0xFFFFu, rw_[j].y >> 16};
+        unsigned ro[4] = {rw_[j].x & 0xFFFFu, rw_[j].x >> 16, rw_[j].y & 0xFFFFu, rw_[j].y >> 16};
+        if constexpr (PK) {       // (the low 6 bits of a row word may hold header bits)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ro[e] &= 0xFFC0u;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           __hip_atomic_fetch_add(static_cast<double *>(__builtin_assume_aligned(lds + (t_lane + 2u * ro[e]), 8)), (double)acc[j][e], __ATOMIC_RELAXED,
@@ -620,8 +705,13 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
     // (the records just requested are pinned as arrived BEFORE the tile's stores: vmcnt counts in order, and the number of stores differs
     // from thread to thread -- left to the compiler, their first use would wait for the stores to complete)
     lds_barrier();                                                 // every wave has finished adding to the tile
+    if constexpr (PK) {
+#pragma unroll
+      for (int j = 0; j < U; ++j) asm volatile("" : "+v"(sl_n[j].x), "+v"(rw_n[j].x), "+v"(rw_n[j].y));
+    } else {
 #pragma unroll
     for (int j = 0; j < U; ++j) asm volatile("" : "+v"(sl_n[j].x), "+v"(sl_n[j].y), "+v"(rw_n[j].x), "+v"(rw_n[j].y), "+v"(hd_n[j]));
+    }
     const bool shared = uflags & RGCN_U_SHARED;
     const bool with_bias = !shared || (uflags & RGCN_U_FIRST);
 #pragma unroll
@@ -662,6 +752,14 @@ __global__ __launch_bounds__(64 * BLK_FWD_NW) void spmm_blk_d16_kernel(
   }
 }
 
+// the forward kernel on packed records for tiles of up to tq x 256 rows
+template <bool RELU, int BF, class L>
+hipError_t spmm_blk_launch_packed(int tq, L &&launch) {
+  if (tq == 1) return launch(kern_c<spmm_blk_d16_kernel<RELU, 1 * BLK_FWD_TQS, BF, true>>);
+  if (tq == 2) return launch(kern_c<spmm_blk_d16_kernel<RELU, 2 * BLK_FWD_TQS, BF, true>>);
+  if (tq == 3) return launch(kern_c<spmm_blk_d16_kernel<RELU, 3 * BLK_FWD_TQS, BF, true>>);
+  return launch(kern_c<spmm_blk_d16_kernel<RELU, 4 * BLK_FWD_TQS, BF, true>>);
+}
 
 }  // namespace
 
@@ -683,6 +781,26 @@ extern "C" int rgcn_bwd_blk_prepare_f32(const int32_t *p_pack, const int32_t *p_
   return RGCN_OK;
 }
 
+extern "C" int64_t rgcn_bwd_blk_packed_rec_bytes(int64_t n_chunks) { return PK_DICT_BYTES + n_chunks * (int64_t)PK_REC; }
+
+extern "C" int rgcn_bwd_blk_prepare_packed_f32(const int32_t *p_pack, const int32_t *p_src, const int32_t *p_dst, const float *p_val,
+                                               int32_t tile_rows, const int32_t *chunk_rel, int64_t n_chunks, const int32_t *dict,
+                                               int32_t n_dict, int64_t n_src, void *rec, void *stream) {
+  if (n_chunks < 0 || tile_rows <= 0 || tile_rows > 1023 || (!p_pack && n_chunks && (!p_src || !p_dst || !p_val)) ||
+      (p_pack && tile_rows > 255) || (n_chunks && !chunk_rel) || !rec || !dict || n_dict < 1 || n_dict > PK_DICT || n_src <= 0 ||
+      n_src > (int64_t(1) << 24)) {
+    rgcn_set_error("bwd_blk_prepare_packed: bad argument (a dictionary of 1 .. 256 vals, n_src <= 2^24, tiles of at most 1023 rows)");
+    return RGCN_EINVAL;
+  }
+  static_assert(WG == PK_DICT, "block 0 copies the dictionary, one entry per thread");
+  const long long n = n_chunks * RGCN_CHUNK;
+  hipLaunchKernelGGL(bwd_blk_prep_packed_kernel, dim3((unsigned)std::max<long long>(1, (n + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream,
+                     reinterpret_cast<const int2 *>(p_pack), p_src, p_dst, p_val, tile_rows, chunk_rel, dict, n_dict, static_cast<char *>(rec),
+                     (long long)n_chunks);
+  HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
 extern "C" int32_t rgcn_bwd_blk_max_rows(int32_t R, int32_t flags) {
   if (R <= 0 || R >= 0xFFFF) return 0;
   const long long fixed = (long long)bwd_blk_lds(R, (flags & RGCN_F_DIAG4) != 0, 0);
@@ -697,7 +815,7 @@ extern "C" int rgcn_bwd_blk_supported(int32_t tile_rows, int32_t R, int32_t flag
 extern "C" int rgcn_bwd_blk_f32(const float *G, const float *X, const float *Wt_packed, float *dX, float *dW, const void *rec,
                                 const int32_t *run_ptr, int64_t n_tiles, int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags,
                                 float *dbias, int64_t n_src, const int32_t *units, int64_t n_units, int64_t n_split, void *stream) {
-  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !run_ptr || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
+  if (!G || !X || !Wt_packed || !dX || !dW || !rec || !run_ptr || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 || (flags & RGCN_F_PACKED_REC) ||
       (units && ((n_units < n_tiles && !(flags & (RGCN_F_ACCUMULATE | RGCN_F_PARTIAL))) || n_split < 0 || n_units > INT32_MAX || n_units <= 0))) {
     rgcn_set_error("bwd_blk: bad argument");
     return RGCN_EINVAL;
@@ -776,7 +894,8 @@ extern "C" int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const fl
   int dev = 0, n_cu = 0;
   HIP_TRY(launch_device(&dev, &n_cu));
   if (n_split) HIP_TRY(zero_async(out, (size_t)n_dst * 16 * sizeof(float), st));          // pieces of hub tiles add their rows
-  const size_t lds = (size_t)tile_rows * 128 + 64;
+  const bool packed = (flags & RGCN_F_PACKED_REC) != 0;
+  const size_t lds = (size_t)tile_rows * 128 + 64 + (packed ? PK_LDS : 0);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
   auto launch = [&](auto k) -> hipError_t {
     constexpr auto kern = decltype(k)::value;
@@ -787,7 +906,10 @@ extern "C" int rgcn_spmm_blk_f32(const float *X, const float *W_packed, const fl
     return hipGetLastError();
   };
   const int tq = (tile_rows + 255) / 256;
-  if (relu) {
+  if (packed) {
+    if (R > 0xFFFF) { rgcn_set_error("spmm_blk: packed records hold the relation in 16 bits"); return RGCN_EINVAL; }
+    HIP_TRY((relu ? spmm_blk_launch_packed<true, 0>(tq, launch) : spmm_blk_launch_packed<false, 0>(tq, launch)));
+  } else if (relu) {
     if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS>>));
     else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS>>));
     else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 3 * BLK_FWD_TQS>>));
@@ -827,7 +949,9 @@ extern "C" int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, cons
   // hub pieces add fp32 rows into the scratch (zeroed), rounded to bf16 once afterwards: never bf16 atomics (rounded at every add)
   float *dst32 = n_split ? scratch : reinterpret_cast<float *>(out);
   if (n_split) HIP_TRY(zero_async(scratch, (size_t)n_dst * 16 * sizeof(float), st));
-  const size_t lds = (size_t)tile_rows * 128 + 64;
+  const bool packed = (flags & RGCN_F_PACKED_REC) != 0;
+  if (packed && R > 0xFFFF) { rgcn_set_error("spmm_blk_bf16: packed records hold the relation in 16 bits"); return RGCN_EINVAL; }
+  const size_t lds = (size_t)tile_rows * 128 + 64 + (packed ? PK_LDS : 0);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_units, n_cu);
   const float *Xf = reinterpret_cast<const float *>(X);
   auto launch = [&](auto k) -> hipError_t {
@@ -840,7 +964,8 @@ extern "C" int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, cons
   };
   const int tq = (tile_rows + 255) / 256;
   if (n_split) {
-    if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 1>>));
+    if (packed) HIP_TRY((spmm_blk_launch_packed<false, 1>(tq, launch)));
+    else if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 1 * BLK_FWD_TQS, 1>>));
     else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 2 * BLK_FWD_TQS, 1>>));
     else if (tq == 3) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 3 * BLK_FWD_TQS, 1>>));
     else HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<false, 4 * BLK_FWD_TQS, 1>>));
@@ -848,6 +973,8 @@ extern "C" int rgcn_spmm_blk_bf16(const uint16_t *X, const float *W_packed, cons
     hipLaunchKernelGGL(round_rows_bf16_kernel, dim3((unsigned)std::min<long long>((n4 + WG - 1) / WG, 4096)), dim3(WG), 0, st,
                        reinterpret_cast<const float4 *>(scratch), reinterpret_cast<uint2 *>(out), n4);
     HIP_TRY(hipGetLastError());
+  } else if (packed) {
+    HIP_TRY((relu ? spmm_blk_launch_packed<true, 3>(tq, launch) : spmm_blk_launch_packed<false, 3>(tq, launch)));
   } else if (relu) {
     if (tq == 1) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 1 * BLK_FWD_TQS, 3>>));
     else if (tq == 2) HIP_TRY(launch(kern_c<spmm_blk_d16_kernel<true, 2 * BLK_FWD_TQS, 3>>));

@@ -26,6 +26,9 @@
 //
 // The chunk records are the block-tile kernel's (rgcn_bwd_blk_prepare_f32, 176 bytes); the relation word carries the local relation
 // number in its high half: rel | li << 16.  own_ptr[tile * NW + wave] = first chunk of the wave in the tile (n_tiles * NW + 1 entries).
+// Static plans whose fields fit come as PACKED records instead (96 bytes per chunk behind a dictionary of the plan's vals:
+// rgcn_bwd_blk_prepare_packed_f32, rgcn_device.h, template parameter PK): S1 0.4000 -> 0.3878 ms per launch (profiles/packed_rec_*.txt);
+// 116 VGPRs against 118 (bf16: 120 against 122), no scratch.
 // Shared group (own_relations(shared=True)): the relation with the most messages -- S1: the self loops, 41 chunks per tile that gather the
 // tile's own rows -- belongs to no wave; its chunks are group NW of a tile (group_ptr, NW + 1 groups per tile) and go, two at a time, to
 // whichever wave is done with its own range, and the waves' sums of it leave the workgroup as ONE set of atomics.  S1: 0.4139 -> 0.4019 ms
@@ -69,13 +72,17 @@ constexpr int OWN_MAX_ROWS = (OWN_LDS_MAX - OWN_NW * BW_SCR2 * 4 - 64) / 192;   
     asm volatile("" : "+s"(lr));                                                                                   \
   }
 
-size_t bwd_own_lds(int rows) { return (size_t)rows * 192 + (size_t)OWN_NW * BW_SCR2 * 4 + 64; }
+size_t bwd_own_lds(int rows, bool packed = false) { return (size_t)rows * 192 + (size_t)OWN_NW * BW_SCR2 * 4 + 64 + (packed ? PK_LDS : 0); }
+constexpr int OWN_MAX_ROWS_PK = (OWN_LDS_MAX - OWN_NW * BW_SCR2 * 4 - 64 - PK_LDS) / 192;      // 762: the dictionary sits behind the counter
 
 // Timing experiments (ablation library only, make abl; wrong results): ABL bits 2 no dW part, 8 no dX tile update, 16 loads only
 // BF (rgcn_bwd_own_bf16): G, X and dX hold bf16 rows (32 bytes); G is gathered 8 bytes per lane (the record's byte offset
 // src << 6 halved) and widened, the X tile in LDS stays fp32, dX is rounded once on the way out; dW and the bias gradient stay fp32.
 // BF = false is the fp32 kernel as it was.
-template <bool RELU, int NW, int K, int ABL = 0, bool BF = false>
+// PK: packed records (rgcn_bwd_blk_prepare_packed_f32, rgcn_device.h): two record loads per lane and chunk instead of three, the val from
+// the dictionary's copy in LDS (PK_LDS bytes behind the counter), the header rel | local << 16 from lane 0's row words.  PK = false is
+// the kernel on the wide records as it was.
+template <bool RELU, int NW, int K, int ABL = 0, bool BF = false, bool PK = false>
 __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
     const float *__restrict__ G, const float *__restrict__ X, const float *__restrict__ Wtp, float *__restrict__ dX,
     float *__restrict__ dWout, const char *__restrict__ rec, const int *__restrict__ gptr, int gstride, int shared_rel, int n_tiles,
@@ -120,6 +127,9 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
   int c0, c1, s0, s1;
   ranges(t, c0, c1, s0, s1);
   if (tid == 0) lds_st(ctr, 0);
+  const float *dict = reinterpret_cast<const float *>(ctr + 16);      // PK: the val dictionary, entry PK_DICT = 0.0f
+  if constexpr (PK)
+    for (int i = tid; i <= PK_DICT; i += NT) ctr[16 + i] = i < PK_DICT ? reinterpret_cast<const int *>(rec)[i] : 0;
   float4 gs = make_float4(0.f, 0.f, 0.f, 0.f);
   const long long g_n4 = dbias ? (long long)n_src * 4 : 0, g_step = (long long)gridDim.x * NT;
   long long g_i = (long long)blockIdx.x * NT + tid;
@@ -163,10 +173,16 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       const int cc = min(c + j, last);                          // scalar: chunks past the wave's range re-read its last chunk (val forced to 0)
+      if constexpr (PK) {       // the slot word of slot m, the four row words of quarter k (lane 0's carry the header)
+        const char *r = rec + PK_DICT_BYTES + (size_t)cc * PK_REC;
+        sl_n[j].x = *reinterpret_cast<const unsigned *>(r + (unsigned)m * 4u);
+        rw_n[j] = *reinterpret_cast<const uint2 *>(r + ((unsigned)PK_REC_ROWS + (unsigned)k * 8u));
+      } else {
       const char *r = rec + (size_t)cc * OWN_REC;
       sl_n[j] = *reinterpret_cast<const uint2 *>(r + slot_lane);
       rw_n[j] = *reinterpret_cast<const uint2 *>(r + rows_lane);
       hd_n[j] = *reinterpret_cast<const int *>(r + OWN_REC_HDR);
+      }
     }
   };
   if (c0 < c1) request_idx(c0, c1 - 1);
@@ -189,13 +205,25 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
       float4 g_[U], w_[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
+        if constexpr (PK) {       // src << 8 | code -> src << 6; the val's LDS read is issued here and awaited at the products
+          w0_[j] = (sl_n[j].x >> 2) & 0xFFFFFFC0u;
+          rw_[j] = rw_n[j];
+          v_[j] = dict[(c + j <= last) ? sl_n[j].x & 0xFFu : (unsigned)PK_DICT];
+          hd_[j] = pk_header(__builtin_amdgcn_readfirstlane(rw_n[j].x), __builtin_amdgcn_readfirstlane(rw_n[j].y));
+        } else {
         w0_[j] = sl_n[j].x;
         rw_[j] = rw_n[j];
         v_[j] = (c + j <= last) ? __builtin_bit_cast(float, sl_n[j].y) : 0.f;
         hd_[j] = __builtin_amdgcn_readfirstlane(hd_n[j]);
+        }
       }
+      if constexpr (PK) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) asm volatile("" : "+v"(w0_[j]));
+      } else {
 #pragma unroll
       for (int j = 0; j < U; ++j) asm volatile("" : "+v"(w0_[j]), "+v"(v_[j]));   // pin the index data here
+      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -248,6 +276,10 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
         ro[j][1] = rw_[j].x >> 16;
         ro[j][2] = rw_[j].y & 0xFFFFu;
         ro[j][3] = rw_[j].y >> 16;
+        if constexpr (PK) {       // (the low 6 bits of a row word may hold header bits)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ro[j][e] &= 0xFFC0u;
+        }
       }
       // ---- phase 2: dW products, two chunks at a time: the scaled rows go through the wave's scratch into K-over-messages layout, the
       // X rows of the slots come from the X tile; the products accumulate IN the wave's register accumulator of the chunk's relation
@@ -404,6 +436,8 @@ __global__ __launch_bounds__(64 * NW) void bwd_own_d16_kernel(
 extern "C" int32_t rgcn_bwd_own_waves(void) { return OWN_NW; }
 extern "C" int32_t rgcn_bwd_own_units(void) { return OWN_NW * OWN_K; }
 extern "C" int32_t rgcn_bwd_own_max_rows(void) { return OWN_MAX_ROWS; }
+// (defined here: the owner kernel's LDS budget is this file's; the forward takes packed records on every tile it takes at all)
+extern "C" int32_t rgcn_bwd_blk_packed_max_rows(int32_t owner) { return owner ? OWN_MAX_ROWS_PK : rgcn_spmm_blk_max_rows(); }
 
 // group_ptr / shared_rel of the two entries: the plan's pointer array with OWN_NW + 1 groups per tile and the shared relation, or NULL / -1
 // (the kernel then walks own_ptr, OWN_NW groups per tile, and there is no shared group)
@@ -420,8 +454,9 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
     rgcn_set_error("bwd_own: bad argument");
     return RGCN_EINVAL;
   }
-  if (tile_rows > rgcn_bwd_own_max_rows()) {
-    rgcn_set_error("bwd_own: tiles of at most %d rows (got %d)", rgcn_bwd_own_max_rows(), tile_rows);
+  const bool packed = (flags & RGCN_F_PACKED_REC) != 0;
+  if (tile_rows > (packed ? OWN_MAX_ROWS_PK : OWN_MAX_ROWS)) {
+    rgcn_set_error("bwd_own: tiles of at most %d rows (got %d)", packed ? OWN_MAX_ROWS_PK : OWN_MAX_ROWS, tile_rows);
     return RGCN_EUNSUPPORTED;
   }
   if (n_src <= 0 || n_src >= (int64_t(1) << 26)) {
@@ -432,7 +467,7 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
   int dev = 0, n_cu = 0;
   HIP_TRY(launch_device(&dev, &n_cu));
   HIP_TRY(zero_dw_dbias_async(dW, (size_t)R, dbias, st));
-  const size_t lds = bwd_own_lds(tile_rows);
+  const size_t lds = bwd_own_lds(tile_rows, packed);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_tiles, n_cu);
   auto launch = [&](auto k) -> hipError_t {
     constexpr auto kern = decltype(k)::value;
@@ -445,6 +480,7 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
 #ifdef RGCN_ABLATIONS
   {
     const int ABLV = rgcn_option_value(RGCN_OPT_BWD_ABL);
+    if (packed) { rgcn_set_error("bwd_own (ablation library): wide records only"); return RGCN_EUNSUPPORTED; }
     if (ABLV == 2) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 2>>));
     else if (ABLV == 8) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 8>>));
     else if (ABLV == 16) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 16>>));
@@ -452,7 +488,9 @@ extern "C" int rgcn_bwd_own_f32(const float *G, const float *X, const float *Wt_
     return RGCN_OK;
   }
 #endif
-  if (flags & RGCN_F_RELU) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<true, OWN_NW, OWN_K>>));
+  if (packed && (flags & RGCN_F_RELU)) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<true, OWN_NW, OWN_K, 0, false, true>>));
+  else if (packed) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, false, true>>));
+  else if (flags & RGCN_F_RELU) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<true, OWN_NW, OWN_K>>));
   else HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K>>));
   return RGCN_OK;
 }
@@ -461,20 +499,21 @@ extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const flo
                                  const int32_t *own_ptr, const int32_t *group_ptr, int32_t shared_rel, const int32_t *unit_rel, int64_t n_tiles,
                                  int32_t tile_rows, int64_t n_dst, int32_t R, int32_t flags, float *dbias, int64_t n_src, void *stream) {
   if (!G || !X || !Wt_packed || !dX || !dW || !rec || !unit_rel || n_tiles <= 0 || tile_rows <= 0 || n_dst <= 0 || R <= 0 ||
-      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || n_src <= 0 || n_src >= (int64_t(1) << 26) || flags != 0 ||
+      R > 0xFFFF || n_dst > INT32_MAX || n_tiles * (int64_t)OWN_NW >= INT32_MAX || n_src <= 0 || n_src >= (int64_t(1) << 26) || (flags & ~RGCN_F_PACKED_REC) != 0 ||
       !own_groups_ok(own_ptr, group_ptr, shared_rel, n_tiles, R)) {
     rgcn_set_error("bwd_own_bf16: bad argument (the records address G rows as src << 6 in 32 bits: n_src < 2^26; no flags)");
     return RGCN_EINVAL;
   }
-  if (tile_rows > rgcn_bwd_own_max_rows()) {
-    rgcn_set_error("bwd_own_bf16: tiles of at most %d rows (got %d)", rgcn_bwd_own_max_rows(), tile_rows);
+  const bool packed = (flags & RGCN_F_PACKED_REC) != 0;
+  if (tile_rows > (packed ? OWN_MAX_ROWS_PK : OWN_MAX_ROWS)) {
+    rgcn_set_error("bwd_own_bf16: tiles of at most %d rows (got %d)", packed ? OWN_MAX_ROWS_PK : OWN_MAX_ROWS, tile_rows);
     return RGCN_EUNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
   int dev = 0, n_cu = 0;
   HIP_TRY(launch_device(&dev, &n_cu));
   HIP_TRY(zero_dw_dbias_async(dW, (size_t)R, dbias, st));
-  const size_t lds = bwd_own_lds(tile_rows);
+  const size_t lds = bwd_own_lds(tile_rows, packed);
   const unsigned n_blocks = (unsigned)std::min<int64_t>(n_tiles, n_cu);
   auto launch = [&](auto k) -> hipError_t {
     constexpr auto kern = decltype(k)::value;
@@ -485,6 +524,7 @@ extern "C" int rgcn_bwd_own_bf16(const uint16_t *G, const uint16_t *X, const flo
                        group_ptr ? OWN_NW + 1 : OWN_NW, group_ptr ? shared_rel : -1, (int)n_tiles, tile_rows, (int)n_dst, dbias, (int)n_src, unit_rel);
     return hipGetLastError();
   };
-  HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>>));
+  if (packed) HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true, true>>));
+  else HIP_TRY(launch(kern_c<bwd_own_d16_kernel<false, OWN_NW, OWN_K, 0, true>>));
   return RGCN_OK;
 }

@@ -180,6 +180,20 @@ constexpr int BW_SCR2 = 16 * 16;  // floats of transposition scratch per wave: [
                                   // slot m is stored at column (k + (m >> 1)) & 3 (b128 writes of 8 consecutive slots and b32 reads of two
                                   // consecutive slots are conflict-free without the 4-float row padding of the first form: 1 KiB, not 1.25)
 
+// Packed chunk records of the hidden-16 tall-tile kernels (rgcn_bwd_blk_prepare_packed_f32): the buffer starts with
+// the val dictionary (256 fp32 bit patterns, sorted as int32, unused entries 0), then 96 bytes per chunk:
+//   [0, 64)   16 x u32  src << 8 | code          (val = dictionary[code])
+//   [64, 96)  16 x u16  tile row << 6; the low 6 bits of rows 0 .. 3 hold bits 0-5, 6-11, 12-17, 18-23 of the header rel | local << 16
+constexpr int PK_REC = 96;
+constexpr int PK_REC_ROWS = 64;
+constexpr int PK_DICT = 256;
+constexpr int PK_DICT_BYTES = PK_DICT * 4;
+constexpr int PK_LDS = PK_DICT_BYTES + 64;      // the kernels' copy of the dictionary + entry 256 = 0.0f (the val of chunks past a range)
+// the header from lane 0's two row words (wave-uniform: scalar arithmetic)
+__device__ __forceinline__ int pk_header(unsigned x, unsigned y) {
+  return (int)((x & 63u) | ((x >> 10) & 0xFC0u) | ((y & 63u) << 12) | (((y >> 16) & 63u) << 18));
+}
+
 // LDS words other waves write: relaxed workgroup-scope atomics (ds_read_b32 / ds_write_b32).  NOT `volatile`: a volatile access through
 // a generic pointer compiles to flat_load / flat_store sc0 sc1 and a wait for vmcnt(0) -- every poll then drains the wave's global loads.
 __device__ __forceinline__ int lds_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }

@@ -1566,14 +1566,15 @@ def spmm_blk(X, W, bias, plan, relu=False):
     dev = X.device
     Wp = pack_w16(W)
     out = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.float32)
-    rec = _blk_rec(plan)
+    pk = _packed_rec_dict(plan, False)
+    rec = _blk_rec(plan, pk)
     units, n_units, n_split = _blk_units(plan)
     if relu and n_split:
         raise NativeLibraryError("spmm_blk: relu in the epilogue needs a plan without hub pieces")
     with _on(dev), _timed("spmm_blk"):
         _check(lib().rgcn_spmm_blk_f32(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
-                                       plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(units), n_units,
-                                       n_split, _stream(dev)), "spmm_blk")
+                                       plan.tile_rows, plan.n_dst, W.shape[0], (F_RELU if relu else 0) | (F_PACKED_REC if pk is not None else 0),
+                                       _dp(units), n_units, n_split, _stream(dev)), "spmm_blk")
     return out
 
 
@@ -1624,14 +1625,15 @@ def spmm_blk_bf16(X, W, bias, plan, relu=False):
     dev = X.device
     Wp = pack_w16(W)
     out = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.bfloat16)
-    rec = _blk_rec(plan)
+    pk = _packed_rec_dict(plan, False)
+    rec = _blk_rec(plan, pk)
     units, n_units, n_split = _blk_units(plan)
     if relu and n_split:
         raise NativeLibraryError("spmm_blk_bf16: relu in the epilogue needs a plan without hub pieces")
     scratch = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.float32) if n_split else None
     with _on(dev), _timed("spmm_blk_bf16"):
         _check(lib().rgcn_spmm_blk_bf16(_dp(X), _dp(Wp), _dp(bias), _dp(out), _dp(scratch), _dp(rec), _dp(plan.run_ptr), plan.n_tiles,
-                                        plan.tile_rows, plan.n_dst, plan.n_src, W.shape[0], F_RELU if relu else 0, _dp(units), n_units, n_split,
+                                        plan.tile_rows, plan.n_dst, plan.n_src, W.shape[0], (F_RELU if relu else 0) | (F_PACKED_REC if pk is not None else 0), _dp(units), n_units, n_split,
                                         _stream(dev)), "spmm_blk_bf16")
     return out
 
@@ -1695,20 +1697,135 @@ def _lean_plan(plan):
     return lean
 
 
-def _blk_rec(plan):
-    """chunk records of the block-tile backward kernel (rgcn_bwd_blk_prepare_f32: 176 bytes per chunk), made once per plan and
-    cached on it -- static (NC) graphs pay it once, per-call (LP) graphs one small launch per step"""
-    rec = getattr(plan, "_blk_rec", None)
+_PACKED_REC_DEFAULT = "1"      # routes: packed_rec (DESIGN.md 4.1a has the measurement that decides it)
+F_PACKED_REC = 128      # rgcn_spmm_blk_* / rgcn_bwd_own_*: `rec` holds packed records (dictionary + 96 bytes per chunk)
+PK_REC, PK_DICT = 96, 256
+
+
+def rec_fields_torch(src, dst, val, chunk_rel, tile_rows):
+    """what a plan's chunk records hold, slot by slot, as the kernels decode them -- the torch description of rgcn_bwd_blk_prepare_f32's
+    record on the unpacked arrays (dst: global destination row, < 0 = pad): (src, row, val bits) [16 n_chunks] int32 and (rel, unit)
+    [n_chunks] int32.  A pad carries +0.0f and the source and tile row of its chunk's first slot (0, 0 when that is a pad too)."""
+    n = chunk_rel.shape[0] * CHUNK
+    src, dst, bits = src[:n].to(torch.int32), dst[:n].to(torch.int32), val[:n].contiguous().view(torch.int32)
+    pad = dst < 0
+    first = torch.arange(n, device=src.device) // CHUNK * CHUNK
+    pad0 = pad[first]
+    zero = torch.zeros_like(src)
+    row = torch.where(pad, zero, dst % tile_rows)
+    src_f = torch.where(pad, torch.where(pad0, zero, src[first]), src)
+    row_f = torch.where(pad, torch.where(pad0, zero, row[first]), row)
+    return src_f, row_f, torch.where(pad, zero, bits), chunk_rel & 0xFFFF, chunk_rel >> 16
+
+
+def packed_rec_dictionary(dst, val):
+    """the val dictionary of the packed records: the distinct BIT PATTERNS (int32 view: -0.0, NaN payloads and denormals stay apart) the
+    records decode to -- the plan's vals, +0.0f for its pads -- ascending as int32; None when there are more than 256.  One host
+    read (the length)."""
+    bits = torch.where(dst < 0, torch.zeros((), dtype=torch.int32, device=val.device), val.contiguous().view(torch.int32))
+    d = torch.unique(bits)
+    return d.contiguous() if 0 < d.numel() <= PK_DICT else None
+
+
+def pack_rec_fields_torch(src, row, bits, rel, unit, dictionary):
+    """packed records from the fields they decode to (rec_fields_torch's five tensors) and the dictionary (ascending int32 bit patterns):
+    the dictionary (256 x int32, unused entries 0), then per chunk 16 x u32 src << 8 | code and 16 x u16 row << 6 with the header
+    rel | unit << 16 spread over the low 6 bits of rows 0 .. 3 -- the bytes rgcn_bwd_blk_prepare_packed_f32 writes.  CPU tensors.
+    Raises ValueError where a field does not fit (include/rgcn_hip.h)."""
+    n_chunks = rel.shape[0]
+    if dictionary is None or not 0 < dictionary.numel() <= PK_DICT:
+        raise ValueError("packed records: a dictionary of 1 .. 256 distinct val bit patterns")
+    if n_chunks and (int(src.max()) >= (1 << 24) or int(src.min()) < 0):
+        raise ValueError("packed records: sources below 2^24")
+    if n_chunks and (int(row.max()) > 1023 or int(row.min()) < 0 or int(rel.max()) >= (1 << 16) or int(rel.min()) < 0 or
+                     int(unit.max()) >= 16 or int(unit.min()) < 0):
+        raise ValueError("packed records: tile rows of at most 1023, relations below 2^16, at most 16 local units")
+    code = torch.searchsorted(dictionary, bits).clamp(max=dictionary.numel() - 1)
+    if not torch.equal(dictionary[code], bits):
+        raise ValueError("packed records: a val is missing from the dictionary")
+    head = torch.zeros(PK_DICT, dtype=torch.int32)
+    head[:dictionary.numel()] = dictionary
+    words = (src.long() << 8) | code
+    words = torch.where(words >= (1 << 31), words - (1 << 32), words).to(torch.int32).view(n_chunks, CHUNK)
+    hdr = (rel.long() | (unit.long() << 16)).view(n_chunks, 1)
+    slot = torch.arange(CHUNK).view(1, CHUNK)
+    hbits = torch.where(slot < 4, (hdr >> (6 * slot.clamp(max=3))) & 63, torch.zeros_like(hdr))
+    rows = (row.long().view(n_chunks, CHUNK) << 6) | hbits
+    rows = torch.where(rows >= (1 << 15), rows - (1 << 16), rows).to(torch.int16)
+    body = torch.cat([words.view(torch.uint8).view(n_chunks, 64), rows.view(torch.uint8).view(n_chunks, 32)], 1)
+    return torch.cat([head.view(torch.uint8), body.reshape(-1)])
+
+
+def pack_rec_torch(src, dst, val, chunk_rel, tile_rows, n_src, dictionary=None):
+    """rgcn_bwd_blk_prepare_packed_f32 in torch ops on a plan's unpacked arrays (CPU tensors; the same bytes)"""
+    n = chunk_rel.shape[0] * CHUNK
+    if dictionary is None:
+        dictionary = packed_rec_dictionary(dst[:n], val[:n])
+    if n_src > (1 << 24) or tile_rows > 1023:
+        raise ValueError("packed records: n_src <= 2^24, tiles of at most 1023 rows")
+    return pack_rec_fields_torch(*rec_fields_torch(src, dst, val, chunk_rel, tile_rows), dictionary)
+
+
+def unpack_rec_torch(rec, n_chunks):
+    """the fields of packed records as the kernels decode them (rec_fields_torch's five tensors) -- CPU tensors"""
+    rec = rec.cpu()
+    dictionary = rec[:4 * PK_DICT].view(torch.int32)
+    body = rec[4 * PK_DICT:4 * PK_DICT + PK_REC * n_chunks].view(n_chunks, PK_REC)
+    words = body[:, :64].contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    rows = body[:, 64:].contiguous().view(torch.int16).long() & 0xFFFF
+    hdr = (rows[:, 0] & 63) | ((rows[:, 1] & 63) << 6) | ((rows[:, 2] & 63) << 12) | ((rows[:, 3] & 63) << 18)
+    i32 = lambda t: t.to(torch.int32)     # noqa: E731
+    return (i32(words >> 8).reshape(-1), i32(rows >> 6).reshape(-1), dictionary[(words & 0xFF).reshape(-1)], i32(hdr & 0xFFFF), i32(hdr >> 16))
+
+
+def _packed_rec_dict(plan, owner):
+    """the val dictionary of `plan` where the S1 kernels read PACKED records, else None -- then they read the wide
+    ones, as before.  Packed applies to static plans (built with host statistics: looking for the distinct vals reads their number back,
+    once per plan) with at most 256 distinct val bit patterns, n_src <= 2^24, relations below 2^16, at most 16 local units and tiles the
+    kernel's LDS holds next to the dictionary; routes: packed_rec=0 keeps every plan on wide records, and so does the ablation library
+    (make abl, loaded through RGCN_HIP_LIB by tools/: its timing variants exist for the wide form only)."""
+    if routes.get("packed_rec", _PACKED_REC_DEFAULT) == "0" or csrc_sha().endswith("-abl"):      # (the ablation library's kernels read wide records only)
+        return None
+    cached = getattr(plan, "_pk_dict", None)
+    if cached is None:
+        cached = False
+        if getattr(plan, "units_host", None) is not None and plan.chunk_rel.shape[0] > 0 and plan.n_src <= (1 << 24) and \
+                plan.num_rels < (1 << 16) and getattr(plan, "own_per_wave", 0) <= 16:
+            d = packed_rec_dictionary(plan.dst[:plan.chunk_rel.shape[0] * CHUNK], plan.val[:plan.chunk_rel.shape[0] * CHUNK])
+            cached = False if d is None else d
+        plan._pk_dict = cached
+    if cached is False or plan.tile_rows > int(lib().rgcn_bwd_blk_packed_max_rows(1 if owner else 0)):
+        return None
+    return cached
+
+
+def blk_rec_format(plan, owner=False):
+    """'packed' or 'wide': the chunk records rgcn_spmm_blk_* (owner=False) / rgcn_bwd_own_* (owner=True) read on this plan"""
+    return "wide" if _packed_rec_dict(plan, owner) is None else "packed"
+
+
+def _blk_rec(plan, dictionary=None):
+    """chunk records of the block-tile kernels, made once per plan AND FORMAT and cached on it -- static (NC) graphs pay it once, per-call
+    (LP) graphs one small launch per step.  dictionary None: the wide records (rgcn_bwd_blk_prepare_f32: 176 bytes per chunk);
+    _packed_rec_dict's answer: the packed ones (rgcn_bwd_blk_prepare_packed_f32: the dictionary + 96 bytes per chunk)."""
+    attr = "_blk_rec" if dictionary is None else "_blk_rec_pk"
+    rec = getattr(plan, attr, None)
     if rec is None:
         n_chunks = plan.chunk_rel.shape[0]
         dev = plan.chunk_rel.device
-        rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(n_chunks)) + 16, device=dev, dtype=torch.uint8)
         packed = plan.pack is not None and plan.tile_rows <= 255
         with _on(dev):
-            _check(lib().rgcn_bwd_blk_prepare_f32(_dp(plan.pack) if packed else None, _dp(plan.src), _dp(plan.dst), _dp(plan.val),
-                                                  plan.tile_rows, _dp(plan.chunk_rel), n_chunks, _dp(rec), _stream(dev)),
-                   "bwd_blk_prepare")
-        plan._blk_rec = rec
+            if dictionary is None:
+                rec = torch.empty(int(lib().rgcn_bwd_blk_rec_bytes(n_chunks)) + 16, device=dev, dtype=torch.uint8)
+                _check(lib().rgcn_bwd_blk_prepare_f32(_dp(plan.pack) if packed else None, _dp(plan.src), _dp(plan.dst), _dp(plan.val),
+                                                      plan.tile_rows, _dp(plan.chunk_rel), n_chunks, _dp(rec), _stream(dev)),
+                       "bwd_blk_prepare")
+            else:       # (no slack: a lane reads 4 or 8 bytes inside its chunk's 96, the workgroup the dictionary's 1024)
+                rec = torch.empty(int(lib().rgcn_bwd_blk_packed_rec_bytes(n_chunks)), device=dev, dtype=torch.uint8)
+                _check(lib().rgcn_bwd_blk_prepare_packed_f32(_dp(plan.pack) if packed else None, _dp(plan.src), _dp(plan.dst), _dp(plan.val),
+                                                             plan.tile_rows, _dp(plan.chunk_rel), n_chunks, _dp(dictionary), dictionary.numel(),
+                                                             plan.n_src, _dp(rec), _stream(dev)), "bwd_blk_prepare_packed")
+        setattr(plan, attr, rec)
     return rec
 
 
@@ -1741,11 +1858,12 @@ def bwd_own(G, X, W, plan, relu=False, want_db=False):
     dX = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.float32)
     buf = torch.empty(W.numel() + 16, device=dev, dtype=torch.float32)       # dW and db back to back: one fill zeroes both
     dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
-    rec = _blk_rec(plan)
+    pk = _packed_rec_dict(plan, True)
+    rec = _blk_rec(plan, pk)
     with _on(dev), _timed("bwd_fused"):
         _check(lib().rgcn_bwd_own_f32(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(getattr(plan, "group_ptr", None)),
-                                      getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0,
-                                      _dp(db) if want_db else None, plan.n_src, _stream(dev)), "bwd_own")
+                                      getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0],
+                                      (F_RELU if relu else 0) | (F_PACKED_REC if pk is not None else 0), _dp(db) if want_db else None, plan.n_src, _stream(dev)), "bwd_own")
     return (dX, dW, db if want_db else None)
 
 
@@ -1759,10 +1877,12 @@ def bwd_own_bf16(G, X, W, plan, relu=False, want_db=False):
     dX = torch.empty((plan.n_dst, 16), device=dev, dtype=torch.bfloat16)
     buf = torch.empty(W.numel() + 16, device=dev, dtype=torch.float32)
     dW, db = buf[:W.numel()].view_as(W), buf[W.numel():]
-    rec = _blk_rec(plan)
+    pk = _packed_rec_dict(plan, True)
+    rec = _blk_rec(plan, pk)
     with _on(dev), _timed("bwd_own_bf16"):
         _check(lib().rgcn_bwd_own_bf16(_dp(G), _dp(X), _dp(Wtp), _dp(dX), _dp(dW), _dp(rec), _dp(plan.own_ptr), _dp(getattr(plan, "group_ptr", None)),
-                                       getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0], F_RELU if relu else 0, _dp(db) if want_db else None, plan.n_src,
+                                       getattr(plan, "shared_rel", -1), _dp(plan.unit_rel), plan.n_tiles, plan.tile_rows, plan.n_dst, W.shape[0],
+                                       (F_RELU if relu else 0) | (F_PACKED_REC if pk is not None else 0), _dp(db) if want_db else None, plan.n_src,
                                        _stream(dev)), "bwd_own_bf16")
     return (dX, dW, db if want_db else None)
 

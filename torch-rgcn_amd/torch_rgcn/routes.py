@@ -22,6 +22,7 @@ NAMES = (
     "deterministic", "relabel", "tile_rows", "bwd", "bwd_kernel", "twopass", "featureless_csr", "dist_comm", "dist_slabs", "deferred_checks",
     "block_path", "block_fwd", "wgrad_tiles", "wgrad_item_chunks", "wgrad", "spmm_csr", "sparse_path", "graph_build", "fbasis_inplace_mb", "fbasis",
     "distmult_bwd", "diag_path", "capture", "fbasis_tile", "pad16_view", "softwin", "softwin_build", "bwd_own", "own_rows_cap",
+    "packed_rec",
 )
 NATIVE = ("bwd_nw", "gemm_bm", "spmm_u", "wgrad_rg", "wgrad_u", "bwd_abl")
 
