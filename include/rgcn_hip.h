@@ -803,10 +803,60 @@ RGCN_API int rgcn_distmult_bwd_rel_bf16(const int64_t *triples, int64_t T, const
                                         const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
                                         int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 
+/* ComplEx decoder (Trouillon et al. 2016; an extension): the same trilinear product over complex numbers.  A row of
+ * `nodes` [n_nodes, d] or `rel` [n_rel, d], d EVEN (else RGCN_EINVAL), holds h = d / 2 complex features, real parts in columns [0, h),
+ * imaginary parts in [h, d):
+ *   scores[t] = Re sum_k e_s[k] r_p[k] conj(e_o[k])  (+ sbias[s] + pbias[p] + obias[o], all three or none, as DistMult).
+ * Six entries, each with the signature and the rules of the DistMult entry of the same role:
+ * rgcn_complex_fwd_f32 / _bf16: rgcn_distmult_fwd_*, the CSR counting pass riding along in the same way (rgcn_distmult_csr_place serves
+ *   either decoder); one wave per triple, a lane owns four adjacent complex features per pass (two 16-byte pieces of an fp32 row, two
+ *   8-byte pieces of a bf16 row when h % 4 == 0, element by element otherwise), fp32 sums.
+ * rgcn_complex_bwd_nodes_f32 / _bf16: rgcn_distmult_bwd_nodes_*: one wave per entity over the two CSRs, no atomics, dnodes fully written
+ *   (bf16: both sides meet in registers, one rounding).  [Re | Im] of d/d e_s = g conj(r) e_o and of d/d e_o = g e_s r.
+ * rgcn_complex_bwd_rel_f32 / _bf16: rgcn_distmult_bwd_rel_bf16: relation and bias gradients from predicate-sorted triples, d/d r =
+ *   g conj(e_s) e_o, a run of one relation summed in registers and flushed with one fp32 atomic per run and feature; drel and the bias
+ *   gradients are zeroed first.
+ * There is no ComplEx twin of the LDS-table route (rgcn_distmult_bwd_all_*) nor of the atomic scatter (rgcn_distmult_bwd_f32). */
+RGCN_API int rgcn_complex_fwd_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
+                                  const float *sbias, const float *pbias, const float *obias, float *scores,
+                                  int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
+                                  int32_t *ranks, void *stream);
+RGCN_API int rgcn_complex_fwd_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                   const float *sbias, const float *pbias, const float *obias, float *scores,
+                                   int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
+                                   int32_t *ranks, void *stream);
+RGCN_API int rgcn_complex_bwd_nodes_f32(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const float *nodes,
+                                        const float *rel, float *dnodes, int64_t n_nodes, int32_t d, void *stream);
+RGCN_API int rgcn_complex_bwd_nodes_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                         const float *rel, uint16_t *dnodes, int64_t n_nodes, int32_t d, void *stream);
+RGCN_API int rgcn_complex_bwd_rel_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
+                                      const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                      int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_complex_bwd_rel_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
+                                       const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                       int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+
+/* The `head` argument of every entry below that takes (batch, Q, head, ...) is a query form code.  Bit 0 is the direction: which end
+ * of the triple is predicted, hence the candidate-side bias, the target column and the side of the filter lookup.  Bit 1 is the form of
+ * the query vector qv[q], of which every candidate's score is the plain dot product qv[q] . nodes[n]:
+ *   RGCN_QUERY_TAIL (s, p, ?) and RGCN_QUERY_HEAD (?, p, o): DistMult, qv = nodes[fixed] * rel[p] element by element;
+ *   | RGCN_QUERY_COMPLEX: ComplEx on the halves layout above (d even, else RGCN_EINVAL), qv = [Re z | Im z] with
+ *       tail: z = a r       (a = e_s):  [ a_re r_re - a_im r_im | a_re r_im + a_im r_re ]
+ *       head: z = conj(r) a (a = e_o):  [ r_re a_re + r_im a_im | r_re a_im - r_im a_re ]
+ *     each element two rounded fp32 products and one rounded add or subtract (the query kernels are compiled with contraction off); with a
+ *     bf16 table that fp32 element is formed from the widened row and split into three bf16 terms exactly as the DistMult one.
+ * Any other value is RGCN_EINVAL.  Only the query pass looks at the form: the product, the epilogues, the masks and the filter index
+ * serve both decoders unchanged.  Entries that build no query vectors (rgcn_rank_count_f32, rgcn_filter_mask_index,
+ * rgcn_rank_filter_index_f32) accept the form bit and ignore it. */
+#define RGCN_QUERY_TAIL 0
+#define RGCN_QUERY_HEAD 1
+#define RGCN_QUERY_COMPLEX 2
+
 /* Ranking evaluator (utils/misc.py:60-110 + torch_rgcn/layers.py:87-98 on the expanded
  * [bn, N, 3] candidate tensor, which is never built here).  For each of the Q test triples in `batch` (int64
- * [Q,3], device) every entity n is scored as its head (head != 0: (n, p, o)) or tail ((s, p, n)):
+ * [Q,3], device) every entity n is scored as its head (direction RGCN_QUERY_HEAD: (n, p, o)) or tail ((s, p, n)):
  *   scores[q, n] = sum_k (nodes[fixed_q,k] * rel[p_q,k]) * nodes[n,k]  (+ sbias + pbias + obias as layers.py:96)
+ * (DistMult forms; the ComplEx forms replace the query vector as stated above)
  * fp32 MFMA NT product.  qvec [Q,d] and qbias [2Q] (only with biases) are caller-provided scratch; scores is
  * [Q, n_nodes] row-major.  Indices are NOT range-checked on the device (the Python wrapper asserts). */
 RGCN_API int rgcn_distmult_score_all_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes,
@@ -857,7 +907,7 @@ RGCN_API int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int3
                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
                                            int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-/* Top-k link prediction: for each of the Q queries of `batch` the k entities that complete it best as its head (head != 0) or its tail,
+/* Top-k link prediction: for each of the Q queries of `batch` the k entities that complete it best as its head (direction RGCN_QUERY_HEAD) or its tail,
  * ids [Q, k] (int64) and scores [Q, k] (float) -- without a [Q, n_nodes] score buffer.  The scores are bit for bit the cells of
  * rgcn_distmult_score_all_f32 / _bf16 (the same product and bias epilogue); the column of `batch` that is predicted is ignored.
  * Order within a row: score descending, equal scores (==: +0 and -0 are one value, returned as +0) by ascending id -- one answer,

@@ -28,7 +28,28 @@
 
 namespace {
 
-// query vectors and the query-side bias terms; one wave per query
+// The query form code of the `head` argument (rgcn_hip.h): bit 0 is the direction -- which end of the triple is predicted, hence the
+// candidate-side bias, the target column and the side of the filter lookup --, bit 1 the form of the query vector.  Only launch_query looks at
+// the form, to choose the query kernel's instantiation; every kernel receives the direction.
+__host__ __device__ __forceinline__ int query_dir(int head) { return head & RGCN_QUERY_HEAD; }
+
+// One complex feature of a ComplEx query vector: a = the anchor row's (re, im), r = the relation's.  tail queries
+// (s, p, ?): z = a r; head queries (?, p, o): z = conj(r) a -- in both the score of candidate n is qv . nodes[n] with qv = [Re z | Im z].
+// Each element is two rounded products and one rounded add or subtract (contraction off), so a*b - c*d in fp32 on the host forms the same bits.
+__device__ __forceinline__ void complex_query(int dir, float a_re, float a_im, float r_re, float r_im, float &re, float &im) {
+#pragma clang fp contract(off)
+  if (dir) {
+    re = r_re * a_re + r_im * a_im;
+    im = r_re * a_im - r_im * a_re;
+  } else {
+    re = a_re * r_re - a_im * r_im;
+    im = a_re * r_im + a_im * r_re;
+  }
+}
+
+// query vectors and the query-side bias terms; one wave per query.  CX: the ComplEx form, a lane owns complex feature k < d / 2 (a
+// sibling instantiation chosen by launch_query: the DistMult one is the kernel it was).  head: the direction.
+template <bool CX>
 __global__ __launch_bounds__(WG) void rank_query_kernel(
     const long long *__restrict__ batch, int Q, int head, const float *__restrict__ nodes,
     const float *__restrict__ rel, const float *__restrict__ sbias, const float *__restrict__ pbias,
@@ -37,7 +58,14 @@ __global__ __launch_bounds__(WG) void rank_query_kernel(
   if (q >= Q) return;
   const long long s = batch[3 * q], p = batch[3 * q + 1], o = batch[3 * q + 2];
   const long long fixed = head ? o : s;
-  for (int k = lane; k < d; k += 64) qvec[(size_t)q * d + k] = nodes[(size_t)fixed * d + k] * rel[(size_t)p * d + k];
+  if constexpr (CX) {
+    const int h = d >> 1;
+    const float *a = nodes + (size_t)fixed * d, *r = rel + (size_t)p * d;
+    for (int k = lane; k < h; k += 64)
+      complex_query(head, a[k], a[k + h], r[k], r[k + h], qvec[(size_t)q * d + k], qvec[(size_t)q * d + k + h]);
+  } else {
+    for (int k = lane; k < d; k += 64) qvec[(size_t)q * d + k] = nodes[(size_t)fixed * d + k] * rel[(size_t)p * d + k];
+  }
   if (lane == 0 && pbias) {
     qb[2 * q] = pbias[p];
     qb[2 * q + 1] = head ? obias[o] : sbias[s];
@@ -224,8 +252,23 @@ __device__ __forceinline__ void strip_store(int g, int e, int q0, int Q, uint2 *
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// the fp32 query element v as three bf16 terms hi + mid + lo = v; the remainders are exact fp32 differences, formed with contraction off
+__device__ __forceinline__ void query_terms(float v, uint16_t &hi, uint16_t &mid, uint16_t &lo) {
+#pragma clang fp contract(off)
+  hi = bf16_round(v);
+  mid = lo = 0;
+  if (v - v == 0.f) {                                    // finite (an inf / NaN element is its own hi: mid = lo = 0)
+    if ((hi & 0x7FFFu) == 0x7F80u) hi = (hi & 0x8000u) | 0x7F7Fu;     // |v| above the largest bf16 rounds to inf: take the largest bf16, the
+    const float r1 = v - bf16_widen(hi);                              // remainder (same binade: exact) goes to mid and lo
+    mid = bf16_round(r1);
+    lo = bf16_round(r1 - bf16_widen(mid));
+  }
+}
+
 // query terms [3][Q][dpad] (dpad = d rounded up to the K step of 32, the tail zeroed here: the product kernel loads whole 16-byte
-// pieces of these rows without a clamp or a mask) and the query-side bias terms; one wave per query
+// pieces of these rows without a clamp or a mask) and the query-side bias terms; one wave per query.  CX: the ComplEx form -- the fp32
+// element from the widened row and the fp32 relation (complex_query), split the same way.  head: the direction.
+template <bool CX>
 __global__ __launch_bounds__(WG) void rank_query_bf16_kernel(
     const long long *__restrict__ batch, int Q, int head, const uint16_t *__restrict__ nodes,
     const float *__restrict__ rel, const float *__restrict__ sbias, const float *__restrict__ pbias,
@@ -236,24 +279,34 @@ __global__ __launch_bounds__(WG) void rank_query_bf16_kernel(
   const long long s = batch[3 * q], p = batch[3 * q + 1], o = batch[3 * q + 2];
   const long long fixed = head ? o : s;
   const size_t term = (size_t)Q * dpad;
-  for (int k = lane; k < dpad; k += 64) {
-    uint16_t hi = 0, mid = 0, lo = 0;
-    if (k < d) {
-      // the fp32 product as the fp32 evaluator forms it, then exact remainders: contraction is off in this function, a fused
-      // fma(x, r, -hi) would split the unrounded product instead (closer to x r, but not what the fp32 kernel multiplies)
-      const float v = bf16_widen(nodes[(size_t)fixed * d + k]) * rel[(size_t)p * d + k];
-      hi = bf16_round(v);
-      if (v - v == 0.f) {                                    // finite (an inf / NaN element is its own hi: mid = lo = 0)
-        if ((hi & 0x7FFFu) == 0x7F80u) hi = (hi & 0x8000u) | 0x7F7Fu;     // |v| above the largest bf16 rounds to inf: take the largest bf16, the
-        const float r1 = v - bf16_widen(hi);                              // remainder (same binade: exact) goes to mid and lo
-        mid = bf16_round(r1);
-        lo = bf16_round(r1 - bf16_widen(mid));
-      }
-    }
+  auto put = [&](int k, uint16_t hi, uint16_t mid, uint16_t lo) {
     uint16_t *dst = qs + (size_t)q * dpad + k;
     dst[0] = hi;
     dst[term] = mid;
     dst[2 * term] = lo;
+  };
+  if constexpr (CX) {
+    const int h = d >> 1;
+    const uint16_t *a = nodes + (size_t)fixed * d;
+    const float *r = rel + (size_t)p * d;
+    for (int k = lane; k < h; k += 64) {
+      float re, im;
+      uint16_t hi, mid, lo;
+      complex_query(head, bf16_widen(a[k]), bf16_widen(a[k + h]), r[k], r[k + h], re, im);
+      query_terms(re, hi, mid, lo);
+      put(k, hi, mid, lo);
+      query_terms(im, hi, mid, lo);
+      put(k + h, hi, mid, lo);
+    }
+    for (int k = d + lane; k < dpad; k += 64) put(k, 0, 0, 0);
+  } else {
+    for (int k = lane; k < dpad; k += 64) {
+      uint16_t hi = 0, mid = 0, lo = 0;
+      // the fp32 product as the fp32 evaluator forms it, then exact remainders: contraction is off in this function, a fused
+      // fma(x, r, -hi) would split the unrounded product instead (closer to x r, but not what the fp32 kernel multiplies)
+      if (k < d) query_terms(bf16_widen(nodes[(size_t)fixed * d + k]) * rel[(size_t)p * d + k], hi, mid, lo);
+      put(k, hi, mid, lo);
+    }
   }
   if (lane == 0 && pbias) {
     qb[2 * q] = pbias[p];
@@ -1172,6 +1225,20 @@ template <class Tile>
 constexpr bool is_bf16 = std::is_same<Tile, TileBf16>::value;
 
 inline int64_t k_pad32(int32_t d) { return ((int64_t)d + 31) / 32 * 32; }
+
+// The `head` argument of an entry point: one of the four query form codes, and an even width for the ComplEx forms (d = 0 where the
+// entry builds no query vectors and ignores the form).  Sets the message and returns true on a bad one.
+inline bool bad_query_form(const char *name, int32_t head, int32_t d) {
+  if (head < 0 || head > (RGCN_QUERY_HEAD | RGCN_QUERY_COMPLEX)) {
+    rgcn_set_error("%s: head = %d is no query form code (RGCN_QUERY_TAIL / RGCN_QUERY_HEAD, | RGCN_QUERY_COMPLEX)", name, (int)head);
+    return true;
+  }
+  if ((head & RGCN_QUERY_COMPLEX) && (d & 1)) {
+    rgcn_set_error("%s: the ComplEx query forms need an even width (real halves | imaginary halves), got d = %d", name, (int)d);
+    return true;
+  }
+  return false;
+}
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <class Tile>
@@ -1189,15 +1256,22 @@ auto with_vec(const typename Tile::elem *nodes, int32_t d, F f) {
   return vec ? f(std::true_type{}) : f(std::false_type{});
 }
 
-// the query kernel of the storage: q = fp32 query vectors [Q][d], or their three bf16 terms [3][Q][k_pad32(d)]
+// the query kernel of the storage and of the form (head: the query form code; the kernels get the direction): q = fp32 query vectors
+// [Q][d], or their three bf16 terms [3][Q][k_pad32(d)]
 template <class Tile>
 void launch_query(hipStream_t st, const long long *b, int64_t Q, int32_t head, const typename Tile::elem *nodes, const float *rel,
                   const float *sbias, const float *pbias, const float *obias, typename Tile::elem *q, float *qb, int32_t d) {
   const dim3 grid((unsigned)((Q + 3) / 4));
-  if constexpr (is_bf16<Tile>)
-    hipLaunchKernelGGL(rank_query_bf16_kernel, grid, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, q, qb, d, (int)k_pad32(d));
-  else
-    hipLaunchKernelGGL(rank_query_kernel, grid, dim3(WG), 0, st, b, (int)Q, head, nodes, rel, sbias, pbias, obias, q, qb, d);
+  const int dir = query_dir(head);
+  auto go = [&](auto cx) {
+    constexpr bool CX = decltype(cx)::value;
+    if constexpr (is_bf16<Tile>)
+      hipLaunchKernelGGL(rank_query_bf16_kernel<CX>, grid, dim3(WG), 0, st, b, (int)Q, dir, nodes, rel, sbias, pbias, obias, q, qb, d, (int)k_pad32(d));
+    else
+      hipLaunchKernelGGL(rank_query_kernel<CX>, grid, dim3(WG), 0, st, b, (int)Q, dir, nodes, rel, sbias, pbias, obias, q, qb, d);
+  };
+  if (head & RGCN_QUERY_COMPLEX) go(std::true_type{});
+  else go(std::false_type{});
 }
 
 // q: the caller's scratch for launch_query; hint: what the storage adds to the argument message
@@ -1214,16 +1288,18 @@ int score_all(const char *name, const char *hint, const int64_t *batch, int64_t 
     rgcn_set_error("%s: biases must be all set (with the qbias scratch) or all NULL", name);
     return RGCN_EINVAL;
   }
+  if (bad_query_form(name, head, d)) return RGCN_EINVAL;
   if (Q == 0) return RGCN_OK;
+  const int dir = query_dir(head);
   const int qbl = (int)((Q + 127) / 128);
   const int64_t nwg = ((n_nodes + 127) / 128) * qbl;
   if (nwg > INT32_MAX) { rgcn_set_error("%s: too many scores in one call; split the batch", name); return RGCN_EUNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   launch_query<Tile>(st, reinterpret_cast<const long long *>(batch), Q, head, nodes, rel, sbias, pbias, obias, q, qbias, d);
-  const float *qb1 = sbias ? qbias : nullptr, *cb1 = sbias ? (head ? sbias : obias) : nullptr;
+  const float *qb1 = sbias ? qbias : nullptr, *cb1 = sbias ? (dir ? sbias : obias) : nullptr;
   with_vec<Tile>(nodes, d, [&](auto vec) {
     hipLaunchKernelGGL((score_all_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, st, (const typename Tile::elem *)q,
-                       nodes, tile_dims<Tile>(Q, d), qb1, cb1, scores, (int)Q, (long long)n_nodes, head, qbl);
+                       nodes, tile_dims<Tile>(Q, d), qb1, cb1, scores, (int)Q, (long long)n_nodes, dir, qbl);
   });
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -1271,9 +1347,10 @@ extern "C" int rgcn_rank_count_f32(const float *scores, const int64_t *batch, in
     rgcn_set_error("rank_count: bad argument");
     return RGCN_EINVAL;
   }
+  if (bad_query_form("rank_count", head, 0)) return RGCN_EINVAL;
   if (Q == 0) return RGCN_OK;
   hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)Q), dim3(WG), 0, (hipStream_t)stream, scores,
-                     reinterpret_cast<const long long *>(batch), head, (long long)n_nodes,
+                     reinterpret_cast<const long long *>(batch), query_dir(head), (long long)n_nodes,
                      reinterpret_cast<long long *>(greater), reinterpret_cast<long long *>(ties));
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -1318,7 +1395,7 @@ struct StripArgs {
   const char *name;
   const int64_t *batch;
   int64_t Q;
-  int32_t head;
+  int32_t head;                   // the query form code; the kernels past launch_query take dir()
   const E *nodes;
   const float *rel, *sbias, *pbias, *obias;
   const int32_t *filt_q, *filt_n;
@@ -1329,6 +1406,7 @@ struct StripArgs {
   int32_t d;
   void *stream;
   FilterIndexDev ix;              // the index forms: K > 0 fills the mask from the index (filt_q / filt_n NULL, F = 0)
+  int32_t dir() const { return query_dir(head); }
 };
 
 inline FilterIndexDev filter_index(const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals, int64_t K) {
@@ -1359,6 +1437,7 @@ int strip_check(const StripArgs<E> &a, bool bad_own, const char *hint) {
     rgcn_set_error("%s: biases must be all set or all NULL", a.name);
     return RGCN_EINVAL;
   }
+  if (bad_query_form(a.name, a.head, a.d)) return RGCN_EINVAL;
   return RGCN_OK;
 }
 
@@ -1396,21 +1475,21 @@ int query_begin(const StripArgs<typename Tile::elem> &a, int64_t bytes_per_cell,
   c.q = q;
   c.dm = tile_dims<Tile>(a.Q, a.d);
   c.qb = a.sbias ? qb : nullptr;
-  c.cbias = a.sbias ? (a.head ? a.sbias : a.obias) : nullptr;
+  c.cbias = a.sbias ? (a.dir() ? a.sbias : a.obias) : nullptr;
   c.part = ws + L.part;
   c.mask = mask;
   if (mask) HIP_TRY(zero_async(mask, (size_t)(a.Q * L.mask_w) * sizeof(unsigned), c.st));
   const dim3 list_grid((unsigned)std::min<int64_t>((a.F + WG - 1) / WG, 1 << 16));
   if (a.F && chunk)
-    hipLaunchKernelGGL(chunk_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
+    hipLaunchKernelGGL(chunk_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.dir(),
                        keep_target, (long long)c_first, (long long)(c_first + c_count));
   else if (a.F)
-    hipLaunchKernelGGL(rank_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.head,
+    hipLaunchKernelGGL(rank_mask_kernel, list_grid, dim3(WG), 0, c.st, mask, (long long)L.mask_w, a.filt_q, a.filt_n, (long long)a.F, c.b, a.dir(),
                        keep_target);
-  if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.head, a.n_nodes, keep_target, c_first, c_first + c_count);
+  if (a.ix.K) launch_index_mask(c.st, mask, L.mask_w, a.ix, c.b, a.Q, a.dir(), a.n_nodes, keep_target, c_first, c_first + c_count);
   if (labels)
     hipLaunchKernelGGL(label_target_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, mask, (long long)L.mask_w, c.b, (int)a.Q,
-                       a.head, (long long)c_first, (long long)(c_first + c_count));
+                       a.dir(), (long long)c_first, (long long)(c_first + c_count));
   launch_query<Tile>(c.st, c.b, a.Q, a.head, a.nodes, a.rel, a.sbias, a.pbias, a.obias, q, qb, a.d);
   return RGCN_OK;
 }
@@ -1445,9 +1524,9 @@ int rank_fused(const StripArgs<typename Tile::elem> &a, int64_t *greater, int64_
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     constexpr bool V = decltype(vec)::value;
     hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
-                       a.head);
+                       a.dir());
     hipLaunchKernelGGL((strip_count_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
-                       (const float *)tscore, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+                       (const float *)tscore, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
   });
   hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const uint2 *)part, (int)(2 * c.n_strips), Q,
                      reinterpret_cast<long long *>(greater), reinterpret_cast<long long *>(ties));
@@ -1530,7 +1609,7 @@ int topk_fused(const StripArgs<typename Tile::elem> &a, int32_t k, int64_t *ids,
     hipError_t e = allow_lds<kern>(c.dev, slabs + lds, (int)(TOPK_LDS_CU - slabs));
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), lds, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.mask, (long long)c.mask_w, part,
-                       (int)a.Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips, (int)k);
+                       (int)a.Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips, (int)k);
     return hipSuccess;
   }));
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((a.Q + 3) / 4)), dim3(WG), 0, c.st, (const unsigned long long *)part,
@@ -1601,9 +1680,9 @@ int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore
     with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
       constexpr bool V = decltype(vec)::value;
       hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
-                         a.head);
+                         a.dir());
       hipLaunchKernelGGL((strip_lse_smooth_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb,
-                         c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+                         c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
     });
     hipLaunchKernelGGL(lse_smooth_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float4 *)part,
                        (int)(2 * c.n_strips), Q, lse, ssum, (int *)cnt);
@@ -1614,9 +1693,9 @@ int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     constexpr bool V = decltype(vec)::value;
     hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
-                       a.head);
+                       a.dir());
     hipLaunchKernelGGL((strip_lse_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
-                       c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+                       c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
   });
   hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float2 *)part, (int)(2 * c.n_strips), Q, lse);
   HIP_TRY(hipGetLastError());
@@ -1739,7 +1818,7 @@ int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, cons
   auto launch = [&](auto vec, auto sm) {
     hipLaunchKernelGGL((softmax_grad_kernel<Tile, decltype(vec)::value, decltype(sm)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes,
                        c.dm, c.qb, c.cbias, c.b, lse, gscale, (int)per_query, inv_q, keep, uni, c.mask, (long long)c.mask_w, dS, (int)a.Q,
-                       (long long)a.n_nodes, (long long)c_first, (long long)c_count, a.head, (int)c.qbl);
+                       (long long)a.n_nodes, (long long)c_first, (long long)c_count, a.dir(), (int)c.qbl);
   };
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     if (smooth) launch(vec, std::true_type{}); else launch(vec, std::false_type{});
@@ -1852,7 +1931,7 @@ int bce_sums(const StripArgs<typename Tile::elem> &a, float *sp, float *ps, int3
   const int Q = (int)a.Q;
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     hipLaunchKernelGGL((strip_bce_kernel<Tile, decltype(vec)::value>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm,
-                       c.qb, c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.head, (int)c.qbl, (int)c.n_strips);
+                       c.qb, c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
   });
   hipLaunchKernelGGL(bce_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float4 *)part, (int)(2 * c.n_strips), Q,
                      sp, ps, (int *)npos);
@@ -1876,7 +1955,7 @@ int bce_grad(const StripArgs<typename Tile::elem> &a, const float *gscale, int32
   with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
     hipLaunchKernelGGL((bce_grad_kernel<Tile, decltype(vec)::value>), dim3((unsigned)nwg), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
                        gscale, (int)per_query, inv, keep, uni, c.mask, (long long)c.mask_w, dS, (int)a.Q, (long long)a.n_nodes,
-                       (long long)c_first, (long long)c_count, a.head, (int)c.qbl);
+                       (long long)c_first, (long long)c_count, a.dir(), (int)c.qbl);
   });
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -1944,11 +2023,12 @@ extern "C" int rgcn_filter_mask_index(const int64_t *batch, int64_t Q, int32_t h
     rgcn_set_error("filter_mask_index: bad argument (K > 0 needs keys, ptr and vals; the columns inside [0, n_nodes))");
     return RGCN_EINVAL;
   }
+  if (bad_query_form("filter_mask_index", head, 0)) return RGCN_EINVAL;
   if (Q == 0) return RGCN_OK;
   const int64_t mask_w = (c_count + 31) / 32;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(zero_async(mask, (size_t)(Q * mask_w) * sizeof(unsigned), st));
-  if (K) launch_index_mask(st, mask, mask_w, ix, reinterpret_cast<const long long *>(batch), Q, head, n_nodes, keep_target, c_first, c_first + c_count);
+  if (K) launch_index_mask(st, mask, mask_w, ix, reinterpret_cast<const long long *>(batch), Q, query_dir(head), n_nodes, keep_target, c_first, c_first + c_count);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1960,9 +2040,10 @@ extern "C" int rgcn_rank_filter_index_f32(float *scores, const int64_t *batch, i
     rgcn_set_error("rank_filter_index: bad argument");
     return RGCN_EINVAL;
   }
+  if (bad_query_form("rank_filter_index", head, 0)) return RGCN_EINVAL;
   if (K == 0 || Q == 0) return RGCN_OK;
   hipLaunchKernelGGL(index_filter_kernel, dim3((unsigned)((Q + WG / 64 - 1) / (WG / 64))), dim3(WG), 0, (hipStream_t)stream, scores, ix,
-                     reinterpret_cast<const long long *>(batch), (int)Q, head, (long long)n_nodes, keep_target);
+                     reinterpret_cast<const long long *>(batch), (int)Q, query_dir(head), (long long)n_nodes, keep_target);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

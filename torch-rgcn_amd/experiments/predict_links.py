@@ -17,6 +17,9 @@ training.objective "1-n-bce" (configs/rgcn/lp-WN18-1n-bce.yaml): the K-vs-All bi
 entities, tails and heads, every known completion of a query among the TRAINING triples a positive label and everything else a negative;
 the labels come from a device-resident FilterIndex, built once and always on (that is what K-vs-All means), so training.filtered with it
 raises ValueError; training.bf16 and training.label_smoothing (here eps / N over all entities) combine with it, the step is captured
+decoder.model (the reference's schema carries the key and never reads it): "complex" builds the ComplEx decoder (an extension;
+configs/rgcn/lp-WN18-complex.yaml, lp-WN18-1n-complex.yaml) -- an even node_embedding read as real halves | imaginary halves -- for every
+objective above, evaluation and prediction included; any other value, or none, is DistMult
 encoder.{model,...,edge_dropout.general}  decoder.l2_penalty  evaluation.{final_run,filtered,check_every,batch_size,verbose}.
 Differences: the positives are sampled by the native edge-neighbourhood sampler (milliseconds instead of minutes per
 epoch), negatives are drawn on the GPU, and evaluation encodes the training graph once (utils/misc.py)."""

@@ -2300,10 +2300,26 @@ def _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q=None, filt
     return batch.shape[0], nodes.shape[0], nodes.shape[1], (0 if filt_q is None else filt_q.shape[0])
 
 
-def _query_prefix(batch, head, nodes, rel, sbias, pbias, obias):
+DECODERS = ("distmult", "complex")
+QUERY_COMPLEX = 2                  # RGCN_QUERY_COMPLEX of rgcn_hip.h: the form bit of the `head` argument
+
+
+def check_decoder(decoder, width):
+    """the argument rule of every `decoder=` keyword, checked without a device: one of DECODERS, and ComplEx rows (real halves | imaginary
+    halves) of an even width -- else ValueError"""
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+    if decoder == "complex" and width % 2:
+        raise ValueError(f"the ComplEx decoder needs an even embedding width (real halves | imaginary halves), got {width}")
+
+
+def _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder="distmult"):
     """what the argument lists of those entry points share, bound once per call: the pointers of batch, nodes, rel and the three biases,
-    head as 0 / 1, the relation count and the stream -> (batch, head, nodes, rel, sbias, pbias, obias, n_rel, stream)"""
-    return _dp(batch), 1 if head else 0, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), rel.shape[0], _stream(nodes.device)
+    head as the query form code of rgcn_hip.h (0 / 1, | QUERY_COMPLEX for decoder="complex"), the relation count and the stream
+    -> (batch, head, nodes, rel, sbias, pbias, obias, n_rel, stream)"""
+    check_decoder(decoder, nodes.shape[1])
+    form = (1 if head else 0) | (QUERY_COMPLEX if decoder == "complex" else 0)
+    return _dp(batch), form, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), rel.shape[0], _stream(nodes.device)
 
 
 def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
@@ -2325,7 +2341,7 @@ def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
     return (scores, [counts, rk, False]) if ranks else scores
 
 
-def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None):
+def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
     """scores [Q, N] of every entity as head (head=True) or tail of each triple of `batch` (int64 [Q,3], device);
     utils/misc.py:71-88 without the [bn, N, 3] candidate tensor."""
     Q, N, d, _ = _req_queries(batch, nodes, rel, sbias, pbias, obias, False)
@@ -2334,7 +2350,7 @@ def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=No
     assert scores.shape == (Q, N) and scores.is_contiguous() and scores.dtype == torch.float32
     qvec = torch.empty(Q, d, device=nodes.device, dtype=torch.float32)
     qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     with _on(nodes.device), _timed("score_all"):
         _check(lib().rgcn_distmult_score_all_f32(b, Q, h, nd, rl, sb, pb, ob, _dp(qvec), _dp(qb), _dp(scores), N, R, d, st), "distmult_score_all")
     return scores
@@ -2501,7 +2517,74 @@ def distmult_bwd_rel_bf16(triples, nodes, rel, gs, with_bias):
     return dr, dsb, dpb, dob
 
 
-def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None):
+# ----------------------------------------------------------------------------- ComplEx on scored triples
+# nodes [N, d] and rel [R, d] hold d / 2 complex features per row, real halves | imaginary halves; nodes fp32 or bf16 (the wrapper picks the
+# entry by the table's dtype), everything else as in the DistMult wrappers of the same role.  The split route only: entity gradients from
+# the two CSRs, relation and bias gradients from predicate-sorted triples.
+
+
+def complex_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
+    """ComplEx scores [T] (fp32) of `triples`; ranks=True: (scores, [row sizes, ranks]) as distmult_fwd -- distmult_csrs finishes the CSRs"""
+    bf16 = nodes.dtype == torch.bfloat16
+    _req_params(nodes, rel, sbias, pbias, obias, bf16=bf16); _req(triples, "triples", torch.int64)
+    check_decoder("complex", nodes.shape[1])
+    T, N, R, d, dev = triples.shape[0], nodes.shape[0], rel.shape[0], nodes.shape[1], nodes.device
+    scores = torch.empty(T, device=dev, dtype=torch.float32)
+    err = _i32(1, dev)
+    counts = rk = None
+    if ranks and T:
+        counts, rk = _i32(2 * N + 3, dev), _i32(2 * T, dev)
+    tr, nd, rl, sb, pb, ob, sc, st = _dp(triples), _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), _dp(scores), _stream(dev)
+    with _on(dev), _timed("complex_fwd_bf16" if bf16 else "complex_fwd"):
+        if bf16:
+            _check(lib().rgcn_complex_fwd_bf16(tr, T, nd, rl, sb, pb, ob, sc, N, R, d, _dp(err), _dp(counts), _dp(rk), st), "complex_fwd_bf16")
+        else:
+            _check(lib().rgcn_complex_fwd_f32(tr, T, nd, rl, sb, pb, ob, sc, N, R, d, _dp(err), _dp(counts), _dp(rk), st), "complex_fwd")
+    dev_check_err(err, "ComplEx triples (s, o < num_nodes, p < num_relations)", IndexError)
+    return (scores, [counts, rk, False]) if ranks else scores
+
+
+def complex_bwd_nodes(triples, ranks, nodes, rel, gs):
+    """entity gradients of ComplEx (the table's dtype; bf16: an fp32 sum per entity rounded once) from the two CSRs of the scored triples,
+    one wave per entity, no atomics, every row written"""
+    bf16 = nodes.dtype == torch.bfloat16
+    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16 if bf16 else torch.float32); _req(rel, "relations")
+    N, d = nodes.shape
+    dev = nodes.device
+    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
+    dn = torch.empty_like(nodes)
+    with _on(dev), _timed("complex_bwd_nodes_bf16" if bf16 else "complex_bwd_nodes"):
+        if bf16:
+            _check(lib().rgcn_complex_bwd_nodes_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d, _stream(dev)),
+                   "complex_bwd_nodes_bf16")
+        else:
+            _check(lib().rgcn_complex_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d, _stream(dev)),
+                   "complex_bwd_nodes")
+    return dn
+
+
+def complex_bwd_rel(triples, nodes, rel, gs, with_bias):
+    """(drel, dsbias, dpbias, dobias), fp32, of ComplEx from predicate-sorted triples; the bias gradients None unless with_bias"""
+    bf16 = nodes.dtype == torch.bfloat16
+    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16 if bf16 else torch.float32); _req(rel, "relations")
+    _req(triples, "triples", torch.int64)
+    T, N, R, d, dev = triples.shape[0], nodes.shape[0], rel.shape[0], nodes.shape[1], nodes.device
+    dr = torch.empty_like(rel)
+    dsb = dpb = dob = None
+    if with_bias:
+        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
+        dpb = torch.empty(R, device=dev, dtype=torch.float32)
+    with _on(dev), _timed("complex_bwd_rel_bf16" if bf16 else "complex_bwd_rel"):
+        if bf16:
+            _check(lib().rgcn_complex_bwd_rel_bf16(_dp(triples), T, _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), N, R, d,
+                                                   _stream(dev)), "complex_bwd_rel_bf16")
+        else:
+            _check(lib().rgcn_complex_bwd_rel_f32(_dp(triples), T, _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), N, R, d,
+                                                  _stream(dev)), "complex_bwd_rel")
+    return dr, dsb, dpb, dob
+
+
+def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
     """distmult_score_all for bf16 nodes [N, d] (rel and biases fp32): fp32 scores [Q, N] on the bf16 matrix instructions, the fp32
     query vectors carried as three bf16 terms -- the sums of the fp32 evaluator on the widened table, in another order.  The C entry does not
     range-check the triples on the device (neither does the fp32 one): this wrapper does, and raises IndexError; whoever calls
@@ -2512,7 +2595,7 @@ def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obi
     assert scores.shape == (Q, N) and scores.is_contiguous() and scores.dtype == torch.float32
     qsplit = torch.empty(max(int(lib().rgcn_distmult_score_all_bf16_workspace_bytes(Q, d)), 16), device=nodes.device, dtype=torch.uint8)
     qb = torch.empty(2 * Q, device=nodes.device, dtype=torch.float32) if sbias is not None else None
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     with _on(nodes.device), _timed("distmult_score_all_bf16"):
         _check(lib().rgcn_distmult_score_all_bf16(b, Q, h, nd, rl, sb, pb, ob, _dp(qsplit), _dp(qb), _dp(scores), N, R, d, st),
                "distmult_score_all_bf16")
@@ -2573,7 +2656,8 @@ def rank_fused_workspace_bytes(Q, N, d, strips=0, bf16=False):
     return int(lib().rgcn_distmult_rank_fused_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
 
 
-def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None):
+def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None,
+                        decoder="distmult"):
     """(greater, ties, tscore) of every query of `batch` (int64 [Q, 3], device) without the [Q, N] score matrix: what rank_count returns
     after distmult_score_all[_bf16] and rank_filter on (filt_q, filt_n) (int32 device lists, None = raw ranks), plus the target's own
     score -- utils/misc.py:40-58, 71-99.  fp32 or bf16 nodes (rel and biases fp32).  strips: candidate strips per block of 128 queries
@@ -2588,7 +2672,7 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     ties = torch.empty(Q, device=dev, dtype=torch.int64)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("rank_fused_index_bf16" if bf16 else "rank_fused_index"):
@@ -2626,17 +2710,17 @@ def distmult_topk(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k
     device lists (filt_q, filt_n) is excluded; rows with fewer than k candidates end in id -1, score -inf.  fp32 or bf16 nodes (rel and
     biases fp32).  1 <= k <= TOPK_MAX (the library refuses a larger k).  strips: as in distmult_rank_fused.  NaN scores are outside the
     contract."""
-    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, None)
+    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, None, "distmult")
 
 
-def distmult_topk_index(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0):
+def distmult_topk_index(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0, decoder="distmult"):
     """distmult_topk with a functional.FilterIndex in place of the lists: every known completion of a query is excluded, the same rows
     (its own profile tags: topk_fused_index[_bf16])"""
     assert filt is not None, "distmult_topk_index needs a FilterIndex"
-    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, None, None, strips, filt)
+    return _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, None, None, strips, filt, decoder)
 
 
-def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
+def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt_n, strips, filt, decoder):
     """distmult_topk and distmult_topk_index: the filter as lists, as an index, or none"""
     bf16 = nodes.dtype == torch.bfloat16
     Q, N, d, F = _req_queries(batch, nodes, rel, sbias, pbias, obias, bf16, filt_q, filt_n, strips)
@@ -2647,7 +2731,7 @@ def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt
     ids = torch.empty(Q, k, device=dev, dtype=torch.int64)
     scores = torch.empty(Q, k, device=dev, dtype=torch.float32)
     ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("topk_fused_index_bf16" if bf16 else "topk_fused_index"):
@@ -2698,7 +2782,8 @@ def lse_workspace_bytes(Q, N, d, strips=0, bf16=False):
     return int(lib().rgcn_distmult_lse_workspace_bytes(Q, N, d, strips, 1 if bf16 else 0))
 
 
-def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False, filt=None):
+def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False, filt=None,
+                 decoder="distmult"):
     """(lse, tscore) fp32 [Q]: lse[q] = log sum exp of the cells of distmult_score_all[_bf16] over every entity that is not on the int32
     device lists (filt_q, filt_n) -- an entry on a query's own target is ignored, as in distmult_rank_fused --, tscore[q] = the target's
     cell, without the [Q, N] score matrix.  The 1-N softmax loss of a query is lse - tscore.  fp32 or bf16 nodes (rel and biases fp32).
@@ -2712,7 +2797,7 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     lse = torch.empty(Q, device=dev, dtype=torch.float32)
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("lse_fused_index_bf16" if bf16 else "lse_fused_index"):
@@ -2741,7 +2826,7 @@ def lse_smooth_workspace_bytes(Q, N, d, strips=0, bf16=False):
 
 
 def distmult_lse_smooth(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, checked=False,
-                        filt=None):
+                        filt=None, decoder="distmult"):
     """(lse, tscore, ssum, cnt): distmult_lse's lse and tscore, bit for bit, and beside them per query ssum fp32 [Q] = the sum of the
     allowed scores and cnt int32 [Q] = how many are allowed -- what label smoothing over the allowed candidates needs:
     loss = lse - (1 - eps) tscore - (eps / cnt) ssum.  Arguments as distmult_lse.  Profile tags lse_smooth[_index][_bf16]."""
@@ -2755,7 +2840,7 @@ def distmult_lse_smooth(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     ssum = torch.empty(Q, device=dev, dtype=torch.float32)
     cnt = torch.empty(Q, device=dev, dtype=torch.int32)
     ws = torch.empty(max(lse_smooth_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         with _on(dev), _timed("lse_smooth_index_bf16" if bf16 else "lse_smooth_index"):
@@ -2786,7 +2871,7 @@ def softmax_grad_workspace_bytes(Q, c_count, d, bf16=False):
 
 
 def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None,
-                          filt=None, keep=None, uni=None):
+                          filt=None, keep=None, uni=None, decoder="distmult"):
     """dS fp32 [Q, c_count]: the gradient cells of the 1-N softmax loss on the candidate columns [c_first, c_first + c_count),
     scale_q (exp(s[q, c] - lse[q]) - [c == target_q]), filtered cells 0; scale_q = gscale / mean_over with gscale a device float [1] or
     [Q] (never read back).  fp32 or bf16 nodes (rel and biases fp32; dS is fp32 either way).  lse: distmult_lse's of the same arguments.
@@ -2813,7 +2898,7 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     dS = out.view(-1)[:Q * c_count].view(Q, c_count)
     ws = torch.empty(max(softmax_grad_workspace_bytes(Q, c_count, d, bf16), 16), device=dev, dtype=torch.uint8)
     per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     if filt is not None:
         fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
         if smooth:
@@ -2881,7 +2966,7 @@ def _label_args(lab_q, lab_n, F, labels, head, N, dev):
 
 
 def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, strips=0, checked=False,
-                      labels=None):
+                      labels=None, decoder="distmult"):
     """(sp, ps, npos): per query of `batch` (int64 [Q, 3], device) sp fp32 [Q] = sum_n softplus(s[q, n]) over EVERY entity, ps fp32 [Q] =
     the sum of s over the positive cells and npos int32 [Q] = their number, s the cells of distmult_score_all[_bf16], without the [Q, N]
     matrix.  A cell is positive if it is the query's own target, or on the int32 device lists (lab_q, lab_n), or a completion of the
@@ -2896,7 +2981,7 @@ def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=Non
     ps = torch.empty(Q, device=dev, dtype=torch.float32)
     npos = torch.empty(Q, device=dev, dtype=torch.int32)
     ws = torch.empty(max(bce_sums_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
     with _on(dev), _timed("bce_sums_bf16" if bf16 else "bce_sums"):
         if bf16:
@@ -2909,7 +2994,7 @@ def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=Non
 
 
 def distmult_bce_grad(batch, head, nodes, rel, sbias, pbias, obias, lab_q, lab_n, gscale, mean_over, c_first, c_count, out=None, labels=None,
-                      label_smoothing=0.0):
+                      label_smoothing=0.0, decoder="distmult"):
     """dS fp32 [Q, c_count]: the gradient cells of the 1-N BCE loss on the candidate columns [c_first, c_first + c_count),
     scale_q (sigmoid(s[q, c]) - (1 - eps) y[q, c] - eps / N) with eps = label_smoothing and y the labels of distmult_bce_sums; EVERY
     cell is written.  scale_q = gscale / (N * mean_over) with gscale a device float [1] or [Q] (never read back).  fp32 or bf16 nodes
@@ -2930,7 +3015,7 @@ def distmult_bce_grad(batch, head, nodes, rel, sbias, pbias, obias, lab_q, lab_n
     per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
     # {keep, uni} as host floats: the library reads them before the launch and hands them to the kernel as arguments
     smooth = (ctypes.c_float * 2)(1.0 - label_smoothing, label_smoothing / N) if label_smoothing else None
-    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias)
+    b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
     sm = None if smooth is None else ctypes.addressof(smooth)
     with _on(dev), _timed("bce_grad_bf16" if bf16 else "bce_grad"):

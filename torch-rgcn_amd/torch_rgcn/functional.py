@@ -1226,6 +1226,79 @@ class _DistMultScoreBF16(torch.autograd.Function):
         return None, dn, dr, dsb, dpb, dob
 
 
+class _ComplExScore(torch.autograd.Function):
+    """ComplEx scores of triples on an fp32 or a bf16 entity table, shaped like _DistMultScore / _DistMultScoreBF16: relations
+    and biases fp32 (complex_score widened bf16 parameters), scores fp32, dnodes in the table's dtype (bf16: an fp32 sum per entity rounded
+    once), the parameter gradients fp32.  ONE route, what DistMult calls "split": the CSR counting pass rides on the scoring kernel, the
+    entity gradients come from the two CSRs without atomics, the relation and bias gradients from the predicate-sorted triples.  There is no
+    LDS-table and no atomic-scatter twin: the route switch distmult_bwd is ignored here, `atomic` included."""
+
+    @staticmethod
+    def forward(ctx, triples, nodes, relations, sbias, pbias, obias):
+        shape = triples.shape[:-1]
+        tr = triples.reshape(-1, 3).contiguous()
+        nodes = dense(nodes)
+        relations = dense(relations)
+        ctx.ranks = None
+        if any(ctx.needs_input_grad[1:]) and tr.shape[0]:
+            scores, ctx.ranks = _native.complex_fwd(tr, nodes, relations, sbias, pbias, obias, ranks=True)
+        else:
+            scores = _native.complex_fwd(tr, nodes, relations, sbias, pbias, obias)
+        ctx.save_for_backward(tr, nodes, relations)
+        ctx.with_bias = sbias is not None
+        return scores.view(shape)
+
+    @staticmethod
+    def backward(ctx, gs):
+        tr, nodes, relations = ctx.saved_tensors
+        gs = dense(gs.reshape(-1).float())
+        order = torch.argsort(tr[:, 1], stable=True)   # predicate runs -> relation gradient accumulates in registers
+        dr, dsb, dpb, dob = _native.complex_bwd_rel(tr[order].contiguous(), nodes, relations, gs[order].contiguous(), ctx.with_bias)
+        if ctx.ranks is None:                          # no triples: nothing was counted
+            return None, torch.zeros_like(nodes), dr, dsb, dpb, dob
+        dn = _native.complex_bwd_nodes(tr, ctx.ranks, nodes, relations, gs)
+        return None, dn, dr, dsb, dpb, dob
+
+
+def _check_decoder(decoder, nodes):
+    """the `decoder=` rule of the public functions, before anything touches a device: "distmult" or "complex" (an even width) -- ValueError"""
+    _native.check_decoder(decoder, nodes.shape[-1])
+
+
+def _complex_mul(x, y, conj_y=False):
+    """x y, or x conj(y), of rows of complex features stored as real halves | imaginary halves; every element two rounded products and
+    one rounded add or subtract, as the query kernels form them"""
+    h = x.shape[-1] // 2
+    x_re, x_im, y_re, y_im = x[..., :h], x[..., h:], y[..., :h], y[..., h:]
+    if conj_y:
+        return torch.cat((x_re * y_re + x_im * y_im, x_im * y_re - x_re * y_im), -1)
+    return torch.cat((x_re * y_re - x_im * y_im, x_re * y_im + x_im * y_re), -1)
+
+
+def _query_vectors(nodes, rel, anchor, p, head, decoder):
+    """qv [Q, d] fp32, the query vectors as the query kernel of the decoder forms them, bit for bit (.float(): bf16 rows): DistMult
+    nodes[anchor] * rel[p]; ComplEx [Re z | Im z] with z = a r for tail queries and z = conj(r) a for head queries"""
+    a, r = nodes[anchor].float(), rel[p]
+    if decoder == "distmult":
+        return a * r
+    if not head:
+        return _complex_mul(a, r)
+    h = a.shape[1] // 2                                # conj(r) a, the terms in the kernel's order
+    a_re, a_im, r_re, r_im = a[:, :h], a[:, h:], r[:, :h], r[:, h:]
+    return torch.cat((r_re * a_re + r_im * a_im, r_re * a_im - r_im * a_re), 1)
+
+
+def _query_vectors_grad(dqv, other, head, decoder, wrt):
+    """the chain rule of _query_vectors: the gradient rows [Q, d] with respect to the anchor rows (wrt="anchor", other = rel[p]) or to the
+    relation rows (wrt="relation", other = nodes[anchor].float()) from g = dqv.  DistMult: g * other.  ComplEx, g read as a complex
+    number: tail da = g conj(r), dr = g conj(a); head da = r g, dr = a conj(g)."""
+    if decoder == "distmult":
+        return dqv * other
+    if not head:
+        return _complex_mul(dqv, other, conj_y=True)
+    return _complex_mul(other, dqv) if wrt == "anchor" else _complex_mul(other, dqv, conj_y=True)
+
+
 def _widen_query_params(nodes, relations, sbias, pbias, obias):
     """-> (relations, sbias, pbias, obias) as the native DistMult calls take them.  fp32 nodes: as they are.  bf16 nodes:
     each fp32 or bf16, else TypeError; bf16 ones widened to fp32, once per call (.float() is a no-op on fp32; they are small)"""
@@ -1244,12 +1317,26 @@ def distmult_score(triples, nodes, relations, sbias=None, pbias=None, obias=None
     return score.apply(triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
 
 
-def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, out=None):
+def complex_score(triples, nodes, relations, sbias=None, pbias=None, obias=None):
+    """ComplEx scores of `triples` [..., 3] (Trouillon et al. 2016; an extension): nodes [N, d] and relations [R, d], d even
+    (else ValueError), hold d / 2 complex features per row, real halves in columns [0, d / 2), imaginary halves behind them, and
+        score(s, p, o) = Re sum_k e_s[k] r_p[k] conj(e_o[k])  (+ sbias[s] + pbias[p] + obias[o], all three or none)
+    -- not symmetric in s and o.  Dtypes as in distmult_score: fp32 nodes, or bf16 nodes with fp32 or bf16 relations and biases (widened
+    here), fp32 scores, dnodes in the table's dtype.  The backward always runs the CSR walk for the entities and the predicate-sorted kernel
+    for relations and biases (DistMult's "split" route); the route switch distmult_bwd has no effect on it."""
+    _check_decoder("complex", nodes)
+    return _ComplExScore.apply(triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
+
+
+def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
     """fp32 scores [Q, N] of every entity as the head (head=True) or the tail of each triple of `batch` (int64 [Q, 3] on the device), no
     autograd: the ranking evaluator's product (utils/misc.py:71-88).  fp32 nodes run the fp32 matrix instructions; bf16 nodes (DESIGN.md
-    4.6) the bf16 ones on the bf16 table, with relations and biases fp32 or bf16 (widened here) -- same sums, another order."""
+    4.6) the bf16 ones on the bf16 table, with relations and biases fp32 or bf16 (widened here) -- same sums, another order.
+    decoder (here and in every all-candidate function below): "distmult", or "complex" for the ComplEx scores of complex_score on the
+    same kernels -- only the query vectors differ; an even width, and any other value is a ValueError."""
+    _check_decoder(decoder, nodes)
     score_all = _native.distmult_score_all_bf16 if nodes.dtype == torch.bfloat16 else _native.distmult_score_all
-    return score_all(batch, head, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias), out=out)
+    return score_all(batch, head, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias), out=out, decoder=decoder)
 
 
 class FilterIndex:
@@ -1314,15 +1401,17 @@ def _filter_args(filt, filt_q, filt_n, nodes, name="filt", lists="filt_q / filt_
         raise ValueError(f"the FilterIndex was built for {filt.num_nodes} entities, the entity table has {nodes.shape[0]}")
 
 
-def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None):
+def distmult_rank_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None, strips=0, filt=None,
+                      decoder="distmult"):
     """(greater, ties, tscore) [Q]: for each triple of `batch` the number of entities that score above its target as the head (head=True)
     or the tail, the number that score the same (the target included) and the target's score -- the counts `_native.rank_count` takes from
     the score matrix of distmult_score_all after `_native.rank_filter` on the int32 device lists (filt_q, filt_n), without that matrix
     (utils/misc.py:40-58, 71-99).  No autograd.  fp32 or bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16
     (widened here), as in distmult_score_all.  filt: a FilterIndex in place of the lists (not both: ValueError) -- the same counts."""
+    _check_decoder(decoder, nodes)
     _filter_args(filt, filt_q, filt_n, nodes)
     relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
-    return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, filt=filt)
+    return _native.distmult_rank_fused(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, filt=filt, decoder=decoder)
 
 
 def distmult_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt_q=None, filt_n=None, strips=0):
@@ -1331,25 +1420,38 @@ def distmult_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obi
     descending and id ascending and cut at k, without that matrix.  The predicted column of `batch` is ignored and every
     listed cell is excluded; rows with fewer than k candidates end in id -1, score -inf.  No autograd.  k <= _native.TOPK_MAX.  fp32 or
     bf16 nodes; with bf16 nodes relations and biases are fp32 or bf16 (widened here), as in distmult_rank_all.  With a FilterIndex in
-    place of the lists: distmult_topk_all_index (this function's parameter list is the one its callers know; it stays)."""
-    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, None)
+    place of the lists: distmult_topk_all_index; over ComplEx scores: complex_topk_all (this function's parameter list is the one its
+    callers know; it stays)."""
+    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, None, "distmult")
 
 
-def distmult_topk_all_index(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0):
+def complex_topk_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt_q=None, filt_n=None, strips=0):
+    """distmult_topk_all over ComplEx scores (complex_score): the same kernels on ComplEx query vectors, the same
+    parameter list (that one is fixed, so the decoder cannot be a keyword of it).  An odd width is a ValueError.  With a FilterIndex:
+    distmult_topk_all_index(..., decoder="complex")."""
+    _check_decoder("complex", nodes)
+    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, None, "complex")
+
+
+def distmult_topk_all_index(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, k=10, filt=None, strips=0, decoder="distmult"):
     """distmult_topk_all with `filt`, a FilterIndex, in place of the lists: every known completion of a query is excluded -- the same
     rows, bit for bit, with no list built on the host.  The index must be on the tensors' device and built for nodes.shape[0] entities
     (ValueError)."""
+    _check_decoder(decoder, nodes)
     if filt is None:
         raise ValueError("distmult_topk_all_index needs a FilterIndex (distmult_topk_all takes lists or no filter)")
     _filter_args(filt, None, None, nodes)
-    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, None, None, strips, filt)
+    return _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, None, None, strips, filt, decoder)
 
 
-def _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, filt):
+def _topk_all(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, filt, decoder):
     relations, sbias, pbias, obias = _widen_query_params(nodes, relations, sbias, pbias, obias)
     if filt is not None:
-        return _native.distmult_topk_index(batch, head, nodes, relations, sbias, pbias, obias, k, filt, strips)
-    return _native.distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips)
+        return _native.distmult_topk_index(batch, head, nodes, relations, sbias, pbias, obias, k, filt, strips, decoder=decoder)
+    if decoder == "distmult":
+        return _native.distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips)
+    # (_native.distmult_topk keeps its parameter list: the list form of another decoder goes to what it wraps)
+    return _native._distmult_topk(batch, head, nodes, relations, sbias, pbias, obias, k, filt_q, filt_n, strips, None, decoder)
 
 
 _UNIT = {}
@@ -1405,22 +1507,25 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
     uni = eps / cnt [Q] are saved as device floats and the backward's cells subtract them -- same chunk plan, same contractions."""
 
     @staticmethod
-    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes, filt=None, smoothing=0.0):
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, mean, strips, chunk_bytes, filt=None, smoothing=0.0,
+                decoder="distmult"):
         batch = batch.reshape(-1, 3).contiguous()
         nodes, relations = dense(nodes), dense(relations)
+        ctx.decoder = decoder
         # range-checked here, once, for the forward and the backward (under deferred checks: clamped, the error queued)
         batch = _native.checked_queries(batch, nodes.shape[0], relations.shape[0], filt_q, filt_n, nodes.dtype == torch.bfloat16)
         # (with a FilterIndex there are no lists: checked_queries takes its unfiltered path -- no read-back under deferred checks)
         ctx.head, ctx.mean, ctx.chunk_bytes, ctx.filt = bool(head), mean, chunk_bytes, filt
         if smoothing:
             lse, tscore, ssum, cnt = _native.distmult_lse_smooth(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips,
-                                                                 checked=True, filt=filt)
+                                                                 checked=True, filt=filt, decoder=decoder)
             keep = torch.full((1,), 1.0 - smoothing, device=lse.device, dtype=torch.float32)
             uni = smoothing / cnt.to(torch.float32)                           # cnt >= 1: the target is always allowed
             ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse, keep, uni)
             loss = lse - keep * tscore - uni * ssum
             return loss.mean() if mean else loss
-        lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True, filt=filt)
+        lse, tscore = _native.distmult_lse(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, strips, checked=True, filt=filt,
+                                           decoder=decoder)
         ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, filt_q, filt_n, lse)
         loss = lse - tscore
         return loss.mean() if mean else loss
@@ -1432,16 +1537,17 @@ class _DistMultSoftmaxLoss(torch.autograd.Function):
 
         def cells(g, c_first, c_count, buf):
             return _native.distmult_softmax_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, g,
-                                                 batch.shape[0] if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt, keep=keep, uni=uni)
+                                                 batch.shape[0] if ctx.mean else 1, c_first, c_count, out=buf, filt=ctx.filt, keep=keep, uni=uni,
+                                                 decoder=ctx.decoder)
         # sum_n dS[q, n] = 0: the query-side bias gradients are zeros
         grads = _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias=False)
-        return (None, None) + grads + (None,) * 7
+        return (None, None) + grads + (None,) * 8
 
 
 def _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias):
     """-> (dnodes, drel, dsbias, dpbias, dobias) of a loss over all candidates of every query of `batch`, from its gradient cells: the
     chunk loop the 1-N softmax loss and the 1-N BCE loss share.  cells(g, c_first, c_count, buf) -> dS fp32 [Q, c_count], the cells of
-    the candidate columns [c_first, c_first + c_count) written into `buf`; ctx: head, chunk_bytes and needs_input_grad (inputs 2..6 are
+    the candidate columns [c_first, c_first + c_count) written into `buf`; ctx: head, decoder, chunk_bytes and needs_input_grad (inputs 2..6 are
     nodes, relations and the three biases).  query_bias: the rows of dS do not sum to zero, so the query-side bias gradients are real --
     dS times a column of ones per chunk, the chunks added in chunk order, then index_add_ into pbias[p] and into obias[anchor] (head) or
     sbias[anchor] (tail); without it they are zeros."""
@@ -1454,7 +1560,7 @@ def _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cell
             g = dense(g.to(torch.float32))
         anchor, p = batch[:, 2 if ctx.head else 0], batch[:, 1]
         bf16 = nodes.dtype == torch.bfloat16
-        qv = nodes[anchor].float() * rel[p]                               # the query vectors, as the query kernel forms them (.float(): bf16 rows)
+        qv = _query_vectors(nodes, rel, anchor, p, ctx.head, ctx.decoder)  # as the query kernel forms them
         plan = softmax_chunk_plan(Q, N, ctx.chunk_bytes)
         # bf16 table: the rows of a chunk widened for the query-side product, one buffer for every chunk (the first chunk is the widest)
         wide = torch.empty(plan[0][1], d, device=dev, dtype=torch.float32) if bf16 and (need_n or need_r) else None
@@ -1484,11 +1590,11 @@ def _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cell
                 part = _native.gemm(dS, rows, split_k=_split_k(c_count, Q, d))
                 dqv = part if dqv is None else dqv.add_(part)
         if need_n:
-            dn.index_add_(0, anchor, dqv * rel[p])
+            dn.index_add_(0, anchor, _query_vectors_grad(dqv, rel[p], ctx.head, ctx.decoder, "anchor"))
             if bf16:
                 dn = dn.to(torch.bfloat16)                                # fp32 sums, one rounding
         if need_r:
-            dr = torch.zeros_like(rel).index_add_(0, p, dqv * nodes[anchor].float())
+            dr = torch.zeros_like(rel).index_add_(0, p, _query_vectors_grad(dqv, nodes[anchor].float(), ctx.head, ctx.decoder, "relation"))
         if need_b:
             cand = cand.view(N)
             zeros = torch.zeros(N, device=dev)
@@ -1532,7 +1638,8 @@ def _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward):
 
 
 def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, filt_q=None, filt_n=None,
-                          reduction="mean", strips=0, chunk_bytes=None, filt=None, bf16_backward="upcast", label_smoothing=0.0):
+                          reduction="mean", strips=0, chunk_bytes=None, filt=None, bf16_backward="upcast", label_smoothing=0.0,
+                          decoder="distmult"):
     """1-N softmax cross-entropy of DistMult (an extension: the reference trains on sampled negatives only).  For each triple of `batch`
     (int64 [Q, 3]) every entity is scored as its head (head=True) or its tail -- the cells s[q, n] of distmult_score_all -- and
         loss[q] = log sum_{n allowed} exp(s[q, n]) - s[q, target_q],
@@ -1563,12 +1670,16 @@ def distmult_softmax_loss(batch, head, nodes, relations, sbias=None, pbias=None,
     the count of the allowed scores beside (max, sum exp) -- lse and the target score keep their bits --, the loss is composed from the
     four [Q] vectors on the device, and the gradient cells become scale_q (exp(s - lse) - (1 - eps) [n == target_q] - eps / n_q): their
     row sums are still 0, so the query-side bias gradients stay zeros.  Nothing is read back; bf16 tables go the routes above.  0 takes
-    the unsmoothed path, call for call."""
+    the unsmoothed path, call for call.
+    decoder="complex": the same loss over ComplEx scores (complex_score) -- the strip pass and the gradient cells are the
+    same kernels on ComplEx query vectors, and the last step of the backward applies their chain rule (tail queries: da = g conj(r),
+    dr = g conj(a); head queries: da = r g, dr = a conj(g), g = dqv read as complex) in place of the two element-wise products."""
+    _check_decoder(decoder, nodes)
     chunk_bytes = _loss_args(label_smoothing, reduction, bf16_backward, chunk_bytes)
     _filter_args(filt, filt_q, filt_n, nodes)
     nodes, relations, sbias, pbias, obias = _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward)
     return _DistMultSoftmaxLoss.apply(batch, head, nodes, relations, sbias, pbias, obias, filt_q, filt_n, reduction == "mean", strips,
-                                      chunk_bytes, filt, float(label_smoothing))
+                                      chunk_bytes, filt, float(label_smoothing), decoder)
 
 
 class _DistMultBCELoss(torch.autograd.Function):
@@ -1579,17 +1690,20 @@ class _DistMultBCELoss(torch.autograd.Function):
     of the lists, kept by reference on ctx as _DistMultSoftmaxLoss keeps its filter."""
 
     @staticmethod
-    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, mean, strips, chunk_bytes, labels=None, smoothing=0.0):
+    def forward(ctx, batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, mean, strips, chunk_bytes, labels=None, smoothing=0.0,
+                decoder="distmult"):
         batch = batch.reshape(-1, 3).contiguous()
         nodes, relations = dense(nodes), dense(relations)
+        ctx.decoder = decoder
         N = nodes.shape[0]
         batch = _native.checked_queries(batch, N, relations.shape[0], lab_q, lab_n, nodes.dtype == torch.bfloat16)
         ctx.head, ctx.mean, ctx.chunk_bytes, ctx.labels, ctx.smoothing = bool(head), mean, chunk_bytes, labels, smoothing
-        sp, ps, _ = _native.distmult_bce_sums(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, strips, checked=True, labels=labels)
+        sp, ps, _ = _native.distmult_bce_sums(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, strips, checked=True, labels=labels,
+                                              decoder=decoder)
         ctx.save_for_backward(batch, nodes, relations, sbias, pbias, obias, lab_q, lab_n)
         if smoothing:
             anchor, p = batch[:, 2 if head else 0], batch[:, 1]
-            rows = (nodes[anchor].float() * relations[p]) @ nodes.sum(0, dtype=torch.float32)     # (the bf16 table is never widened)
+            rows = _query_vectors(nodes, relations, anchor, p, head, decoder) @ nodes.sum(0, dtype=torch.float32)     # (the bf16 table is never widened)
             if sbias is not None:
                 cbias, abias = (sbias, obias) if head else (obias, sbias)
                 rows = rows + (cbias.sum() + N * (pbias[p] + abias[anchor]))
@@ -1604,9 +1718,9 @@ class _DistMultBCELoss(torch.autograd.Function):
 
         def cells(g, c_first, c_count, buf):
             return _native.distmult_bce_grad(batch, ctx.head, nodes, rel, sbias, pbias, obias, lab_q, lab_n, g, batch.shape[0] if ctx.mean else 1,
-                                             c_first, c_count, out=buf, labels=ctx.labels, label_smoothing=ctx.smoothing)
+                                             c_first, c_count, out=buf, labels=ctx.labels, label_smoothing=ctx.smoothing, decoder=ctx.decoder)
         grads = _all_candidate_backward(ctx, g, batch, nodes, rel, sbias, pbias, obias, cells, query_bias=True)
-        return (None, None) + grads + (None,) * 7
+        return (None, None) + grads + (None,) * 8
 
 
 def distmult_bce_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, labels=None,
@@ -1629,12 +1743,29 @@ def distmult_bce_loss(batch, head, nodes, relations, sbias=None, pbias=None, obi
     cells scale_q (sigmoid(s) - (1 - eps) y - eps / N), contracted on the matrix cores in the same order, the same index_add_ last; the
     query-side bias gradients are dS times a column of ones, the chunks added in chunk order.  Nothing is read back: range checks go
     through checked_queries, and under route deferred_checks = 1 the call does not synchronise and can be captured.
-    bf16 nodes, bf16_backward ("upcast" / "native"), strips: as in distmult_softmax_loss.  label_smoothing: a real number in [0, 1)."""
+    bf16 nodes, bf16_backward ("upcast" / "native"), strips: as in distmult_softmax_loss.  label_smoothing: a real number in [0, 1).
+    Over ComplEx scores: complex_bce_loss (this function's parameter list is fixed, so the decoder cannot be a keyword of it)."""
+    return _bce_loss(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, labels, reduction, strips, chunk_bytes, bf16_backward,
+                     label_smoothing, "distmult")
+
+
+def complex_bce_loss(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, labels=None,
+                     reduction="mean", strips=0, chunk_bytes=None, bf16_backward="upcast", label_smoothing=0.0):
+    """distmult_bce_loss over ComplEx scores (complex_score), the same parameter list: the strip pass and the gradient
+    cells are the same kernels on ComplEx query vectors, the smoothed row sum and the last step of the backward go through the query
+    vectors' own form and chain rule, as in distmult_softmax_loss(..., decoder="complex").  An odd width is a ValueError."""
+    _check_decoder("complex", nodes)
+    return _bce_loss(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, labels, reduction, strips, chunk_bytes, bf16_backward,
+                     label_smoothing, "complex")
+
+
+def _bce_loss(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, labels, reduction, strips, chunk_bytes, bf16_backward,
+              label_smoothing, decoder):
     chunk_bytes = _loss_args(label_smoothing, reduction, bf16_backward, chunk_bytes)
     _filter_args(labels, lab_q, lab_n, nodes, name="labels", lists="lab_q / lab_n")
     nodes, relations, sbias, pbias, obias = _loss_params(nodes, relations, sbias, pbias, obias, bf16_backward)
     return _DistMultBCELoss.apply(batch, head, nodes, relations, sbias, pbias, obias, lab_q, lab_n, reduction == "mean", strips, chunk_bytes,
-                                  labels, float(label_smoothing))
+                                  labels, float(label_smoothing), decoder)
 
 
 class _MaskedCE(torch.autograd.Function):

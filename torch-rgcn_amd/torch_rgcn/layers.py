@@ -6,6 +6,7 @@ sparse ops.
     RelationalGraphConvolutionNC   reference torch_rgcn/layers.py:101-308
     RelationalGraphConvolutionLP   reference torch_rgcn/layers.py:311-565
     DistMult                       reference torch_rgcn/layers.py:9-98
+    ComplEx                        an extension: DistMult's interface over complex numbers
 
 What is the same: the function computed, out = sum_r A_r X W_r + b with the
 reference's exact per-edge normalisation (including the link-prediction
@@ -43,6 +44,8 @@ def _require_gpu(t, what):
 
 class DistMult(Module):
     """DistMult decoder: score(s,p,o) = <e_s, r_p, e_o> (+ per-entity / per-relation biases)."""
+
+    decoder = "distmult"           # what the all-candidate functions of functional.py take as `decoder=` (ComplEx overrides it)
 
     def __init__(self, indim, outdim, num_nodes, num_rel, w_init='standard-normal', w_gain=False, b_init=None):
         super().__init__()
@@ -109,7 +112,7 @@ class DistMult(Module):
         # (without b_init the three biases are registered as None: one call serves both)
         return F_.distmult_softmax_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias,
                                         filt_q=filt_q, filt_n=filt_n, reduction=reduction, filt=filt, bf16_backward=bf16_backward,
-                                        label_smoothing=label_smoothing)
+                                        label_smoothing=label_smoothing, decoder=self.decoder)
 
     def bce_loss(self, triples, nodes, head=False, lab_q=None, lab_n=None, labels=None, reduction="mean", bf16_backward="upcast",
                  label_smoothing=0.0):
@@ -120,8 +123,31 @@ class DistMult(Module):
         label_smoothing: eps in [0, 1), y' = (1 - eps) y + eps / N over ALL entities."""
         _require_gpu(nodes, "DistMult node embeddings")
         triples = triples.to(nodes.device)
-        return F_.distmult_bce_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias, lab_q=lab_q, lab_n=lab_n,
-                                    labels=labels, reduction=reduction, bf16_backward=bf16_backward, label_smoothing=label_smoothing)
+        bce_loss = F_.complex_bce_loss if self.decoder == "complex" else F_.distmult_bce_loss
+        return bce_loss(triples, head, nodes, self.relations, self.sbias, self.pbias, self.obias, lab_q=lab_q, lab_n=lab_n,
+                        labels=labels, reduction=reduction, bf16_backward=bf16_backward, label_smoothing=label_smoothing)
+
+
+class ComplEx(DistMult):
+    """ComplEx decoder (Trouillon et al. 2016; an extension, the reference has DistMult only): score(s,p,o) = Re <e_s, r_p, conj(e_o)>
+    (+ the same biases) -- not symmetric in s and o, so it can tell (a, hypernym, b) from (b, hypernym, a).  A row of the embeddings and
+    of `relations`, `outdim` wide, holds outdim / 2 complex features: real halves in the first columns, imaginary halves behind them
+    (an odd outdim: ValueError).  Constructor, parameter names and shapes are DistMult's, so a state dict loads either way; s_penalty is
+    inherited (|e|^2 = re^2 + im^2); softmax_loss and bce_loss run DistMult's all-candidate kernels on ComplEx query vectors."""
+
+    decoder = "complex"
+
+    def __init__(self, indim, outdim, num_nodes, num_rel, w_init='standard-normal', w_gain=False, b_init=None):
+        if outdim % 2:
+            raise ValueError(f"ComplEx needs an even embedding width (real halves | imaginary halves), got outdim = {outdim}")
+        super().__init__(indim, outdim, num_nodes, num_rel, w_init, w_gain, b_init)
+
+    def forward(self, triples, nodes):
+        _require_gpu(nodes, "ComplEx node embeddings")
+        triples = triples.to(nodes.device)
+        if self.b_init:
+            return F_.complex_score(triples, nodes, self.relations, self.sbias, self.pbias, self.obias)
+        return F_.complex_score(triples, nodes, self.relations)
 
 
 class _RGCBase(Module):

@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .layers import DistMult, RelationalGraphConvolutionLP, RelationalGraphConvolutionNC
+from .layers import ComplEx, DistMult, RelationalGraphConvolutionLP, RelationalGraphConvolutionNC
 from .utils import add_inverse_and_self, schlichtkrull_normal_, select_w_init
 
 
@@ -73,7 +73,8 @@ def _init_embedding(tensor, name, gain=1.0):
 
 
 class LinkPredictor(nn.Module):
-    """RGCN encoder (1-2 LP layers over learnt embeddings) + DistMult decoder."""
+    """RGCN encoder (1-2 LP layers over learnt embeddings) + DistMult decoder; decoder_config `model: complex` (any letter case; an
+    extension) builds the ComplEx decoder on the same embeddings instead, read as node_embedding / 2 complex features."""
 
     def __init__(self, nnodes=None, nrel=None, nfeat=None, encoder_config=None, decoder_config=None):
         super().__init__()
@@ -97,8 +98,11 @@ class LinkPredictor(nn.Module):
         self.rgc1 = RelationalGraphConvolutionLP(in_features=self._rgc1_in(nemb, nhid1), out_features=nhid1, **lp)
         if layers == 2:
             self.rgc2 = RelationalGraphConvolutionLP(in_features=nhid1, out_features=nhid2, **lp)
-        self.scoring_function = DistMult(nrel, nemb, nnodes, nrel, self._layer_init(dec.get("weight_init"), "standard-normal"),
-                                         dec.get("include_gain", False), dec.get("bias_init"))
+        complex_decoder = str(dec.get("model", "distmult")).lower() == "complex"      # anything else: DistMult, as before the key was read
+        assert not complex_decoder or nemb % 2 == 0, "The ComplEx decoder needs an even node_embedding (real halves | imaginary halves)!"
+        self.scoring_function = (ComplEx if complex_decoder else DistMult)(
+            nrel, nemb, nnodes, nrel, self._layer_init(dec.get("weight_init"), "standard-normal"), dec.get("include_gain", False),
+            dec.get("bias_init"))
 
     @staticmethod
     def _layer_init(name, default="glorot-normal"):

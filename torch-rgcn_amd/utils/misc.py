@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from torch_rgcn import _native
-from torch_rgcn.functional import (FilterIndex, distmult_rank_all, distmult_score_all, distmult_topk_all,  # noqa: F401  (FilterIndex: re-exported)
-                                   distmult_topk_all_index)
+from torch_rgcn.functional import (FilterIndex, complex_topk_all, distmult_rank_all, distmult_score_all,  # noqa: F401  (FilterIndex: re-exported)
+                                   distmult_topk_all, distmult_topk_all_index)
 from torch_rgcn.layers import DistMult
 
 _SCORE_BYTES = 1 << 30     # score-matrix budget per chunk of queries
@@ -185,11 +185,12 @@ def evaluate(model, graph, test_set, true_triples, num_nodes, batch_size=16, hit
                     r, c = _filter_index(true_triples, num_nodes).lists(test_set[fr:fr + batch_size].numpy(), head)
                     if len(r):
                         rows, cols = torch.from_numpy(r).to(device), torch.from_numpy(c).to(device)
-                raw, ties, _ = distmult_rank_all(batch, head, x, *params, filt_q=rows, filt_n=cols, filt=index)
+                raw, ties, _ = distmult_rank_all(batch, head, x, *params, filt_q=rows, filt_n=cols, filt=index,
+                                                 decoder=decoder.decoder)
                 ranks.extend((raw + (ties - 1) // 2 + 1).tolist())
                 continue
             if fast:        # (bf16 embeddings: the bf16 matrix instructions on the bf16 table, fp32 scores -- DESIGN.md 4.6)
-                scores = distmult_score_all(batch, head, x, *params)
+                scores = distmult_score_all(batch, head, x, *params, decoder=decoder.decoder)
             else:
                 ar = torch.arange(num_nodes, device=device).view(1, num_nodes, 1).expand(bn, num_nodes, 1)
                 bexp = (batch[:, 1:] if head else batch[:, :2]).view(bn, 1, 2).expand(bn, num_nodes, 2)
@@ -247,6 +248,7 @@ def predict(model, graph, queries, num_nodes, k=10, head=False, true_triples=Non
     assert x.shape[0] == num_nodes, "num_nodes differs from the encoder output"
     params = (decoder.relations.detach(), *((decoder.sbias.detach(), decoder.pbias.detach(), decoder.obias.detach())
                                             if decoder.b_init else ()))
+    topk_lists = complex_topk_all if decoder.decoder == "complex" else distmult_topk_all
     fuse = k <= _native.TOPK_MAX and (fused is None or bool(fused))      # (a larger k takes the fallback whatever `fused` says)
     if fuse:
         batch_size = _topk_batch(len(queries), num_nodes, x.shape[1], k)
@@ -266,11 +268,11 @@ def predict(model, graph, queries, num_nodes, k=10, head=False, true_triples=Non
                 rows, cols = torch.from_numpy(r).to(device), torch.from_numpy(c).to(device)
         if fuse:
             if index is not None:
-                i, s = distmult_topk_all_index(batch, head, x, *params, k=k, filt=index)
+                i, s = distmult_topk_all_index(batch, head, x, *params, k=k, filt=index, decoder=decoder.decoder)
             else:
-                i, s = distmult_topk_all(batch, head, x, *params, k=k, filt_q=rows, filt_n=cols)
+                i, s = topk_lists(batch, head, x, *params, k=k, filt_q=rows, filt_n=cols)
         else:
-            sc = distmult_score_all(batch, head, x, *params)
+            sc = distmult_score_all(batch, head, x, *params, decoder=decoder.decoder)
             if index is not None:
                 _native.rank_filter_index(sc, batch, head, index, keep_target=True)
             elif rows is not None:
