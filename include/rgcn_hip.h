@@ -884,6 +884,33 @@ RGCN_API int rgcn_rank_filter_f32(float *scores, int64_t Q, int64_t n_nodes, con
  * batch[q,2].  rank = greater + (ties - 1) / 2 + 1 is left to the caller (misc.py:99-101). */
 RGCN_API int rgcn_rank_count_f32(const float *scores, const int64_t *batch, int64_t Q, int32_t head,
                                  int64_t n_nodes, int64_t *greater, int64_t *ties, void *stream);
+/* Device-resident filter index (DESIGN.md 4.5): the known completions of one direction as a sorted table on the device, in place of
+ * the per-call lists (filt_q, filt_n, F).  fkeys [K] (int64), STRICTLY ASCENDING, key = p * n_nodes + o for head queries (the known
+ * heads of (?, p, o)) and p * n_nodes + s for tail queries; fptr [K + 1] (int64); fvals [fptr[K]] (int32), the completions of key k in
+ * fvals[fptr[k] .. fptr[k + 1]), ASCENDING AND UNIQUE within a key, each in [0, n_nodes).  NOTHING of the index is range-checked on the
+ * device: its builder (functional.FilterIndex) validates it once on the host.  K = 0 with NULL pointers = no index.
+ *
+ * rgcn_filter_mask_index zeroes the caller's mask [Q][ceil(c_count / 32)] (uint32) and sets, for each query q of `batch`, the bit
+ * n - c_first of row q for every completion n of the query's key inside the columns [c_first, c_first + c_count) (inside [0, n_nodes));
+ * keep_target == 0 skips a completion equal to the query's own target (batch[q, 0] for head queries, batch[q, 2] for tail queries).  One
+ * wave per query: the key's binary search, two more over the key's sorted completions for the column range, then integer atomic OR.
+ * These are the bits the lists (filt_q, filt_n) set; the filtered entry points below fill the mask of their workspace the same way.
+ * n_nodes is the entity count the keys were formed with.  No host synchronisation, no memset. */
+RGCN_API int rgcn_filter_mask_index(const int64_t *batch, int64_t Q, int32_t head, const int64_t *fkeys, const int64_t *fptr,
+                                    const int32_t *fvals, int64_t K, int32_t keep_target, int64_t c_first, int64_t c_count, uint32_t *mask,
+                                    int64_t n_nodes, void *stream);
+/* rgcn_rank_filter_f32 from the index: scores[q, n] = -inf for every completion n of query q's key other than the query's own target
+ * (scores row-major [Q, n_nodes]); keep_target != 0 (prediction: the query has no target) writes that cell too, as a list built for
+ * prediction does.  Index contract as above: keys strictly ascending, fvals ascending within a key, nothing checked. */
+RGCN_API int rgcn_rank_filter_index_f32(float *scores, const int64_t *batch, int64_t Q, int32_t head, int64_t n_nodes, const int64_t *fkeys,
+                                        const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t keep_target, void *stream);
+/* The filter block.  Every filtered entry point below -- one per role and storage -- takes, directly behind obias, the seven arguments
+ *   filt_q, filt_n, F,  fkeys, fptr, fvals, K
+ * the filter as per-call lists (filt_q / filt_n [F], int32, device) or as the index above, by the caller's choice.  F > 0 needs both
+ * lists, K > 0 needs keys, ptr and vals; F > 0 and K > 0 together, F < 0 and K < 0 are RGCN_EINVAL; F = 0 and K = 0 (the pointers are
+ * not read) is unfiltered.  Both fill the same mask of the workspace, so with the same excluded cells every result is bit for bit the
+ * same whichever way the filter came; workspace sizes, passes and errors do not depend on it.  Ranking, log-sum-exp and gradient cells
+ * skip an entry on the query's own target; top-k excludes every entry; the BCE roles read the block as labels (see there). */
 /* Fused ranking evaluator (utils/misc.py:40-58, 71-99): greater [Q] and ties [Q] (int64, what rgcn_rank_count_f32 returns after
  * rgcn_distmult_score_all_* and rgcn_rank_filter_f32) straight from the entity table -- no [Q, n_nodes] score buffer exists.  Three
  * passes on `stream`, no host synchronisation, no memset: the query pass of the score-all entries; tscore [Q] (float, always written) =
@@ -891,27 +918,29 @@ RGCN_API int rgcn_rank_count_f32(const float *scores, const int64_t *batch, int6
  * 128 x 128 tile per 128 queries on the rows nodes[target_q]); the count pass = that product again, tile by tile, with an epilogue that
  * compares with tscore instead of storing.  A workgroup owns 128 queries and one of `strips` runs of consecutive candidate tiles
  * (strips = 0: the library's choice, two workgroups per compute unit; a strip may own no tile), keeps its counters in registers and
- * writes one (greater, ties) pair per strip and query; a last kernel sums the strips.  filt_q / filt_n [F] (int32, device; F = 0 with
- * NULL lists = raw ranks) set bits in a mask [Q][ceil(n_nodes / 32)] inside the workspace with integer atomic OR (duplicates are
+ * writes one (greater, ties) pair per strip and query; a last kernel sums the strips.  The filter block (no filter = raw
+ * ranks) sets bits in a mask [Q][ceil(n_nodes / 32)] inside the workspace with integer atomic OR (duplicates are
  * harmless) and a masked cell compares as -inf.  An entry on a query's own target -- a caller error in both routes -- is IGNORED here.
- * Entries are NOT range-checked on the device (the Python wrapper checks 0 <= filt_q < Q, 0 <= filt_n < n_nodes).
+ * List entries are NOT range-checked on the device (the Python wrapper checks 0 <= filt_q < Q, 0 <= filt_n < n_nodes).
  * workspace: rgcn_distmult_rank_fused_workspace_bytes(Q, n_nodes, d, strips, bf16) bytes (the same `strips` as the call; no device is
  * asked: strips = 0 sizes for the largest default), 16-byte aligned.  Errors as the score-all entries: RGCN_EINVAL for bad, NULL or
  * misaligned arguments, strips < 0 and biases partly set; RGCN_EUNSUPPORTED beyond INT32_MAX workgroups; Q == 0 launches nothing. */
 RGCN_API int64_t rgcn_distmult_rank_fused_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
 RGCN_API int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                          const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
-                                          int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                          const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                          int64_t K, int32_t strips, void *workspace, int64_t *greater, int64_t *ties, float *tscore,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 RGCN_API int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                           const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                           const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                           const int32_t *fvals, int64_t K, int32_t strips, void *workspace, int64_t *greater,
                                            int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 /* Top-k link prediction: for each of the Q queries of `batch` the k entities that complete it best as its head (direction RGCN_QUERY_HEAD) or its tail,
  * ids [Q, k] (int64) and scores [Q, k] (float) -- without a [Q, n_nodes] score buffer.  The scores are bit for bit the cells of
  * rgcn_distmult_score_all_f32 / _bf16 (the same product and bias epilogue); the column of `batch` that is predicted is ignored.
  * Order within a row: score descending, equal scores (==: +0 and -0 are one value, returned as +0) by ascending id -- one answer,
- * whatever `strips` is.  filt_q / filt_n [F] (int32, device; F = 0 with NULL lists = no filter) exclude cells through the bit mask of
+ * whatever `strips` is.  The filter block excludes cells through the bit mask of
  * the fused evaluator; prediction has no target, so EVERY listed cell is excluded (the ranking entries ignore an entry on the target).
  * A score of -inf -- what an excluded cell holds on the materialised route -- is excluded as well.  With fewer than k candidates left
  * (k > n_nodes, heavy filtering) the tail of a row is id -1, score -inf.  NaN scores are outside the contract.
@@ -925,18 +954,19 @@ RGCN_API int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int3
  * bad, NULL or misaligned arguments, k < 1, strips < 0 and biases partly set; Q == 0 launches nothing.  Filter entries and triples are
  * NOT range-checked on the device (the Python wrapper checks). */
 RGCN_API int64_t rgcn_distmult_topk_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t k, int32_t strips, int32_t bf16);
-RGCN_API int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                    const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                    const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
-                                    float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel, const float *sbias,
+                                    const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F,
+                                    const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips,
+                                    void *workspace, int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 RGCN_API int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                     const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
-                                     float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                     const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                     int64_t K, int32_t k, int32_t strips, void *workspace, int64_t *ids, float *scores, int64_t n_nodes,
+                                     int32_t n_rel, int32_t d, void *stream);
 /* 1-N softmax loss (an extension: the reference trains on sampled negatives only), forward: for each of the Q queries of `batch`
  *   lse[q] = log sum_{n allowed} exp(s[q, n])      and      tscore[q] = s[q, target_q]
  * with s the cells of rgcn_distmult_score_all_f32 / _bf16 bit for bit (the same product and bias epilogue) and `allowed` every
- * n < n_nodes whose bit of the fused evaluator's mask is clear -- filt_q / filt_n [F] as in rgcn_distmult_rank_fused_*: an entry on a
+ * n < n_nodes whose bit of the fused evaluator's mask is clear -- the filter block as in rgcn_distmult_rank_fused_*: an entry on a
  * query's own target is IGNORED, so the target is always in the sum.  The loss of a query is lse[q] - tscore[q]; no [Q, n_nodes] buffer
  * exists.  Passes on `stream`, no host synchronisation, no memset: the query pass; the target pass of the fused evaluator; the strip
  * pass on its grid, each wave keeping one (m, l) = (largest score, sum exp(score - m)) pair per query row in registers and writing one
@@ -947,109 +977,50 @@ RGCN_API int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t he
  * misaligned arguments, strips < 0 and biases partly set; RGCN_EUNSUPPORTED beyond INT32_MAX workgroups; Q == 0 launches nothing.
  * Filter entries and triples are NOT range-checked on the device (the Python wrapper checks). */
 RGCN_API int64_t rgcn_distmult_lse_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
-RGCN_API int rgcn_distmult_lse_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                   const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                   const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
-                                   int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+RGCN_API int rgcn_distmult_lse_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel, const float *sbias,
+                                   const float *pbias, const float *obias, const int32_t *filt_q, const int32_t *filt_n, int64_t F,
+                                   const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips,
+                                   void *workspace, float *lse, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 RGCN_API int rgcn_distmult_lse_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                     const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                    const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
-                                    int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                    const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                    int64_t K, int32_t strips, void *workspace, float *lse, float *tscore, int64_t n_nodes, int32_t n_rel,
+                                    int32_t d, void *stream);
 /* 1-N softmax loss, gradient cells of the candidate columns [c_first, c_first + c_count) (c_first a multiple of 128, the chunk inside
- * [0, n_nodes)), fp32 only: the product is computed again, one 128 x 128 tile per workgroup, and
+ * [0, n_nodes)), fp32 table: the product is computed again, one 128 x 128 tile per workgroup, and
  *   dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - [c == target_q]),   a filtered cell 0,
  * dS row-major [Q, c_count].  scale_q = gscale[per_query ? q : 0] / mean_over: gscale is a DEVICE float ([1], or [Q] with
  * per_query != 0) -- the upstream gradient, never read back --, mean_over >= 1 the host's divisor of a mean (the ABI passes no float by
  * value).  lse [Q]: what rgcn_distmult_lse_f32 returned for the same arguments.  The call stands alone: query vectors, bias terms and
- * the filter bits OF THE CHUNK are formed again in `workspace` (rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d) bytes,
+ * the filter bits OF THE CHUNK are formed again in `workspace` (rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d, bf16) bytes,
  * 16-byte aligned: nothing of the forward's workspace has to outlive it, and the mask is [Q][ceil(c_count / 32)] words, not the whole
  * [Q][ceil(n_nodes / 32)]).  No host synchronisation, no memset; errors as above. */
-RGCN_API int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d);
+RGCN_API int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d, int32_t bf16);
 RGCN_API int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                            const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
-                                            int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
-                                            int32_t n_rel, int32_t d, void *stream);
+                                            const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                            const int32_t *fvals, int64_t K, const float *lse, const float *gscale, int32_t per_query,
+                                            int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                            int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 /* The same gradient cells on a bf16 entity table: nodes bf16 [n_nodes, d], rel and the biases fp32, dS fp32 row-major
  * [Q, c_count] as above, the same chunk contract.  The product runs on v_mfma_f32_16x16x32_bf16 from the three bf16 terms of the fp32
  * query vector nodes[fixed] * rel[p] (their sum is the vector exactly, as in rgcn_distmult_score_all_bf16): s is bit for bit the cell
  * rgcn_distmult_score_all_bf16 stores and rgcn_distmult_lse_bf16 adds, so a row whose only allowed cell is its target gets
  * exp(0) - 1 = 0.  lse [Q]: what rgcn_distmult_lse_bf16 returned for the same arguments.  16-byte loads of the entity rows when
  * d % 8 == 0 and `nodes` is 16-byte aligned, element by element otherwise -- the choice the forward makes for the same table.
- * workspace: rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d) bytes (the query terms 3 Q ceil32(d) bf16, 2 Q bias terms,
+ * workspace: rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d, 1) bytes (the query terms 3 Q ceil32(d) bf16, 2 Q bias terms,
  * the chunk's mask [Q][ceil(c_count / 32)]; no device is asked; 0 for arguments the call refuses), 16-byte aligned.  Errors as the fp32
  * form: RGCN_EINVAL for a bad chunk, NULL or misaligned arguments, biases partly set and mean_over < 1; RGCN_EUNSUPPORTED beyond
  * INT32_MAX workgroups; Q == 0 launches nothing; nothing is launched on a refused call.  No host synchronisation, no memset. */
-RGCN_API int64_t rgcn_distmult_softmax_grad_bf16_workspace_bytes(int64_t Q, int64_t c_count, int32_t d);
 RGCN_API int rgcn_distmult_softmax_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                              const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                             const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
-                                             int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
-                                             int32_t n_rel, int32_t d, void *stream);
-/* Device-resident filter index (DESIGN.md 4.5): the known completions of one direction as a sorted table on the device, in place of
- * the per-call lists (filt_q, filt_n, F).  fkeys [K] (int64), STRICTLY ASCENDING, key = p * n_nodes + o for head queries (the known
- * heads of (?, p, o)) and p * n_nodes + s for tail queries; fptr [K + 1] (int64); fvals [fptr[K]] (int32), the completions of key k in
- * fvals[fptr[k] .. fptr[k + 1]), ASCENDING AND UNIQUE within a key, each in [0, n_nodes).  NOTHING of the index is range-checked on the
- * device: its builder (functional.FilterIndex) validates it once on the host.  K = 0 with NULL pointers = no filter, as F = 0 is.
- *
- * rgcn_filter_mask_index zeroes the caller's mask [Q][ceil(c_count / 32)] (uint32) and sets, for each query q of `batch`, the bit
- * n - c_first of row q for every completion n of the query's key inside the columns [c_first, c_first + c_count) (inside [0, n_nodes));
- * keep_target == 0 skips a completion equal to the query's own target (batch[q, 0] for head queries, batch[q, 2] for tail queries).  One
- * wave per query: the key's binary search, two more over the key's sorted completions for the column range, then integer atomic OR.
- * These are the bits the list forms set from (filt_q, filt_n); the _index entry points below call it on the mask of their workspace.
- * n_nodes is the entity count the keys were formed with.  No host synchronisation, no memset. */
-RGCN_API int rgcn_filter_mask_index(const int64_t *batch, int64_t Q, int32_t head, const int64_t *fkeys, const int64_t *fptr,
-                                    const int32_t *fvals, int64_t K, int32_t keep_target, int64_t c_first, int64_t c_count, uint32_t *mask,
-                                    int64_t n_nodes, void *stream);
-/* rgcn_rank_filter_f32 from the index: scores[q, n] = -inf for every completion n of query q's key other than the query's own target
- * (scores row-major [Q, n_nodes]); keep_target != 0 (prediction: the query has no target) writes that cell too, as a list built for
- * prediction does.  Index contract as above: keys strictly ascending, fvals ascending within a key, nothing checked. */
-RGCN_API int rgcn_rank_filter_index_f32(float *scores, const int64_t *batch, int64_t Q, int32_t head, int64_t n_nodes, const int64_t *fkeys,
-                                        const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t keep_target, void *stream);
-/* The filtered entry points with the index (fkeys, fptr, fvals, K) where the list forms take (filt_q, filt_n, F): everything else --
- * the workspace sizes and layouts, the passes, the errors -- is the list form's, and with the same excluded cells every result is bit
- * for bit the list form's (the mask is filled another way; the product kernels are the same).  Index contract as above: keys strictly
- * ascending, fvals ascending and unique within a key, nothing range-checked on the device, the index validated by its builder.  Ranking,
- * log-sum-exp and gradient cells skip a completion on the query's own target; top-k excludes every completion. */
-RGCN_API int rgcn_distmult_rank_fused_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
-                                                void *stream);
-RGCN_API int rgcn_distmult_rank_fused_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                 const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                 const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                 int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
-                                                 void *stream);
-RGCN_API int rgcn_distmult_topk_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                          const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
-                                          int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_topk_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                           const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
-                                           int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_lse_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                         const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                         const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
-                                         float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                          const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
-                                          float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
-                                                  int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
-                                                  float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
-                                                   int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
-                                                   float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                             const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                             const int32_t *fvals, int64_t K, const float *lse, const float *gscale, int32_t per_query,
+                                             int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                             int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 /* 1-N softmax loss with label smoothing (an extension with no reference counterpart, as the 1-N entries above), forward.  With A_q the
  * allowed set of query q as in rgcn_distmult_lse_* (every n < n_nodes whose mask bit is clear; an entry on the query's own target is
- * ignored, so the target is in A_q and |A_q| >= 1), the four rgcn_distmult_lse_* forms again with two more outputs behind tscore:
+ * ignored, so the target is in A_q and |A_q| >= 1), the two rgcn_distmult_lse_* entries again with two more outputs behind tscore:
  *   ssum[q] = sum_{n in A_q} s[q, n]   (float [Q])        and        cnt[q] = |A_q|   (int32 [Q]),
  * from which the caller composes, for a smoothing eps in [0, 1),
  *   loss[q] = lse[q] - (1 - eps) tscore[q] - (eps / cnt[q]) ssum[q]
@@ -1066,52 +1037,36 @@ RGCN_API int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t
 RGCN_API int64_t rgcn_distmult_lse_smooth_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16);
 RGCN_API int rgcn_distmult_lse_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                           const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                          const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
-                                          float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                          const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                          int64_t K, int32_t strips, void *workspace, float *lse, float *tscore, float *ssum, int32_t *cnt,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
 RGCN_API int rgcn_distmult_lse_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                            const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                           const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                           const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                           const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse, float *tscore,
                                            float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_lse_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
-                                                int32_t d, void *stream);
-RGCN_API int rgcn_distmult_lse_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                 const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                 const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                 float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
-                                                 int32_t d, void *stream);
-/* 1-N softmax loss with label smoothing, gradient cells (an extension with no reference counterpart): the four
- * rgcn_distmult_softmax_grad_* forms again with two more inputs behind gscale,
+/* 1-N softmax loss with label smoothing, gradient cells (an extension with no reference counterpart): the two
+ * rgcn_distmult_softmax_grad_* entries again with two more inputs behind gscale,
  *   dS[q, c - c_first] = scale_q (exp(s[q, c] - lse[q]) - keep[0] [c == target_q] - uni[q]),   a filtered cell 0,
  * keep a DEVICE float [1] holding 1 - eps and uni a DEVICE float [Q] holding eps / cnt[q] (the ABI passes no float by value; neither is
  * read back).  The sum of a row of dS is still 0.  lse: what the smoothed or the unsmoothed forward returned for the same arguments (the
- * same bits).  Chunk contract, scale_q, workspace (rgcn_distmult_softmax_grad[_bf16]_workspace_bytes), passes and errors are those of
+ * same bits).  Chunk contract, scale_q, workspace (rgcn_distmult_softmax_grad_workspace_bytes), passes and errors are those of
  * the unsmoothed forms; NULL keep or uni is RGCN_EINVAL.  A row whose only allowed cell is its target gets exp(0) - keep - uni, which is
  * 0 exactly when keep + uni is 1 exactly (eps = 0.25: 0.75 and 0.25). */
 RGCN_API int rgcn_distmult_softmax_grad_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                                    const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                                   const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
-                                                   const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
-                                                   void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                                   const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                                   const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                   const float *keep, const float *uni, int32_t per_query, int64_t mean_over,
+                                                   int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                                   int32_t n_rel, int32_t d, void *stream);
 RGCN_API int rgcn_distmult_softmax_grad_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                                     const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                                    const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
-                                                    const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
-                                                    void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_softmax_grad_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                         const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                         const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
-                                                         const float *gscale, const float *keep, const float *uni, int32_t per_query,
-                                                         int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
-                                                         int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
-RGCN_API int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                          const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                          const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
-                                                          const float *gscale, const float *keep, const float *uni, int32_t per_query,
-                                                          int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
-                                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream);
+                                                    const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                                    const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                    const float *keep, const float *uni, int32_t per_query, int64_t mean_over,
+                                                    int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                                    int32_t n_rel, int32_t d, void *stream);
 /* 1-N multi-label binary cross-entropy of DistMult ("K-vs-All"; an extension -- the reference's sampled-negative BCE,
  * experiments/predict_links.py:160-176 with utils/misc.py negative_sampling, is this loss on a sample of the cells), forward sums.
  * Replaces: distmult_score_all into a [Q, n_nodes] logit matrix, a dense [Q, n_nodes] label matrix and
@@ -1125,8 +1080,8 @@ RGCN_API int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, 
  * Three rules differ from the rgcn_distmult_lse_* forms.  (1) The mask bits are labels: a listed cell on the query's own target STAYS
  * set, and the target's bit is set whether it is listed or not (duplicates are harmless: integer OR).  (2) Nothing is filtered out:
  * every n < n_nodes adds to sp, whatever its bit; only the columns of the ragged last tile at or beyond n_nodes are out of all three
- * sums.  (3) (the gradient entry below) the rows of dS do not sum to zero.  The lists and the index are two ways to name the positives:
- * at most ONE of F and K may be non-zero (RGCN_EINVAL); both zero is 1-vs-All, the target alone positive.  The mask
+ * sums.  (3) (the gradient entry below) the rows of dS do not sum to zero.  The lists and the index are two ways to name the positives
+ * (the filter block's contract); both zero is 1-vs-All, the target alone positive.  The mask
  * [Q][ceil(n_nodes / 32)] of the workspace is filled on every call.  softplus(s) = max(s, 0) + log(1 + exp(-|s|)): finite for every
  * finite fp32 score.  Passes: mask (zero, lists or index, targets) | query vectors | one strip pass (rgcn_distmult_lse_smooth_*'s walk,
  * strips and occupancy: one 16-byte partial per strip half and query, zeros for a strip without a tile) | a merge in index order -- one

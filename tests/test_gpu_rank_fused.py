@@ -330,12 +330,12 @@ def test_c_abi_argument_errors():
     assert p(ws) % 16 == 0
 
     def f32(w=p(ws), gp=p(g), tp=p(t), tsp=p(ts), strips=0, F=0, q=None, n=None):
-        return L.rgcn_distmult_rank_fused_f32(p(batch), Q, 1, p(nodes), p(rel), None, None, None, q, n, F, strips, w, gp, tp, tsp, N, 3, dim,
-                                              st)
+        return L.rgcn_distmult_rank_fused_f32(p(batch), Q, 1, p(nodes), p(rel), None, None, None, q, n, F, None, None, None, 0, strips, w, gp, tp, tsp,
+                                              N, 3, dim, st)
 
     def b16(w=p(ws), gp=p(g), tp=p(t), tsp=p(ts), strips=0, F=0, q=None, n=None):
-        return L.rgcn_distmult_rank_fused_bf16(p(batch), Q, 1, p(nodes16), p(rel), None, None, None, q, n, F, strips, w, gp, tp, tsp, N, 3,
-                                               dim, st)
+        return L.rgcn_distmult_rank_fused_bf16(p(batch), Q, 1, p(nodes16), p(rel), None, None, None, q, n, F, None, None, None, 0, strips, w, gp, tp, tsp,
+                                               N, 3, dim, st)
 
     for call in (f32, b16):
         assert call(w=None) == _native.EINVAL and call(gp=None) == _native.EINVAL and call(tsp=None) == _native.EINVAL
@@ -348,12 +348,12 @@ def test_c_abi_argument_errors():
     torch.cuda.synchronize()
     assert g.tolist() == [-7] * Q and t.tolist() == [-7] * Q and ts.tolist() == [-7.0] * Q          # nothing was launched
     # biases partly set; Q == 0 is fine with nothing else set
-    assert L.rgcn_distmult_rank_fused_f32(p(batch), Q, 1, p(nodes), p(rel), p(ts), None, None, None, None, 0, 0, p(ws), p(g), p(t), p(ts),
-                                          N, 3, dim, st) == _native.EINVAL
-    assert L.rgcn_distmult_rank_fused_f32(None, 0, 1, None, None, None, None, None, None, None, 0, 0, None, None, None, None, N, 3, dim,
-                                          st) == _native.OK
-    assert L.rgcn_distmult_rank_fused_bf16(None, 0, 1, None, None, None, None, None, None, None, 0, 0, None, None, None, None, N, 3, dim,
-                                           st) == _native.OK
+    assert L.rgcn_distmult_rank_fused_f32(p(batch), Q, 1, p(nodes), p(rel), p(ts), None, None, None, None, 0, None, None, None, 0, 0, p(ws), p(g),
+                                          p(t), p(ts), N, 3, dim, st) == _native.EINVAL
+    assert L.rgcn_distmult_rank_fused_f32(None, 0, 1, None, None, None, None, None, None, None, 0, None, None, None, 0, 0, None, None, None, None,
+                                          N, 3, dim, st) == _native.OK
+    assert L.rgcn_distmult_rank_fused_bf16(None, 0, 1, None, None, None, None, None, None, None, 0, None, None, None, 0, 0, None, None, None, None,
+                                           N, 3, dim, st) == _native.OK
     # and the good call, through the same closures
     assert f32(F=1, q=p(fq), n=p(fn)) == _native.OK
     want = _native.distmult_rank_fused(batch, True, nodes, rel, filt_q=fq, filt_n=fn)

@@ -525,8 +525,8 @@ def test_wrapper_argument_errors():
     ws = torch.empty(_native.lse_workspace_bytes(2, 10, 8) + 1024, device=DEV, dtype=torch.uint8)
 
     def grad(c_first=0, c_count=10, mean_over=2, w=p(ws), out=p(dS)):
-        return L.rgcn_distmult_softmax_grad_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, p(lse), p(g), 0, mean_over,
-                                                c_first, c_count, w, out, 10, 3, 8, st)
+        return L.rgcn_distmult_softmax_grad_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, None, None, None, 0, p(lse), p(g), 0,
+                                                mean_over, c_first, c_count, w, out, 10, 3, 8, st)
     assert grad(c_first=64) == _native.EINVAL and grad(c_first=128) == _native.EINVAL and grad(c_count=11) == _native.EINVAL
     assert grad(c_count=0) == _native.EINVAL and grad(mean_over=0) == _native.EINVAL and grad(w=None) == _native.EINVAL
     assert grad(out=None) == _native.EINVAL and grad(w=p(ws) + 4) == _native.EINVAL

@@ -461,17 +461,19 @@ def test_the_bf16_entry_points_refuse_what_the_fp32_ones_refuse():
     p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     lse, g = torch.zeros(2, device=DEV), torch.ones(1, device=DEV)
     dS = torch.full((2, 10), -7.0, device=DEV)
-    ws = torch.empty(L.rgcn_distmult_softmax_grad_bf16_workspace_bytes(2, 10, 8) + 1024, device=DEV, dtype=torch.uint8)
+    ws = torch.empty(L.rgcn_distmult_softmax_grad_workspace_bytes(2, 10, 8, 1) + 1024, device=DEV, dtype=torch.uint8)
 
     def lists(c_first=0, c_count=10, mean_over=2, w=p(ws), out=p(dS)):
-        return L.rgcn_distmult_softmax_grad_bf16(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, p(lse), p(g), 0, mean_over,
-                                                 c_first, c_count, w, out, 10, 3, 8, st)
+        filt_q, filt_n, F = None, None, 0
+        return L.rgcn_distmult_softmax_grad_bf16(p(ok), 2, 1, p(nodes), p(rel), None, None, None, filt_q, filt_n, F, None, None, None, 0, p(lse),
+                                                 p(g), 0, mean_over, c_first, c_count, w, out, 10, 3, 8, st)
 
     def index(c_first=0, c_count=10, mean_over=2, w=p(ws), out=p(dS)):
-        return L.rgcn_distmult_softmax_grad_index_bf16(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, None, 0, p(lse), p(g), 0,
-                                                       mean_over, c_first, c_count, w, out, 10, 3, 8, st)
+        fkeys, fptr, fvals, K = None, None, None, 0
+        return L.rgcn_distmult_softmax_grad_bf16(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, fkeys, fptr, fvals, K, p(lse),
+                                                 p(g), 0, mean_over, c_first, c_count, w, out, 10, 3, 8, st)
 
-    for grad, name in ((lists, b"distmult_softmax_grad_bf16"), (index, b"distmult_softmax_grad_index_bf16")):
+    for grad, name in ((lists, b"distmult_softmax_grad_bf16"), (index, b"distmult_softmax_grad_bf16")):
         for kw in ({"c_first": 64}, {"c_first": 128}, {"c_count": 11}, {"c_count": 0}, {"mean_over": 0}, {"w": None}, {"out": None},
                    {"w": p(ws) + 4}):
             assert grad(**kw) == _native.EINVAL, (name, kw)
@@ -480,11 +482,11 @@ def test_the_bf16_entry_points_refuse_what_the_fp32_ones_refuse():
         assert (dS == -7.0).all()                                                                  # nothing was launched
     # biases partly set
     sb = torch.zeros(10, device=DEV)
-    assert L.rgcn_distmult_softmax_grad_bf16(p(ok), 2, 1, p(nodes), p(rel), p(sb), None, None, None, None, 0, p(lse), p(g), 0, 2, 0, 10, p(ws),
-                                             p(dS), 10, 3, 8, st) == _native.EINVAL
+    assert L.rgcn_distmult_softmax_grad_bf16(p(ok), 2, 1, p(nodes), p(rel), p(sb), None, None, None, None, 0, None, None, None, 0, p(lse), p(g), 0, 2,
+                                             0, 10, p(ws), p(dS), 10, 3, 8, st) == _native.EINVAL
     # Q == 0 launches nothing
-    assert L.rgcn_distmult_softmax_grad_bf16(None, 0, 1, p(nodes), p(rel), None, None, None, None, None, 0, None, None, 0, 2, 0, 10, p(ws),
-                                             None, 10, 3, 8, st) == _native.OK
+    assert L.rgcn_distmult_softmax_grad_bf16(None, 0, 1, p(nodes), p(rel), None, None, None, None, None, 0, None, None, None, 0, None, None, 0, 2, 0, 10,
+                                             p(ws), None, 10, 3, 8, st) == _native.OK
     torch.cuda.synchronize()
     assert (dS == -7.0).all()
     for grad in (lists, index):

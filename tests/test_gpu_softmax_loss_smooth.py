@@ -606,12 +606,12 @@ def test_the_entry_points_refuse_null_outputs_and_inputs():
     ws = torch.empty(_native.lse_smooth_workspace_bytes(2, 10, 8) + 1024, device=DEV, dtype=torch.uint8)
 
     def fwd(ssum=p(ss), cnt=p(cn), w=p(ws)):
-        return L.rgcn_distmult_lse_smooth_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, 0, w, p(lse), p(ts), ssum, cnt,
-                                              10, 3, 8, st)
+        return L.rgcn_distmult_lse_smooth_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, None, None, None, 0, 0, w, p(lse), p(ts),
+                                              ssum, cnt, 10, 3, 8, st)
 
     def grad(k=p(keep), u=p(uni), c_first=0):
-        return L.rgcn_distmult_softmax_grad_smooth_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, p(lse), p(g), k, u, 0, 2,
-                                                       c_first, 10, p(ws), p(dS), 10, 3, 8, st)
+        return L.rgcn_distmult_softmax_grad_smooth_f32(p(ok), 2, 1, p(nodes), p(rel), None, None, None, None, None, 0, None, None, None, 0, p(lse), p(g),
+                                                       k, u, 0, 2, c_first, 10, p(ws), p(dS), 10, 3, 8, st)
     assert fwd(ssum=None) == _native.EINVAL and fwd(cnt=None) == _native.EINVAL and fwd(w=p(ws) + 4) == _native.EINVAL
     assert grad(k=None) == _native.EINVAL and grad(u=None) == _native.EINVAL and grad(c_first=64) == _native.EINVAL
     assert b"distmult_softmax_grad_smooth" in L.rgcn_last_error()

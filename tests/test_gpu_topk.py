@@ -437,10 +437,12 @@ def test_c_abi_argument_errors():
     assert p(ws) % 16 == 0
 
     def f32(w=p(ws), ip=p(ids), sp=p(sc), strips=0, F=0, q=None, n=None, k=k):
-        return L.rgcn_distmult_topk_f32(p(batch), Q, 1, p(nodes), p(rel), None, None, None, q, n, F, k, strips, w, ip, sp, N, 3, dim, st)
+        return L.rgcn_distmult_topk_f32(p(batch), Q, 1, p(nodes), p(rel), None, None, None, q, n, F, None, None, None, 0, k, strips, w, ip, sp,
+                                        N, 3, dim, st)
 
     def b16(w=p(ws), ip=p(ids), sp=p(sc), strips=0, F=0, q=None, n=None, k=k):
-        return L.rgcn_distmult_topk_bf16(p(batch), Q, 1, p(nodes16), p(rel), None, None, None, q, n, F, k, strips, w, ip, sp, N, 3, dim, st)
+        return L.rgcn_distmult_topk_bf16(p(batch), Q, 1, p(nodes16), p(rel), None, None, None, q, n, F, None, None, None, 0, k, strips, w, ip, sp,
+                                         N, 3, dim, st)
 
     for call in (f32, b16):
         assert call(w=None) == _native.EINVAL and call(ip=None) == _native.EINVAL and call(sp=None) == _native.EINVAL
@@ -453,12 +455,12 @@ def test_c_abi_argument_errors():
     torch.cuda.synchronize()
     assert (ids == -7).all() and (sc == -7.0).all()                       # nothing was launched
     # biases partly set; Q == 0 is fine with nothing else set
-    assert L.rgcn_distmult_topk_f32(p(batch), Q, 1, p(nodes), p(rel), p(sc), None, None, None, None, 0, k, 0, p(ws), p(ids), p(sc), N, 3,
-                                    dim, st) == _native.EINVAL
-    assert L.rgcn_distmult_topk_f32(None, 0, 1, None, None, None, None, None, None, None, 0, k, 0, None, None, None, N, 3, dim,
-                                    st) == _native.OK
-    assert L.rgcn_distmult_topk_bf16(None, 0, 1, None, None, None, None, None, None, None, 0, k, 0, None, None, None, N, 3, dim,
-                                     st) == _native.OK
+    assert L.rgcn_distmult_topk_f32(p(batch), Q, 1, p(nodes), p(rel), p(sc), None, None, None, None, 0, None, None, None, 0, k, 0, p(ws), p(ids),
+                                    p(sc), N, 3, dim, st) == _native.EINVAL
+    assert L.rgcn_distmult_topk_f32(None, 0, 1, None, None, None, None, None, None, None, 0, None, None, None, 0, k, 0, None, None, None,
+                                    N, 3, dim, st) == _native.OK
+    assert L.rgcn_distmult_topk_bf16(None, 0, 1, None, None, None, None, None, None, None, 0, None, None, None, 0, k, 0, None, None, None,
+                                     N, 3, dim, st) == _native.OK
     # and the good call, through the same closures: rows of k in the first Q * k cells of the outputs
     assert f32(F=1, q=p(fq), n=p(fn)) == _native.OK
     want = _native.distmult_topk(batch, True, nodes, rel, k=k, filt_q=fq, filt_n=fn)

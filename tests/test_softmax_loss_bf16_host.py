@@ -1,4 +1,4 @@
-"""Host side of the native bf16 backward of the 1-N softmax loss (no GPU): the three C entry points exist and bind from the header, the
+"""Host side of the native bf16 backward of the 1-N softmax loss (no GPU): the C entry points exist and bind from the header, the
 workspace-size function (which asks no device), the bf16 configuration, and the argument errors raised before anything touches a device."""
 import ctypes
 import os
@@ -11,7 +11,7 @@ import yaml
 from conftest import PKG
 from torch_rgcn import _native, functional
 
-NEW = ("rgcn_distmult_softmax_grad_bf16_workspace_bytes", "rgcn_distmult_softmax_grad_bf16", "rgcn_distmult_softmax_grad_index_bf16")
+NEW = ("rgcn_distmult_softmax_grad_workspace_bytes", "rgcn_distmult_softmax_grad_bf16", "rgcn_distmult_softmax_grad_smooth_bf16")
 
 
 def test_the_library_exports_and_the_header_binds_the_new_entry_points():
@@ -20,11 +20,11 @@ def test_the_library_exports_and_the_header_binds_the_new_entry_points():
     for name in NEW:
         assert hasattr(raw, name), name
         assert getattr(L, name).argtypes is not None, name
-    size = L.rgcn_distmult_softmax_grad_bf16_workspace_bytes
-    assert size.restype is ctypes.c_int64 and size.argtypes == [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
+    size = L.rgcn_distmult_softmax_grad_workspace_bytes
+    assert size.restype is ctypes.c_int64 and size.argtypes == [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     # the signatures of the fp32 forms (every pointer is a void pointer to the binder: `const uint16_t *nodes` for `const float *nodes`)
     assert L.rgcn_distmult_softmax_grad_bf16.argtypes == L.rgcn_distmult_softmax_grad_f32.argtypes
-    assert L.rgcn_distmult_softmax_grad_index_bf16.argtypes == L.rgcn_distmult_softmax_grad_index_f32.argtypes
+    assert L.rgcn_distmult_softmax_grad_smooth_bf16.argtypes == L.rgcn_distmult_softmax_grad_smooth_f32.argtypes
     header = open(_native._HEADER_PATH).read()
     for name in NEW[1:]:
         decl = header[header.index(f"RGCN_API int {name}("):]
@@ -36,7 +36,9 @@ def pad32(d):
 
 
 def test_bf16_gradient_workspace_bytes():
-    size = _native.lib().rgcn_distmult_softmax_grad_bf16_workspace_bytes
+    def size(Q, c_count, d):
+        return _native.lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d, 1)
+
     assert size(-1, 128, 8) == 0 and size(10, 0, 8) == 0 and size(10, -1, 8) == 0 and size(10, 128, 0) == 0 and size(10, 128, -3) == 0
     Qs = [0, 1, 2, 127, 128, 129, 5_000, 131_072]
     Cs = [1, 31, 32, 33, 127, 128, 129, 1_000, 40_943, 1_000_000]
@@ -55,8 +57,8 @@ def test_bf16_gradient_workspace_bytes():
     # the mask of a chunk, not of the whole table
     assert size(5_000, 128, 200) < 8 * 2 ** 20
     # the fp32 form keeps its values: fp32 query vectors where this one holds three bf16 terms
-    f32 = _native.lib().rgcn_distmult_softmax_grad_workspace_bytes
-    assert f32(5_000, 128, 200) - 5_000 * 200 * 4 == size(5_000, 128, 200) - 3 * 5_000 * 224 * 2
+    f32 = _native.lib().rgcn_distmult_softmax_grad_workspace_bytes(5_000, 128, 200, 0)
+    assert f32 - 5_000 * 200 * 4 == size(5_000, 128, 200) - 3 * 5_000 * 224 * 2
 
 
 def test_the_bf16_configuration_is_the_one_to_n_configuration_plus_one_key():

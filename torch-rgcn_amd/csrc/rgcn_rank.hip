@@ -20,7 +20,8 @@
 // Layout of the file: the two product loops (fp32, bf16) and the epilogues (store, count, select, add) first; then a tile-precision trait
 // (TileF32 / TileBf16) and the kernel roles -- score_all_kernel, target_score_kernel, strip_count_kernel, strip_select_kernel,
 // strip_lse_kernel, strip_lse_smooth_kernel, strip_bce_kernel, softmax_grad_kernel, bce_grad_kernel -- each written once over
-// <Tile, VEC>; then the entry points.
+// <Tile, VEC>; then the entry points: one per role and storage, each taking the filter (the labels of the BCE roles) as the lists
+// (filt_q, filt_n, F) or as the device-resident index (fkeys, fptr, fvals, K) -- StripArgs carries both, strip_check refuses both at once.
 #include <cmath>
 #include <cstdlib>
 
@@ -1405,7 +1406,7 @@ struct StripArgs {
   int64_t n_nodes;
   int32_t d;
   void *stream;
-  FilterIndexDev ix;              // the index forms: K > 0 fills the mask from the index (filt_q / filt_n NULL, F = 0)
+  FilterIndexDev ix;              // the filter as an index: K > 0 fills the mask from it (then F = 0; strip_check refuses both)
   int32_t dir() const { return query_dir(head); }
 };
 
@@ -1542,39 +1543,21 @@ extern "C" int64_t rgcn_distmult_rank_fused_workspace_bytes(int64_t Q, int64_t n
 
 extern "C" int rgcn_distmult_rank_fused_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                            const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                            const int32_t *fvals, int64_t K, int32_t strips, void *workspace, int64_t *greater,
                                             int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
   return rank_fused<TileF32>({"distmult_rank_fused", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                              n_nodes, d, stream}, greater, ties, tscore);
+                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, greater, ties, tscore);
 }
 
 extern "C" int rgcn_distmult_rank_fused_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                              const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                             const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, int64_t *greater,
+                                             const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                             const int32_t *fvals, int64_t K, int32_t strips, void *workspace, int64_t *greater,
                                              int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
   return rank_fused<TileBf16>({"distmult_rank_fused_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips,
-                               workspace, n_nodes, d, stream}, greater, ties, tscore);
-}
-
-extern "C" int rgcn_distmult_rank_fused_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                  int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
-                                                  void *stream) {
-  (void)n_rel;
-  return rank_fused<TileF32>({"distmult_rank_fused_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
-                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, greater, ties, tscore);
-}
-
-extern "C" int rgcn_distmult_rank_fused_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                   int64_t *greater, int64_t *ties, float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d,
-                                                   void *stream) {
-  (void)n_rel;
-  return rank_fused<TileBf16>({"distmult_rank_fused_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
                                workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, greater, ties, tscore);
 }
 
@@ -1627,38 +1610,22 @@ extern "C" int64_t rgcn_distmult_topk_workspace_bytes(int64_t Q, int64_t n_nodes
 
 extern "C" int rgcn_distmult_topk_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                       const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                      const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
-                                      float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+                                      const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                      int64_t K, int32_t k, int32_t strips, void *workspace, int64_t *ids, float *scores, int64_t n_nodes,
+                                      int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return topk_fused<TileF32>({"distmult_topk", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes,
-                              d, stream}, k, ids, scores);
+  return topk_fused<TileF32>({"distmult_topk", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
 }
 
 extern "C" int rgcn_distmult_topk_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                        const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                       const int32_t *filt_n, int64_t F, int32_t k, int32_t strips, void *workspace, int64_t *ids,
-                                       float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+                                       const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                       int64_t K, int32_t k, int32_t strips, void *workspace, int64_t *ids, float *scores, int64_t n_nodes,
+                                       int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
   return topk_fused<TileBf16>({"distmult_topk_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                               n_nodes, d, stream}, k, ids, scores);
-}
-
-extern "C" int rgcn_distmult_topk_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                            const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
-                                            int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return topk_fused<TileF32>({"distmult_topk_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
-                              n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
-}
-
-extern "C" int rgcn_distmult_topk_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                             const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                             const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t k, int32_t strips, void *workspace,
-                                             int64_t *ids, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return topk_fused<TileBf16>({"distmult_topk_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
-                               workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
+                               n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, k, ids, scores);
 }
 
 // ------------------------------------------------------------------ 1-N softmax loss: entry points
@@ -1675,29 +1642,24 @@ int lse_fused(const StripArgs<typename Tile::elem> &a, float *lse, float *tscore
   auto too_many = [&](int64_t) { return smooth && a.n_nodes > INT32_MAX; };
   if (int rc = strip_begin<Tile>(a, smooth ? sizeof(float4) : sizeof(float2), 0, too_many, smooth ? "entities" : "strips", c)) return rc;
   const int Q = (int)a.Q;
+  const dim3 strip_grid((unsigned)(c.n_strips * c.qbl)), merge_grid((unsigned)((a.Q + WG - 1) / WG));
+  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
+    hipLaunchKernelGGL((target_score_kernel<Tile, decltype(vec)::value>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
+                       c.b, tscore, Q, a.dir());
+  });
+  auto strip = [&](auto kern, auto *part) {
+    hipLaunchKernelGGL(kern, strip_grid, dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.mask, (long long)c.mask_w, part, Q,
+                       (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
+  };
   if (smooth) {
     float4 *part = static_cast<float4 *>(c.part);
-    with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
-      constexpr bool V = decltype(vec)::value;
-      hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
-                         a.dir());
-      hipLaunchKernelGGL((strip_lse_smooth_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb,
-                         c.cbias, c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
-    });
-    hipLaunchKernelGGL(lse_smooth_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float4 *)part,
-                       (int)(2 * c.n_strips), Q, lse, ssum, (int *)cnt);
-    HIP_TRY(hipGetLastError());
-    return RGCN_OK;
+    with_vec<Tile>(a.nodes, a.d, [&](auto vec) { strip(strip_lse_smooth_kernel<Tile, decltype(vec)::value>, part); });
+    hipLaunchKernelGGL(lse_smooth_merge_kernel, merge_grid, dim3(WG), 0, c.st, (const float4 *)part, (int)(2 * c.n_strips), Q, lse, ssum, (int *)cnt);
+  } else {
+    float2 *part = static_cast<float2 *>(c.part);
+    with_vec<Tile>(a.nodes, a.d, [&](auto vec) { strip(strip_lse_kernel<Tile, decltype(vec)::value>, part); });
+    hipLaunchKernelGGL(lse_merge_kernel, merge_grid, dim3(WG), 0, c.st, (const float2 *)part, (int)(2 * c.n_strips), Q, lse);
   }
-  float2 *part = static_cast<float2 *>(c.part);
-  with_vec<Tile>(a.nodes, a.d, [&](auto vec) {
-    constexpr bool V = decltype(vec)::value;
-    hipLaunchKernelGGL((target_score_kernel<Tile, V>), dim3((unsigned)c.qbl), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias, c.b, tscore, Q,
-                       a.dir());
-    hipLaunchKernelGGL((strip_lse_kernel<Tile, V>), dim3((unsigned)(c.n_strips * c.qbl)), dim3(WG), 0, c.st, c.q, a.nodes, c.dm, c.qb, c.cbias,
-                       c.mask, (long long)c.mask_w, part, Q, (long long)a.n_nodes, a.dir(), (int)c.qbl, (int)c.n_strips);
-  });
-  hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((a.Q + WG - 1) / WG)), dim3(WG), 0, c.st, (const float2 *)part, (int)(2 * c.n_strips), Q, lse);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1715,94 +1677,56 @@ extern "C" int64_t rgcn_distmult_lse_workspace_bytes(int64_t Q, int64_t n_nodes,
 
 extern "C" int rgcn_distmult_lse_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                     const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
-                                     int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+                                     const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                     int64_t K, int32_t strips, void *workspace, float *lse, float *tscore, int64_t n_nodes, int32_t n_rel,
+                                     int32_t d, void *stream) {
   (void)n_rel;
-  return lse_fused<TileF32>({"distmult_lse", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes, d,
-                             stream}, lse, tscore);
+  return lse_fused<TileF32>({"distmult_lse", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes,
+                             d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
 }
 
 extern "C" int rgcn_distmult_lse_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                       const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                      const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
-                                      int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+                                      const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr, const int32_t *fvals,
+                                      int64_t K, int32_t strips, void *workspace, float *lse, float *tscore, int64_t n_nodes, int32_t n_rel,
+                                      int32_t d, void *stream) {
   (void)n_rel;
   return lse_fused<TileBf16>({"distmult_lse_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                              n_nodes, d, stream}, lse, tscore);
-}
-
-extern "C" int rgcn_distmult_lse_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                           const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
-                                           float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return lse_fused<TileF32>({"distmult_lse_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace, n_nodes,
-                             d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
-}
-
-extern "C" int rgcn_distmult_lse_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                            const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse,
-                                            float *tscore, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return lse_fused<TileBf16>({"distmult_lse_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
                               n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore);
 }
 
-// label smoothing: the four forms again with ssum and cnt behind tscore, four floats per cell of the partials
+// label smoothing: both storages again with ssum and cnt behind tscore, four floats per cell of the partials
 extern "C" int64_t rgcn_distmult_lse_smooth_workspace_bytes(int64_t Q, int64_t n_nodes, int32_t d, int32_t strips, int32_t bf16) {
   return (Q < 0 || n_nodes <= 0 || d <= 0 || strips < 0) ? 0 : strip_layout(Q, n_nodes, d, strips, bf16 != 0, sizeof(float4)).total;
 }
 
 extern "C" int rgcn_distmult_lse_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                             const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                            const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                            const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                            const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse, float *tscore,
                                             float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return lse_fused<TileF32>({"distmult_lse_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace, n_nodes,
-                             d, stream}, lse, tscore, true, ssum, cnt);
+  return lse_fused<TileF32>({"distmult_lse_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
+                             n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore, true, ssum, cnt);
 }
 
 extern "C" int rgcn_distmult_lse_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                              const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                             const int32_t *filt_n, int64_t F, int32_t strips, void *workspace, float *lse, float *tscore,
+                                             const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                             const int32_t *fvals, int64_t K, int32_t strips, void *workspace, float *lse, float *tscore,
                                              float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return lse_fused<TileBf16>({"distmult_lse_smooth_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips, workspace,
-                              n_nodes, d, stream}, lse, tscore, true, ssum, cnt);
-}
-
-extern "C" int rgcn_distmult_lse_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                  const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                  const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                  float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
-                                                  int32_t d, void *stream) {
-  (void)n_rel;
-  return lse_fused<TileF32>({"distmult_lse_smooth_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips, workspace,
-                             n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore, true, ssum, cnt);
-}
-
-extern "C" int rgcn_distmult_lse_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                   const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                   const int64_t *fptr, const int32_t *fvals, int64_t K, int32_t strips, void *workspace,
-                                                   float *lse, float *tscore, float *ssum, int32_t *cnt, int64_t n_nodes, int32_t n_rel,
-                                                   int32_t d, void *stream) {
-  (void)n_rel;
-  return lse_fused<TileBf16>({"distmult_lse_smooth_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, strips,
+  return lse_fused<TileBf16>({"distmult_lse_smooth_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, strips,
                               workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, tscore, true, ssum, cnt);
 }
 
-extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
-  return softmax_grad_workspace_bytes(Q, c_count, d, false);
-}
-
-extern "C" int64_t rgcn_distmult_softmax_grad_bf16_workspace_bytes(int64_t Q, int64_t c_count, int32_t d) {
-  return softmax_grad_workspace_bytes(Q, c_count, d, true);
+extern "C" int64_t rgcn_distmult_softmax_grad_workspace_bytes(int64_t Q, int64_t c_count, int32_t d, int32_t bf16) {
+  return softmax_grad_workspace_bytes(Q, c_count, d, bf16 != 0);
 }
 
 namespace {
 
-// what the list form and the index form of the gradient-cell entry share: a.F fills the chunk's mask from the lists, a.ix.K from the index
+// the gradient cells of both storages, plain and smoothed: a.F fills the chunk's mask from the lists, a.ix.K from the index
 template <class Tile>
 int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, const float *gscale, int32_t per_query, int64_t mean_over, int64_t c_first,
                  int64_t c_count, float *dS, bool smooth = false, const float *keep = nullptr, const float *uni = nullptr) {
@@ -1831,86 +1755,51 @@ int softmax_grad(const StripArgs<typename Tile::elem> &a, const float *lse, cons
 
 extern "C" int rgcn_distmult_softmax_grad_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                               const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                              const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
-                                              int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
-                                              int32_t n_rel, int32_t d, void *stream) {
+                                              const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                              const int32_t *fvals, int64_t K, const float *lse, const float *gscale, int32_t per_query,
+                                              int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                              int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return softmax_grad<TileF32>({"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace, n_nodes, d,
-                       stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
-}
-
-extern "C" int rgcn_distmult_softmax_grad_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                    const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                    const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
-                                                    int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
-                                                    float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return softmax_grad<TileF32>({"distmult_softmax_grad_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0, workspace, n_nodes,
-                       d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
+  return softmax_grad<TileF32>({"distmult_softmax_grad", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace,
+                                n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first,
+                                c_count, dS);
 }
 
 extern "C" int rgcn_distmult_softmax_grad_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
                                                const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                               const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, int32_t per_query,
-                                               int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
-                                               int32_t n_rel, int32_t d, void *stream) {
+                                               const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                               const int32_t *fvals, int64_t K, const float *lse, const float *gscale, int32_t per_query,
+                                               int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                               int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return softmax_grad<TileBf16>({"distmult_softmax_grad_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace,
-                                 n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS);
-}
-
-extern "C" int rgcn_distmult_softmax_grad_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                     const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                     const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
-                                                     int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace,
-                                                     float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return softmax_grad<TileBf16>({"distmult_softmax_grad_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
+  return softmax_grad<TileBf16>({"distmult_softmax_grad_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0,
                                  workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
                                  c_first, c_count, dS);
 }
 
-// label smoothing: the four forms again with keep [1] and uni [Q] behind gscale, the smoothed instantiation of the cell kernel
+// label smoothing: both storages again with keep [1] and uni [Q] behind gscale, the smoothed instantiation of the cell kernel
 extern "C" int rgcn_distmult_softmax_grad_smooth_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
                                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                                     const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
-                                                     const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
-                                                     void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+                                                     const int32_t *filt_n, int64_t F, const int64_t *fkeys, const int64_t *fptr,
+                                                     const int32_t *fvals, int64_t K, const float *lse, const float *gscale,
+                                                     const float *keep, const float *uni, int32_t per_query, int64_t mean_over,
+                                                     int64_t c_first, int64_t c_count, void *workspace, float *dS, int64_t n_nodes,
+                                                     int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
-  return softmax_grad<TileF32>({"distmult_softmax_grad_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0, workspace,
-                                n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS, true, keep, uni);
+  return softmax_grad<TileF32>({"distmult_softmax_grad_smooth", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0,
+                                workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
+                                c_first, c_count, dS, true, keep, uni);
 }
 
-extern "C" int rgcn_distmult_softmax_grad_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                      const float *sbias, const float *pbias, const float *obias, const int32_t *filt_q,
-                                                      const int32_t *filt_n, int64_t F, const float *lse, const float *gscale, const float *keep,
-                                                      const float *uni, int32_t per_query, int64_t mean_over, int64_t c_first, int64_t c_count,
-                                                      void *workspace, float *dS, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+extern "C" int rgcn_distmult_softmax_grad_smooth_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes,
+                                                      const float *rel, const float *sbias, const float *pbias, const float *obias,
+                                                      const int32_t *filt_q, const int32_t *filt_n, int64_t F, const int64_t *fkeys,
+                                                      const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
+                                                      const float *gscale, const float *keep, const float *uni, int32_t per_query,
+                                                      int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
+                                                      int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
   (void)n_rel;
   return softmax_grad<TileBf16>({"distmult_softmax_grad_smooth_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, F, 0,
-                                 workspace, n_nodes, d, stream}, lse, gscale, per_query, mean_over, c_first, c_count, dS, true, keep, uni);
-}
-
-extern "C" int rgcn_distmult_softmax_grad_smooth_index_f32(const int64_t *batch, int64_t Q, int32_t head, const float *nodes, const float *rel,
-                                                           const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                           const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
-                                                           const float *gscale, const float *keep, const float *uni, int32_t per_query,
-                                                           int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
-                                                           int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return softmax_grad<TileF32>({"distmult_softmax_grad_smooth_index", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
-                                workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over, c_first,
-                               c_count, dS, true, keep, uni);
-}
-
-extern "C" int rgcn_distmult_softmax_grad_smooth_index_bf16(const int64_t *batch, int64_t Q, int32_t head, const uint16_t *nodes, const float *rel,
-                                                            const float *sbias, const float *pbias, const float *obias, const int64_t *fkeys,
-                                                            const int64_t *fptr, const int32_t *fvals, int64_t K, const float *lse,
-                                                            const float *gscale, const float *keep, const float *uni, int32_t per_query,
-                                                            int64_t mean_over, int64_t c_first, int64_t c_count, void *workspace, float *dS,
-                                                            int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  (void)n_rel;
-  return softmax_grad<TileBf16>({"distmult_softmax_grad_smooth_index_bf16", batch, Q, head, nodes, rel, sbias, pbias, obias, nullptr, nullptr, 0, 0,
                                  workspace, n_nodes, d, stream, filter_index(fkeys, fptr, fvals, K)}, lse, gscale, per_query, mean_over,
                                  c_first, c_count, dS, true, keep, uni);
 }

@@ -2603,7 +2603,7 @@ def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obi
 
 
 def _index_args(filt, head, N, device, filt_q=None):
-    """the (fkeys, fptr, fvals, K) arguments of an _index entry point from a functional.FilterIndex: the table of the direction `head`
+    """the (fkeys, fptr, fvals, K) arguments of an entry point from a functional.FilterIndex: the table of the direction `head`
     asks for, NULLs for an index without keys.  The index was validated when it was built: nothing is checked per call but that it is
     the index of these tensors."""
     assert filt_q is None, "a FilterIndex or the filter lists, not both"
@@ -2616,6 +2616,19 @@ def _index_args(filt, head, N, device, filt_q=None):
 def _list_args(filt_q, filt_n, F):
     """the (filt_q, filt_n) arguments of a list entry point: NULLs for no lists or empty ones (F = 0)"""
     return (_dp(filt_q), _dp(filt_n)) if F else (None, None)
+
+
+def _filter_call_args(filt_q, filt_n, F, filt, head, N, dev):
+    """the filter block (filt_q, filt_n, F, fkeys, fptr, fvals, K) of a filtered entry point: the filter -- the positive cells of the
+    BCE roles -- as int32 device lists, as a functional.FilterIndex, or neither"""
+    if filt is not None:
+        return (None, None, 0) + _index_args(filt, head, N, dev, filt_q)
+    return _list_args(filt_q, filt_n, F) + (F, None, None, None, 0)
+
+
+def _filter_tag(tag, filt, bf16):
+    """the profile tag of a filtered call: tag[_index][_bf16]"""
+    return tag + ("_index" if filt is not None else "") + ("_bf16" if bf16 else "")
 
 
 def filter_mask_index(batch, head, filt, keep_target=False, c_first=0, c_count=None, out=None):
@@ -2673,24 +2686,14 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    if filt is not None:
-        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
-        with _on(dev), _timed("rank_fused_index_bf16" if bf16 else "rank_fused_index"):
-            if bf16:
-                _check(lib().rgcn_distmult_rank_fused_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
-                                                                 _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_index_bf16")
-            else:
-                _check(lib().rgcn_distmult_rank_fused_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
-                                                                _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_index")
-    else:
-        fq, fn = _list_args(filt_q, filt_n, F)
-        with _on(dev), _timed("rank_fused_bf16" if bf16 else "rank_fused"):
-            if bf16:
-                _check(lib().rgcn_distmult_rank_fused_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(greater),
-                                                           _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_bf16")
-            else:
-                _check(lib().rgcn_distmult_rank_fused_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(greater),
-                                                          _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused")
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    with _on(dev), _timed(_filter_tag("rank_fused", filt, bf16)):
+        if bf16:
+            _check(lib().rgcn_distmult_rank_fused_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
+                                                       _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_bf16")
+        else:
+            _check(lib().rgcn_distmult_rank_fused_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
+                                                      _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused")
     return greater, ties, tscore
 
 
@@ -2732,24 +2735,14 @@ def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt
     scores = torch.empty(Q, k, device=dev, dtype=torch.float32)
     ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    if filt is not None:
-        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
-        with _on(dev), _timed("topk_fused_index_bf16" if bf16 else "topk_fused_index"):
-            if bf16:
-                _check(lib().rgcn_distmult_topk_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
-                                                           _dp(scores), N, R, d, st), "distmult_topk_index_bf16")
-            else:
-                _check(lib().rgcn_distmult_topk_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
-                                                          _dp(scores), N, R, d, st), "distmult_topk_index")
-    else:
-        fq, fn = _list_args(filt_q, filt_n, F)
-        with _on(dev), _timed("topk_fused_bf16" if bf16 else "topk_fused"):
-            if bf16:
-                _check(lib().rgcn_distmult_topk_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, k, strips, _dp(ws), _dp(ids), _dp(scores),
-                                                     N, R, d, st), "distmult_topk_bf16")
-            else:
-                _check(lib().rgcn_distmult_topk_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, k, strips, _dp(ws), _dp(ids), _dp(scores),
-                                                    N, R, d, st), "distmult_topk")
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    with _on(dev), _timed(_filter_tag("topk_fused", filt, bf16)):
+        if bf16:
+            _check(lib().rgcn_distmult_topk_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
+                                                 _dp(scores), N, R, d, st), "distmult_topk_bf16")
+        else:
+            _check(lib().rgcn_distmult_topk_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
+                                                _dp(scores), N, R, d, st), "distmult_topk")
     return ids, scores
 
 
@@ -2798,24 +2791,14 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     tscore = torch.empty(Q, device=dev, dtype=torch.float32)
     ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    if filt is not None:
-        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
-        with _on(dev), _timed("lse_fused_index_bf16" if bf16 else "lse_fused_index"):
-            if bf16:
-                _check(lib().rgcn_distmult_lse_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                          N, R, d, st), "distmult_lse_index_bf16")
-            else:
-                _check(lib().rgcn_distmult_lse_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                         N, R, d, st), "distmult_lse_index")
-    else:
-        fq, fn = _list_args(filt_q, filt_n, F)
-        with _on(dev), _timed("lse_fused_bf16" if bf16 else "lse_fused"):
-            if bf16:
-                _check(lib().rgcn_distmult_lse_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                    N, R, d, st), "distmult_lse_bf16")
-            else:
-                _check(lib().rgcn_distmult_lse_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                   N, R, d, st), "distmult_lse")
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    with _on(dev), _timed(_filter_tag("lse_fused", filt, bf16)):
+        if bf16:
+            _check(lib().rgcn_distmult_lse_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                                N, R, d, st), "distmult_lse_bf16")
+        else:
+            _check(lib().rgcn_distmult_lse_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
+                                               N, R, d, st), "distmult_lse")
     return lse, tscore
 
 
@@ -2841,33 +2824,21 @@ def distmult_lse_smooth(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     cnt = torch.empty(Q, device=dev, dtype=torch.int32)
     ws = torch.empty(max(lse_smooth_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    if filt is not None:
-        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
-        with _on(dev), _timed("lse_smooth_index_bf16" if bf16 else "lse_smooth_index"):
-            if bf16:
-                _check(lib().rgcn_distmult_lse_smooth_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
-                                                                 _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_index_bf16")
-            else:
-                _check(lib().rgcn_distmult_lse_smooth_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
-                                                                _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_index")
-    else:
-        fq, fn = _list_args(filt_q, filt_n, F)
-        with _on(dev), _timed("lse_smooth_bf16" if bf16 else "lse_smooth"):
-            if bf16:
-                _check(lib().rgcn_distmult_lse_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                           _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_bf16")
-            else:
-                _check(lib().rgcn_distmult_lse_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                          _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth")
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    with _on(dev), _timed(_filter_tag("lse_smooth", filt, bf16)):
+        if bf16:
+            _check(lib().rgcn_distmult_lse_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
+                                                       _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_bf16")
+        else:
+            _check(lib().rgcn_distmult_lse_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
+                                                      _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth")
     return lse, tscore, ssum, cnt
 
 
 def softmax_grad_workspace_bytes(Q, c_count, d, bf16=False):
     """bytes of a gradient-cell call's workspace (query vectors, query-side bias terms, the chunk's [Q][ceil(c_count / 32)] filter mask);
     needs no device; 0 for arguments the call refuses"""
-    if bf16:
-        return int(lib().rgcn_distmult_softmax_grad_bf16_workspace_bytes(Q, c_count, d))
-    return int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d))
+    return int(lib().rgcn_distmult_softmax_grad_workspace_bytes(Q, c_count, d, 1 if bf16 else 0))
 
 
 def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, filt_n, lse, gscale, mean_over, c_first, c_count, out=None,
@@ -2899,48 +2870,26 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     ws = torch.empty(max(softmax_grad_workspace_bytes(Q, c_count, d, bf16), 16), device=dev, dtype=torch.uint8)
     per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    if filt is not None:
-        fk, fp, fv, K = _index_args(filt, head, N, dev, filt_q)
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    with _on(dev), _timed(_filter_tag("softmax_grad_smooth" if smooth else "softmax_grad", filt, bf16)):
         if smooth:
-            with _on(dev), _timed("softmax_grad_smooth_index_bf16" if bf16 else "softmax_grad_smooth_index"):
-                if bf16:
-                    _check(lib().rgcn_distmult_softmax_grad_smooth_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                                              _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws),
-                                                                              _dp(dS), N, R, d, st), "distmult_softmax_grad_smooth_index_bf16")
-                else:
-                    _check(lib().rgcn_distmult_softmax_grad_smooth_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                                             _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws),
-                                                                             _dp(dS), N, R, d, st), "distmult_softmax_grad_smooth_index")
-            return dS
-        with _on(dev), _timed("softmax_grad_index_bf16" if bf16 else "softmax_grad_index"):
             if bf16:
-                _check(lib().rgcn_distmult_softmax_grad_index_bf16(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale), per_query,
-                                                                   over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
-                       "distmult_softmax_grad_index_bf16")
+                _check(lib().rgcn_distmult_softmax_grad_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                                    _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS),
+                                                                    N, R, d, st), "distmult_softmax_grad_smooth_bf16")
             else:
-                _check(lib().rgcn_distmult_softmax_grad_index_f32(b, Q, h, nd, rl, sb, pb, ob, fk, fp, fv, K, _dp(lse), _dp(gscale), per_query,
-                                                                  over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
-                       "distmult_softmax_grad_index")
-    else:
-        fq, fn = _list_args(filt_q, filt_n, F)
-        if smooth:
-            with _on(dev), _timed("softmax_grad_smooth_bf16" if bf16 else "softmax_grad_smooth"):
-                if bf16:
-                    _check(lib().rgcn_distmult_softmax_grad_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), _dp(keep),
-                                                                        _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d,
-                                                                        st), "distmult_softmax_grad_smooth_bf16")
-                else:
-                    _check(lib().rgcn_distmult_softmax_grad_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), _dp(keep),
-                                                                       _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d,
-                                                                       st), "distmult_softmax_grad_smooth")
-            return dS
-        with _on(dev), _timed("softmax_grad_bf16" if bf16 else "softmax_grad"):
+                _check(lib().rgcn_distmult_softmax_grad_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                                   _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS),
+                                                                   N, R, d, st), "distmult_softmax_grad_smooth")
+        else:
             if bf16:
-                _check(lib().rgcn_distmult_softmax_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,
-                                                             c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_softmax_grad_bf16")
+                _check(lib().rgcn_distmult_softmax_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                             per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
+                       "distmult_softmax_grad_bf16")
             else:
-                _check(lib().rgcn_distmult_softmax_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, _dp(lse), _dp(gscale), per_query, over,
-                                                            c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_softmax_grad")
+                _check(lib().rgcn_distmult_softmax_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
+                                                            per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
+                       "distmult_softmax_grad")
     return dS
 
 
@@ -2955,14 +2904,6 @@ def bce_grad_workspace_bytes(Q, c_count, d, bf16=False):
     """bytes of a BCE gradient-cell call's workspace (query vectors, query-side bias terms, the chunk's [Q][ceil(c_count / 32)] label
     mask); needs no device; 0 for arguments the call refuses"""
     return int(lib().rgcn_distmult_bce_grad_workspace_bytes(Q, c_count, d, 1 if bf16 else 0))
-
-
-def _label_args(lab_q, lab_n, F, labels, head, N, dev):
-    """the (filt_q, filt_n, F, fkeys, fptr, fvals, K) arguments of a BCE entry point: the positive cells as lists, as a
-    functional.FilterIndex, or neither (the targets alone)"""
-    if labels is not None:
-        return (None, None, 0) + _index_args(labels, head, N, dev, lab_q)
-    return _list_args(lab_q, lab_n, F) + (F, None, None, None, 0)
 
 
 def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, lab_q=None, lab_n=None, strips=0, checked=False,
@@ -2982,7 +2923,7 @@ def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=Non
     npos = torch.empty(Q, device=dev, dtype=torch.int32)
     ws = torch.empty(max(bce_sums_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(lab_q, lab_n, F, labels, head, N, dev)
     with _on(dev), _timed("bce_sums_bf16" if bf16 else "bce_sums"):
         if bf16:
             _check(lib().rgcn_distmult_bce_sums_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps),
@@ -3016,7 +2957,7 @@ def distmult_bce_grad(batch, head, nodes, rel, sbias, pbias, obias, lab_q, lab_n
     # {keep, uni} as host floats: the library reads them before the launch and hands them to the kernel as arguments
     smooth = (ctypes.c_float * 2)(1.0 - label_smoothing, label_smoothing / N) if label_smoothing else None
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
-    fq, fn, F, fk, fp, fv, K = _label_args(lab_q, lab_n, F, labels, head, N, dev)
+    fq, fn, F, fk, fp, fv, K = _filter_call_args(lab_q, lab_n, F, labels, head, N, dev)
     sm = None if smooth is None else ctypes.addressof(smooth)
     with _on(dev), _timed("bce_grad_bf16" if bf16 else "bce_grad"):
         if bf16:
