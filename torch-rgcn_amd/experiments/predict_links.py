@@ -43,6 +43,28 @@ from utils.misc import evaluate, generate_true_dict, negative_sampling, select_s
 OPTIMISERS = {"adam": torch.optim.Adam, "adamw": torch.optim.AdamW, "adagrad": torch.optim.Adagrad, "sgd": torch.optim.SGD}
 
 
+def step_loss(model, graph, batch_idx, train_lbl, objective="negative-sampling", train_filter=None, loss_kw=None, decoder_l2_penalty=0.0):
+    """The scalar loss of one training step of `model` (LinkPredictor / CompressionRelationPredictor) on the message graph `graph`.
+    objective "negative-sampling": batch_idx holds the positives and their corrupted copies, train_lbl their 1 / 0 labels -- the mean BCE.
+    "1-n" / "1-n-bce": batch_idx holds the positives alone (train_lbl is not read) -- half the tail loss plus half the head loss over ALL
+    entities; train_filter: the FilterIndex of the cells left out (1-n; None: unfiltered) or of the positive labels (1-n-bce);
+    loss_kw: bf16_backward / label_smoothing of both terms.  decoder_l2_penalty times model.compute_penalty is added in every objective."""
+    if objective not in ("negative-sampling", "1-n", "1-n-bce"):
+        raise NotImplementedError(f"'{objective}' training objective has not been implemented!")
+    if objective in ("1-n", "1-n-bce"):   # half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
+        x = model.encode(graph)
+        decoder_ = model.scoring_function
+        loss_kw = loss_kw or {}
+        if objective == "1-n-bce":        # the index holds the positive labels
+            term = lambda head: decoder_.bce_loss(batch_idx, x, head=head, labels=train_filter, **loss_kw)  # noqa: E731
+        else:                             # the index (if any) holds the cells left out
+            term = lambda head: decoder_.softmax_loss(batch_idx, x, head=head, filt=train_filter, **loss_kw)  # noqa: E731
+        loss = 0.5 * (term(False) + term(True))
+        return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
+    predictions, penalty = model(graph, batch_idx)
+    return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
+
+
 def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=None, hipgraph=None, fused_eval=None, device_filter=False):
     """-> (loss per epoch, {"mrr", "hits@1", "hits@3", "hits@10"} of the final evaluation).
     The training step (per-step graph build, encoder, decoder, loss, backward, optimiser) is captured once in a hipGraph and replayed
@@ -175,22 +197,9 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
                                torch.zeros(graph_batch_size * neg_sample_rate, device=device)])
         return batch_idx, train_lbl
 
-    def step_loss(graph, batch_idx, train_lbl):
-        if one_to_n:      # 1-N softmax or BCE: half the tail loss, half the head loss (static shapes, filtered or not: the captured step works)
-            x = model.encode(graph)
-            decoder_ = model.scoring_function
-            if k_vs_all:  # the index holds the positive labels
-                term = lambda head: decoder_.bce_loss(batch_idx, x, head=head, labels=train_filter, **loss_kw)  # noqa: E731
-            else:         # the index (if any) holds the cells left out
-                term = lambda head: decoder_.softmax_loss(batch_idx, x, head=head, filt=train_filter, **loss_kw)  # noqa: E731
-            loss = 0.5 * (term(False) + term(True))
-            return loss + decoder_l2_penalty * model.compute_penalty(batch_idx, x)
-        predictions, penalty = model(graph, batch_idx)
-        return bce_with_logits(predictions, train_lbl) + decoder_l2_penalty * penalty
-
     def train_step(graph, batch_idx, train_lbl):
         optimiser.zero_grad(set_to_none=False)
-        loss = step_loss(graph, batch_idx, train_lbl)
+        loss = step_loss(model, graph, batch_idx, train_lbl, objective, train_filter, loss_kw, decoder_l2_penalty)
         loss.backward(gradient=unit_gradient(loss.device))      # (no ones_like() fill per step; MaskedCrossEntropy skips the multiplication)
         optimiser.step()
         return loss
@@ -245,7 +254,7 @@ def run(cfg, data_dir=None, epochs=None, quiet=False, max_test=None, synthetic=N
         else:
             optimiser.zero_grad()
             graph, batch_idx, train_lbl = sample_inputs()
-            loss = step_loss(graph, batch_idx, train_lbl)
+            loss = step_loss(model, graph, batch_idx, train_lbl, objective, train_filter, loss_kw, decoder_l2_penalty)
             t2 = time.time()
             loss.backward(gradient=unit_gradient(loss.device))
             optimiser.step()
