@@ -24,7 +24,7 @@ Autograd function -> tests (each differentiable input frozen at least once):
     _DiagMPBF16                test_bf16_diagonal_frozen
     _BlockSelfMPBF16           test_bf16_lp_block_self_frozen
     _FeaturelessBasisMPBF16    test_bf16_featureless_basis_tile_frozen
-    _DistMultScore             test_distmult_frozen, test_distmult_all_frozen_scores_only
+    _TripleScore               test_distmult_frozen, test_distmult_all_frozen_scores_only
     (wrapper flags no layer reaches: test_wrappers_without_bias_gradient)
 Out of scope: _ShardedRelationalMP (needs a process group), _MaskedCE and _BCEWithLogits (one differentiable input), the two-layer
 ReLU-token chain (its hidden activation is not integer-valued)."""

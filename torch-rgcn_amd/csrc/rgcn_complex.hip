@@ -14,7 +14,7 @@
 // LDS-table route nor of its atomic scatter.
 #include <cstdlib>
 
-#include "rgcn_device.h"      // HIP_TRY, f32x4, WG, zero_async, the bf16 widen / round helpers
+#include "rgcn_device.h"      // HIP_TRY, f32x4, WG, zero_async, aligned, the bf16 widen / round helpers
 
 namespace {
 
@@ -207,8 +207,6 @@ __global__ __launch_bounds__(WG) void complex_bwd_rel_kernel(
     }
   }
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // the argument rule every entry shares: real halves | imaginary halves
 inline bool odd_width(const char *name, int32_t d) {

@@ -31,6 +31,9 @@ namespace {
 constexpr int WG = 256;            // 4 wavefronts
 constexpr int LDS_TILE_BYTES = 64 * 1024;
 
+// host: p is a multiple of a (a power of two) -- how the launchers pick a kernel's vector form
+inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 // ------------------------------------------------------------------ spmm
 // One WAVE per destination tile (a workgroup = 4 independent waves = 4 tiles).  The wave is the
 // only writer of its tile's rows, so the LDS accumulation is a plain read-modify-write

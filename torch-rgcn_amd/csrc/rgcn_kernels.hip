@@ -2038,32 +2038,46 @@ extern "C" int rgcn_diag_wgrad_bf16(const uint16_t *X, const uint16_t *G, float 
   return RGCN_OK;
 }
 
-extern "C" int rgcn_distmult_fwd_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
-                                     const float *sbias, const float *pbias, const float *obias, float *scores,
-                                     int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
-                                     int32_t *ranks, void *stream) {
+// ------------------------------------------------------------------ DistMult on scored triples: one launcher per role, BF = a bf16
+// entity table (the relation table, the biases, the scores and every other gradient stay fp32).  The extern "C" entries
+// below pass their own names, as rgcn_complex.hip's do.  Reference lines: layers.py:86-98 (forward) and its autograd dual.
+namespace {
+
+inline bool some_but_not_all(const void *a, const void *b, const void *c) { return (a != nullptr) != (b != nullptr) || (a != nullptr) != (c != nullptr); }
+
+template <bool BF>
+int distmult_fwd(const char *name, const int64_t *triples, int64_t T, const void *nodes, const float *rel, const float *sbias,
+                 const float *pbias, const float *obias, float *scores, int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag,
+                 int32_t *rank_counts, int32_t *ranks, void *stream) {
   if (T < 0 || d <= 0 || (T && (!triples || !nodes || !rel || !scores)) || (rank_counts != nullptr) != (ranks != nullptr) ||
-      (rank_counts && (n_nodes <= 0 || 2 * T > INT32_MAX))) { rgcn_set_error("distmult_fwd: bad argument"); return RGCN_EINVAL; }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) { rgcn_set_error("distmult_fwd: biases must be all set or all NULL"); return RGCN_EINVAL; }
-  if (err_flag) HIP_TRY(zero_async(err_flag, sizeof(int32_t), (hipStream_t)stream));
-  if (rank_counts) HIP_TRY(zero_async(rank_counts, (size_t)(2 * n_nodes + 3) * sizeof(int32_t), (hipStream_t)stream));
+      (rank_counts && (n_nodes <= 0 || 2 * T > INT32_MAX))) { rgcn_set_error("%s: bad argument", name); return RGCN_EINVAL; }
+  if (some_but_not_all(sbias, pbias, obias)) { rgcn_set_error("%s: biases must be all set or all NULL", name); return RGCN_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  if (err_flag) HIP_TRY(zero_async(err_flag, sizeof(int32_t), st));
+  if (rank_counts) HIP_TRY(zero_async(rank_counts, (size_t)(2 * n_nodes + 3) * sizeof(int32_t), st));
   if (T == 0) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((T + 3) / 4, 256 * 32);
-  hipLaunchKernelGGL(distmult_fwd_kernel<false>, dim3(gx), dim3(WG), 0, (hipStream_t)stream,
-                     reinterpret_cast<const long long *>(triples), (long long)T, nodes, rel, sbias, pbias, obias,
-                     scores, d, (long long)n_nodes, n_rel, err_flag, rank_counts, ranks,
-                     (int)((d & 3) == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(rel)) & 15) == 0));
+  // quarter rows: 16 bytes of an fp32 entity table, 8 of a bf16 one, 16 of the relation table
+  const int vec = (d & 3) == 0 && aligned(nodes, BF ? 8 : 16) && aligned(rel, 16);
+  hipLaunchKernelGGL(distmult_fwd_kernel<BF>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples), (long long)T,
+                     static_cast<const float *>(nodes), rel, sbias, pbias, obias, scores, d, (long long)n_nodes, n_rel, err_flag,
+                     rank_counts, ranks, vec);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
 
-extern "C" int rgcn_distmult_bwd_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
-                                     const float *gs, float *dnodes, float *drel, float *dsbias, float *dpbias,
-                                     float *dobias, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  if (T < 0 || d <= 0 || !drel || (T && (!triples || !nodes || !rel || !gs))) { rgcn_set_error("distmult_bwd: bad argument"); return RGCN_EINVAL; }
+// Relation (and bias) gradients from predicate-sorted triples.  dnodes: fp32, optional, for the fp32 entry alone -- set: the kernel also
+// scatters the entity gradients with atomics; NULL: they come from distmult_bwd_nodes (no atomics).  The two entries do not check the same
+// things: the bf16 one also refuses n_nodes < 0, n_rel <= 0 and bias gradients that are neither all set nor all NULL.
+template <bool BF>
+int distmult_bwd(const char *name, const int64_t *triples, int64_t T, const void *nodes, const float *rel, const float *gs, float *dnodes,
+                 float *drel, float *dsbias, float *dpbias, float *dobias, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  if (T < 0 || d <= 0 || (BF && (n_nodes < 0 || n_rel <= 0)) || !drel || (T && (!triples || !nodes || !rel || !gs))) {
+    rgcn_set_error("%s: bad argument", name);
+    return RGCN_EINVAL;
+  }
+  if (BF && some_but_not_all(dsbias, dpbias, dobias)) { rgcn_set_error("%s: bias gradients must be all set or all NULL", name); return RGCN_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  // dnodes == NULL: the entity gradients are computed by rgcn_distmult_bwd_nodes_f32 (no atomics); this call then yields the
-  // relation (and bias) gradients only
   if (dnodes) HIP_TRY(zero_async(dnodes, (size_t)n_nodes * d * sizeof(float), st));
   HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
   if (dsbias) {
@@ -2073,137 +2087,119 @@ extern "C" int rgcn_distmult_bwd_f32(const int64_t *triples, int64_t T, const fl
   }
   if (T == 0) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((T + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(distmult_bwd_kernel<false>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples),
-                     (long long)T, nodes, rel, gs, dnodes, drel, dsbias, dpbias, dobias, d, (long long)n_nodes, n_rel, dnodes ? 0 : 1);
+  hipLaunchKernelGGL(distmult_bwd_kernel<BF>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples), (long long)T,
+                     static_cast<const float *>(nodes), rel, gs, dnodes, drel, dsbias, dpbias, dobias, d, (long long)n_nodes, n_rel,
+                     dnodes ? 0 : 1);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
 
-extern "C" int rgcn_distmult_bwd_all_supported(int32_t n_rel, int32_t d) { return n_rel > 0 && d > 0 && (int64_t)n_rel * (d + 1) <= 4096; }
+// the vector form of the CSR walks: fp32 asks d % 4 == 0 alone; bf16 also 8 bytes of the entity table and of dnodes, 16 of the relation
+// table (quarter rows, as distmult_fwd)
+template <bool BF>
+bool walk_vec(int32_t d, const void *nodes, const float *rel, const void *dnodes) {
+  return d % 4 == 0 && (!BF || (aligned(nodes, 8) && aligned(dnodes, 8) && aligned(rel, 16)));
+}
 
-extern "C" int rgcn_distmult_bwd_all_f32(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const float *nodes,
-                                         const float *rel, float *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
-                                         int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || !drel || n_nodes < 0 || d <= 0 || n_rel <= 0) { rgcn_set_error("distmult_bwd_all: bad argument"); return RGCN_EINVAL; }
-  if ((dsbias != nullptr) != (dpbias != nullptr) || (dsbias != nullptr) != (dobias != nullptr)) { rgcn_set_error("distmult_bwd_all: bias gradients must be all set or all NULL"); return RGCN_EINVAL; }
-  if (!rgcn_distmult_bwd_all_supported(n_rel, d)) { rgcn_set_error("distmult_bwd_all: n_rel (d + 1) = %lld floats do not fit the LDS table (4096)", (long long)n_rel * (d + 1)); return RGCN_EUNSUPPORTED; }
+// Every gradient from the two CSRs of the scored triples, the relation table in LDS
+template <bool BF>
+int distmult_bwd_all(const char *name, const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const void *nodes,
+                     const float *rel, void *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias, int64_t n_nodes,
+                     int32_t n_rel, int32_t d, void *stream) {
+  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || !drel || n_nodes < 0 || d <= 0 || n_rel <= 0) { rgcn_set_error("%s: bad argument", name); return RGCN_EINVAL; }
+  if (some_but_not_all(dsbias, dpbias, dobias)) { rgcn_set_error("%s: bias gradients must be all set or all NULL", name); return RGCN_EINVAL; }
+  if (!rgcn_distmult_bwd_all_supported(n_rel, d)) { rgcn_set_error("%s: n_rel (d + 1) = %lld floats do not fit the LDS table (4096)", name, (long long)n_rel * (d + 1)); return RGCN_EUNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
   if (dpbias) HIP_TRY(zero_async(dpbias, (size_t)n_rel * sizeof(float), st));
   if (!n_nodes) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 1024);        // (29 KB of LDS per workgroup at WN18's size: up to 5 per CU)
   const size_t lds = ((size_t)n_rel * 4 * ((d + 3) / 4) + n_rel) * sizeof(double);
-  const unsigned gx2 = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 256 * 32);
-  const int4 *en = reinterpret_cast<const int4 *>(entries);
-  // two launches (object side without LDS at full occupancy, then subject side + relation table): the one-launch form was measured slower
-  auto go = [&](auto k2, auto k1) {
-    hipLaunchKernelGGL(k2, dim3(gx2), dim3(WG), 0, st, rowptr_s, rowptr_o, en, nodes, rel, dnodes, drel, dsbias, dpbias, dobias,
-                       (long long)n_nodes, n_rel, d);
-    hipLaunchKernelGGL(k1, dim3(gx), dim3(WG), lds, st, rowptr_s, rowptr_o, en, nodes, rel, dnodes, drel, dsbias, dpbias, dobias,
+  auto go = [&](auto k, unsigned grid, size_t shared) {
+    hipLaunchKernelGGL(k, dim3(grid), dim3(WG), shared, st, rowptr_s, rowptr_o, reinterpret_cast<const int4 *>(entries),
+                       static_cast<const float *>(nodes), rel, static_cast<float *>(dnodes), drel, dsbias, dpbias, dobias,
                        (long long)n_nodes, n_rel, d);
   };
-  if (d % 4 == 0) go(distmult_bwd_all_kernel<2, true, true>, distmult_bwd_all_kernel<1, true, true>);
-  else go(distmult_bwd_all_kernel<2, false, true>, distmult_bwd_all_kernel<1, false, true>);
+  const bool vec = walk_vec<BF>(d, nodes, rel, dnodes);
+  if constexpr (BF) {                              // ONE walk: both sides meet in registers, dnodes is rounded once
+    if (vec) go(distmult_bwd_all_kernel<3, true, true, true>, gx, lds);
+    else go(distmult_bwd_all_kernel<3, false, true, true>, gx, lds);
+  } else {
+    // two launches (object side without LDS at full occupancy, then subject side + relation table): the one-launch form was measured slower
+    const unsigned gx2 = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 256 * 32);
+    if (vec) { go(distmult_bwd_all_kernel<2, true, true>, gx2, 0); go(distmult_bwd_all_kernel<1, true, true>, gx, lds); }
+    else { go(distmult_bwd_all_kernel<2, false, true>, gx2, 0); go(distmult_bwd_all_kernel<1, false, true>, gx, lds); }
+  }
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
 
-extern "C" int rgcn_distmult_bwd_nodes_f32(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const float *nodes,
-                                           const float *rel, float *dnodes, int64_t n_nodes, int32_t d, void *stream) {
-  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || n_nodes < 0 || d <= 0) { rgcn_set_error("distmult_bwd_nodes: bad argument"); return RGCN_EINVAL; }
+// Entity gradients alone: one wave per entity over the two CSRs, no atomics, every row written
+template <bool BF>
+int distmult_bwd_nodes(const char *name, const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const void *nodes,
+                       const float *rel, void *dnodes, int64_t n_nodes, int32_t d, void *stream) {
+  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || n_nodes < 0 || d <= 0) { rgcn_set_error("%s: bad argument", name); return RGCN_EINVAL; }
   if (!n_nodes) return RGCN_OK;
   const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 256 * 32);
-  const int4 *en = reinterpret_cast<const int4 *>(entries);
   auto go = [&](auto k) {
-    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), 0, (hipStream_t)stream, rowptr_s, rowptr_o, en, nodes, rel, dnodes, (float *)nullptr,
-                       (float *)nullptr, (float *)nullptr, (float *)nullptr, (long long)n_nodes, 0, d);
+    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), 0, (hipStream_t)stream, rowptr_s, rowptr_o, reinterpret_cast<const int4 *>(entries),
+                       static_cast<const float *>(nodes), rel, static_cast<float *>(dnodes), (float *)nullptr, (float *)nullptr,
+                       (float *)nullptr, (float *)nullptr, (long long)n_nodes, 0, d);
   };
-  if (d % 4 == 0) go(distmult_bwd_all_kernel<3, true, false>);
-  else go(distmult_bwd_all_kernel<3, false, false>);
+  if (walk_vec<BF>(d, nodes, rel, dnodes)) go(distmult_bwd_all_kernel<3, true, false, BF>);
+  else go(distmult_bwd_all_kernel<3, false, false, BF>);
   HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
 
-// ------------------------------------------------------------------ DistMult on a bf16 entity table
-// reference lines as their fp32 twins above: layers.py:86-98 (forward) and its autograd dual
+}  // namespace
+
+extern "C" int rgcn_distmult_bwd_all_supported(int32_t n_rel, int32_t d) { return n_rel > 0 && d > 0 && (int64_t)n_rel * (d + 1) <= 4096; }
+
+extern "C" int rgcn_distmult_fwd_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
+                                     const float *sbias, const float *pbias, const float *obias, float *scores,
+                                     int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
+                                     int32_t *ranks, void *stream) {
+  return distmult_fwd<false>("distmult_fwd", triples, T, nodes, rel, sbias, pbias, obias, scores, n_nodes, n_rel, d, err_flag, rank_counts, ranks, stream);
+}
+
 extern "C" int rgcn_distmult_fwd_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
                                       const float *sbias, const float *pbias, const float *obias, float *scores,
                                       int64_t n_nodes, int32_t n_rel, int32_t d, int32_t *err_flag, int32_t *rank_counts,
                                       int32_t *ranks, void *stream) {
-  if (T < 0 || d <= 0 || (T && (!triples || !nodes || !rel || !scores)) || (rank_counts != nullptr) != (ranks != nullptr) ||
-      (rank_counts && (n_nodes <= 0 || 2 * T > INT32_MAX))) { rgcn_set_error("distmult_fwd_bf16: bad argument"); return RGCN_EINVAL; }
-  if ((sbias != nullptr) != (pbias != nullptr) || (sbias != nullptr) != (obias != nullptr)) { rgcn_set_error("distmult_fwd_bf16: biases must be all set or all NULL"); return RGCN_EINVAL; }
-  if (err_flag) HIP_TRY(zero_async(err_flag, sizeof(int32_t), (hipStream_t)stream));
-  if (rank_counts) HIP_TRY(zero_async(rank_counts, (size_t)(2 * n_nodes + 3) * sizeof(int32_t), (hipStream_t)stream));
-  if (T == 0) return RGCN_OK;
-  const unsigned gx = (unsigned)std::min<int64_t>((T + 3) / 4, 256 * 32);
-  // quarter rows: 8 bytes of the entity table, 16 of the relation table
-  const int vec = (d & 3) == 0 && (reinterpret_cast<uintptr_t>(nodes) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0;
-  hipLaunchKernelGGL(distmult_fwd_kernel<true>, dim3(gx), dim3(WG), 0, (hipStream_t)stream,
-                     reinterpret_cast<const long long *>(triples), (long long)T, reinterpret_cast<const float *>(nodes), rel, sbias, pbias, obias,
-                     scores, d, (long long)n_nodes, n_rel, err_flag, rank_counts, ranks, vec);
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
+  return distmult_fwd<true>("distmult_fwd_bf16", triples, T, nodes, rel, sbias, pbias, obias, scores, n_nodes, n_rel, d, err_flag, rank_counts, ranks, stream);
 }
 
-extern "C" int rgcn_distmult_bwd_all_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
-                                          const float *rel, uint16_t *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
-                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || !drel || n_nodes < 0 || d <= 0 || n_rel <= 0) { rgcn_set_error("distmult_bwd_all_bf16: bad argument"); return RGCN_EINVAL; }
-  if ((dsbias != nullptr) != (dpbias != nullptr) || (dsbias != nullptr) != (dobias != nullptr)) { rgcn_set_error("distmult_bwd_all_bf16: bias gradients must be all set or all NULL"); return RGCN_EINVAL; }
-  if (!rgcn_distmult_bwd_all_supported(n_rel, d)) { rgcn_set_error("distmult_bwd_all_bf16: n_rel (d + 1) = %lld floats do not fit the LDS table (4096)", (long long)n_rel * (d + 1)); return RGCN_EUNSUPPORTED; }
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
-  if (dpbias) HIP_TRY(zero_async(dpbias, (size_t)n_rel * sizeof(float), st));
-  if (!n_nodes) return RGCN_OK;
-  const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 1024);
-  const size_t lds = ((size_t)n_rel * 4 * ((d + 3) / 4) + n_rel) * sizeof(double);
-  const int4 *en = reinterpret_cast<const int4 *>(entries);
-  auto go = [&](auto k) {
-    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), lds, st, rowptr_s, rowptr_o, en, reinterpret_cast<const float *>(nodes), rel,
-                       reinterpret_cast<float *>(dnodes), drel, dsbias, dpbias, dobias, (long long)n_nodes, n_rel, d);
-  };
-  // quarter rows: 8 bytes of the entity table and of dnodes, 16 of the relation table (as rgcn_distmult_fwd_bf16)
-  if (d % 4 == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(dnodes)) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0)
-    go(distmult_bwd_all_kernel<3, true, true, true>);
-  else go(distmult_bwd_all_kernel<3, false, true, true>);
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
-}
-
-extern "C" int rgcn_distmult_bwd_nodes_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
-                                            const float *rel, uint16_t *dnodes, int64_t n_nodes, int32_t d, void *stream) {
-  if (!rowptr_s || !rowptr_o || !nodes || !rel || !dnodes || n_nodes < 0 || d <= 0) { rgcn_set_error("distmult_bwd_nodes_bf16: bad argument"); return RGCN_EINVAL; }
-  if (!n_nodes) return RGCN_OK;
-  const unsigned gx = (unsigned)std::min<int64_t>((n_nodes + 3) / 4, 256 * 32);
-  const int4 *en = reinterpret_cast<const int4 *>(entries);
-  auto go = [&](auto k) {
-    hipLaunchKernelGGL(k, dim3(gx), dim3(WG), 0, (hipStream_t)stream, rowptr_s, rowptr_o, en, reinterpret_cast<const float *>(nodes), rel,
-                       reinterpret_cast<float *>(dnodes), (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (long long)n_nodes, 0, d);
-  };
-  if (d % 4 == 0 && ((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(dnodes)) & 7) == 0 && (reinterpret_cast<uintptr_t>(rel) & 15) == 0)
-    go(distmult_bwd_all_kernel<3, true, false, true>);
-  else go(distmult_bwd_all_kernel<3, false, false, true>);
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
+extern "C" int rgcn_distmult_bwd_f32(const int64_t *triples, int64_t T, const float *nodes, const float *rel,
+                                     const float *gs, float *dnodes, float *drel, float *dsbias, float *dpbias,
+                                     float *dobias, int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  return distmult_bwd<false>("distmult_bwd", triples, T, nodes, rel, gs, dnodes, drel, dsbias, dpbias, dobias, n_nodes, n_rel, d, stream);
 }
 
 extern "C" int rgcn_distmult_bwd_rel_bf16(const int64_t *triples, int64_t T, const uint16_t *nodes, const float *rel,
                                           const float *gs, float *drel, float *dsbias, float *dpbias, float *dobias,
                                           int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
-  if (T < 0 || d <= 0 || n_nodes < 0 || n_rel <= 0 || !drel || (T && (!triples || !nodes || !rel || !gs))) { rgcn_set_error("distmult_bwd_rel_bf16: bad argument"); return RGCN_EINVAL; }
-  if ((dsbias != nullptr) != (dpbias != nullptr) || (dsbias != nullptr) != (dobias != nullptr)) { rgcn_set_error("distmult_bwd_rel_bf16: bias gradients must be all set or all NULL"); return RGCN_EINVAL; }
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(zero_async(drel, (size_t)n_rel * d * sizeof(float), st));
-  if (dsbias) {
-    HIP_TRY(zero_async(dsbias, (size_t)n_nodes * sizeof(float), st));
-    HIP_TRY(zero_async(dobias, (size_t)n_nodes * sizeof(float), st));
-    HIP_TRY(zero_async(dpbias, (size_t)n_rel * sizeof(float), st));
-  }
-  if (T == 0) return RGCN_OK;
-  const unsigned gx = (unsigned)std::min<int64_t>((T + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(distmult_bwd_kernel<true>, dim3(gx), dim3(WG), 0, st, reinterpret_cast<const long long *>(triples),
-                     (long long)T, reinterpret_cast<const float *>(nodes), rel, gs, (float *)nullptr, drel, dsbias, dpbias, dobias, d, (long long)n_nodes, n_rel, 1);
-  HIP_TRY(hipGetLastError());
-  return RGCN_OK;
+  return distmult_bwd<true>("distmult_bwd_rel_bf16", triples, T, nodes, rel, gs, nullptr, drel, dsbias, dpbias, dobias, n_nodes, n_rel, d, stream);
+}
+
+extern "C" int rgcn_distmult_bwd_all_f32(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const float *nodes,
+                                         const float *rel, float *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                         int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  return distmult_bwd_all<false>("distmult_bwd_all", rowptr_s, rowptr_o, entries, nodes, rel, dnodes, drel, dsbias, dpbias, dobias, n_nodes, n_rel, d, stream);
+}
+
+extern "C" int rgcn_distmult_bwd_all_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                          const float *rel, uint16_t *dnodes, float *drel, float *dsbias, float *dpbias, float *dobias,
+                                          int64_t n_nodes, int32_t n_rel, int32_t d, void *stream) {
+  return distmult_bwd_all<true>("distmult_bwd_all_bf16", rowptr_s, rowptr_o, entries, nodes, rel, dnodes, drel, dsbias, dpbias, dobias, n_nodes, n_rel, d, stream);
+}
+
+extern "C" int rgcn_distmult_bwd_nodes_f32(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const float *nodes,
+                                           const float *rel, float *dnodes, int64_t n_nodes, int32_t d, void *stream) {
+  return distmult_bwd_nodes<false>("distmult_bwd_nodes", rowptr_s, rowptr_o, entries, nodes, rel, dnodes, n_nodes, d, stream);
+}
+
+extern "C" int rgcn_distmult_bwd_nodes_bf16(const int32_t *rowptr_s, const int32_t *rowptr_o, const int32_t *entries, const uint16_t *nodes,
+                                            const float *rel, uint16_t *dnodes, int64_t n_nodes, int32_t d, void *stream) {
+  return distmult_bwd_nodes<true>("distmult_bwd_nodes_bf16", rowptr_s, rowptr_o, entries, nodes, rel, dnodes, n_nodes, d, stream);
 }

@@ -2322,23 +2322,111 @@ def _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder="distmul
     return _dp(batch), form, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), rel.shape[0], _stream(nodes.device)
 
 
+def _entry(role, bf16):
+    """(the native function of `role` for the storage, its name): rgcn_<role>_f32 as "<role>", rgcn_<role>_bf16 as "<role>_bf16".  The
+    name is what _check reports; for the roles on scored triples it is the profile tag as well"""
+    return (getattr(lib(), "rgcn_" + role + "_bf16"), role + "_bf16") if bf16 else (getattr(lib(), "rgcn_" + role + "_f32"), role)
+
+
+# ----------------------------------------------------------------------------- decoders on scored triples: one body per role
+# decoder: "distmult" or "complex" (DESIGN.md 4.5: nodes [N, d] and rel [R, d] hold d / 2 complex features per row, real halves |
+# imaginary halves).  bf16: the entity table's storage (DESIGN.md 4.6) -- nodes bf16; the relation table, the biases, the scores and the
+# parameter gradients fp32 (bf16 parameters are widened by the caller, once per call); dnodes bf16, an fp32 sum per entity rounded once.
+# The public wrappers below fix both; the ComplEx ones pick the storage by the table's dtype.
+
+
+def _table_dtype(bf16):
+    return torch.bfloat16 if bf16 else torch.float32
+
+
+def _bias_grads(nodes, rel, with_bias):
+    """(dsbias [N], dpbias [R], dobias [N]), fp32 buffers for a native call to fill, or three None"""
+    if not with_bias:
+        return None, None, None
+    N, R, dev = nodes.shape[0], rel.shape[0], nodes.device
+    return tuple(torch.empty(n, device=dev, dtype=torch.float32) for n in (N, R, N))
+
+
+def _triple_fwd(decoder, bf16, triples, nodes, rel, sbias, pbias, obias, ranks):
+    """scores [T], fp32; ranks=True: (scores, [row sizes, ranks, False]) -- the counting pass of the backward's two CSRs done by the scoring
+    kernel (see distmult_csrs; the list is consumed by it)"""
+    _req_params(nodes, rel, sbias, pbias, obias, bf16=bf16); _req(triples, "triples", torch.int64)
+    if decoder == "complex":
+        check_decoder(decoder, nodes.shape[1])
+    fn, tag = _entry(decoder + "_fwd", bf16)
+    T, N, dev = triples.shape[0], nodes.shape[0], nodes.device
+    scores = torch.empty(T, device=dev, dtype=torch.float32)
+    err = _i32(1, dev)
+    counts = rk = None
+    if ranks and T:
+        counts, rk = _i32(2 * N + 3, dev), _i32(2 * T, dev)
+    with _on(dev), _timed(tag):
+        _check(fn(_dp(triples), T, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), _dp(scores), N, rel.shape[0], nodes.shape[1],
+                  _dp(err), _dp(counts), _dp(rk), _stream(dev)), tag)
+    # the reference indexes nodes[s], relations[p], nodes[o] (layers.py:89-93) and raises IndexError on a bad index
+    dev_check_err(err, ("ComplEx" if decoder == "complex" else "DistMult") + " triples (s, o < num_nodes, p < num_relations)", IndexError)
+    return (scores, [counts, rk, False]) if ranks else scores
+
+
+def _triple_bwd_nodes(decoder, bf16, triples, ranks, nodes, rel, gs):
+    """entity gradients (the table's dtype) without atomics: the two CSRs of the scored triples (distmult_csrs) and one wave per entity,
+    every row written"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", _table_dtype(bf16)); _req(rel, "relations")
+    fn, tag = _entry(decoder + "_bwd_nodes", bf16)
+    N, d = nodes.shape
+    dev = nodes.device
+    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
+    dn = torch.empty_like(nodes)
+    with _on(dev), _timed(tag):
+        _check(fn(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d, _stream(dev)), tag)
+    return dn
+
+
+def _triple_bwd_rel(decoder, bf16, triples, nodes, rel, gs, with_bias):
+    """(drel, dsbias, dpbias, dobias), fp32, from predicate-sorted triples; the bias gradients None unless with_bias.  (DistMult has this
+    entry for bf16 tables only: on fp32 ones distmult_bwd serves, with or without its scatter.)"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", _table_dtype(bf16)); _req(rel, "relations"); _req(triples, "triples", torch.int64)
+    fn, tag = _entry(decoder + "_bwd_rel", bf16)
+    dev = nodes.device
+    dr = torch.empty_like(rel)
+    dsb, dpb, dob = _bias_grads(nodes, rel, with_bias)
+    with _on(dev), _timed(tag):
+        _check(fn(_dp(triples), triples.shape[0], _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), nodes.shape[0],
+                  rel.shape[0], nodes.shape[1], _stream(dev)), tag)
+    return dr, dsb, dpb, dob
+
+
+def _distmult_bwd_all(bf16, triples, ranks, nodes, rel, gs, with_bias):
+    """(dnodes, drel, dsbias, dpbias, dobias) of DistMult from the two CSRs of the scored triples -- no predicate sort, no atomics on the
+    entity rows; bias gradients None unless with_bias"""
+    _req(gs, "grad_scores"); _req(nodes, "nodes", _table_dtype(bf16)); _req(rel, "relations")
+    fn, tag = _entry("distmult_bwd_all", bf16)
+    N, d = nodes.shape
+    dev = nodes.device
+    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
+    dn, dr = torch.empty_like(nodes), torch.empty_like(rel)
+    dsb, dpb, dob = _bias_grads(nodes, rel, with_bias)
+    with _on(dev), _timed(tag):
+        _check(fn(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), N, rel.shape[0],
+                  d, _stream(dev)), tag)
+    return dn, dr, dsb, dpb, dob
+
+
 def distmult_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
     """scores [T]; ranks=True: (scores, [row sizes, ranks]) -- the counting pass of the backward's two CSRs done by the scoring kernel
     (see distmult_csrs; the list is consumed by it)"""
-    _req_params(nodes, rel, sbias, pbias, obias); _req(triples, "triples", torch.int64)
-    T = triples.shape[0]
-    scores = torch.empty(T, device=nodes.device, dtype=torch.float32)
-    err = _i32(1, nodes.device)
-    counts = rk = None
-    if ranks and T:
-        counts, rk = _i32(2 * nodes.shape[0] + 3, nodes.device), _i32(2 * T, nodes.device)
-    with _on(nodes.device), _timed("distmult_fwd"):
-        _check(lib().rgcn_distmult_fwd_f32(_dp(triples), T, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                           _dp(scores), nodes.shape[0], rel.shape[0], nodes.shape[1], _dp(err),
-                                           _dp(counts), _dp(rk), _stream(nodes.device)), "distmult_fwd")
-    # the reference indexes nodes[s], relations[p], nodes[o] (layers.py:89-93) and raises IndexError on a bad index
-    dev_check_err(err, "DistMult triples (s, o < num_nodes, p < num_relations)", IndexError)
-    return (scores, [counts, rk, False]) if ranks else scores
+    return _triple_fwd("distmult", False, triples, nodes, rel, sbias, pbias, obias, ranks)
+
+
+def distmult_fwd_bf16(triples, nodes, rel, sbias, pbias, obias, ranks=False):
+    """distmult_fwd for bf16 nodes: fp32 scores [T]; ranks=True as there (the CSR counting pass rides along)"""
+    return _triple_fwd("distmult", True, triples, nodes, rel, sbias, pbias, obias, ranks)
+
+
+def complex_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
+    """ComplEx scores [T] (fp32) of `triples`, nodes fp32 or bf16; ranks=True: (scores, [row sizes, ranks]) as distmult_fwd -- distmult_csrs
+    finishes the CSRs"""
+    return _triple_fwd("complex", nodes.dtype == torch.bfloat16, triples, nodes, rel, sbias, pbias, obias, ranks)
 
 
 def distmult_score_all(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
@@ -2385,14 +2473,17 @@ def distmult_bwd(triples, nodes, rel, gs, with_bias, nodes_grad=True):
     _req(gs, "grad_scores")
     dn = torch.empty_like(nodes) if nodes_grad else None
     dr = torch.empty_like(rel)
-    dsb = torch.empty(nodes.shape[0], device=nodes.device) if with_bias else None
-    dob = torch.empty(nodes.shape[0], device=nodes.device) if with_bias else None
-    dpb = torch.empty(rel.shape[0], device=nodes.device) if with_bias else None
+    dsb, dpb, dob = _bias_grads(nodes, rel, with_bias)
     with _on(nodes.device), _timed("distmult_bwd"):
         _check(lib().rgcn_distmult_bwd_f32(_dp(triples), triples.shape[0], _dp(nodes), _dp(rel), _dp(gs), _dp(dn),
                                            _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), nodes.shape[0], rel.shape[0],
                                            nodes.shape[1], _stream(nodes.device)), "distmult_bwd")
     return dn, dr, dsb, dpb, dob
+
+
+def distmult_bwd_rel(triples, nodes, rel, gs, with_bias):
+    """(drel, dsbias, dpbias, dobias) of distmult_bwd without its scatter: the fp32 counterpart of distmult_bwd_rel_bf16"""
+    return distmult_bwd(triples, nodes, rel, gs, with_bias, nodes_grad=False)[1:]
 
 
 def distmult_bwd_all_supported(n_rel, d):
@@ -2418,170 +2509,42 @@ def distmult_csrs(triples, ranks, nodes, rel, gs):
 def distmult_bwd_all(triples, ranks, nodes, rel, gs, with_bias):
     """(dnodes, drel, dsbias, dpbias, dobias) of DistMult from two CSRs of the scored triples -- no predicate sort, no atomics on
     the entity rows (rgcn_distmult_bwd_all_f32); bias gradients None unless with_bias"""
-    _req(gs, "grad_scores"); _req(nodes, "nodes"); _req(rel, "relations")
-    N, d = nodes.shape
-    R = rel.shape[0]
-    dev = nodes.device
-    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
-    dn, dr = torch.empty_like(nodes), torch.empty_like(rel)
-    dsb = dpb = dob = None
-    if with_bias:
-        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
-        dpb = torch.empty(R, device=dev, dtype=torch.float32)
-    with _on(dev), _timed("distmult_bwd_all"):
-        _check(lib().rgcn_distmult_bwd_all_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), _dp(dr), _dp(dsb),
-                                               _dp(dpb), _dp(dob), N, R, d, _stream(dev)), "distmult_bwd_all")
-    return dn, dr, dsb, dpb, dob
+    return _distmult_bwd_all(False, triples, ranks, nodes, rel, gs, with_bias)
+
+
+def distmult_bwd_all_bf16(triples, ranks, nodes, rel, gs, with_bias):
+    """distmult_bwd_all for bf16 nodes: (dnodes bf16, drel, dsbias, dpbias, dobias fp32) from ONE walk of the two CSRs"""
+    return _distmult_bwd_all(True, triples, ranks, nodes, rel, gs, with_bias)
 
 
 def distmult_bwd_nodes(triples, ranks, nodes, rel, gs):
     """entity gradients of DistMult without atomics: the two CSRs of the scored triples (distmult_csrs) and one wave per entity
     (rgcn_distmult_bwd_nodes_f32)"""
-    _req(gs, "grad_scores"); _req(nodes, "nodes"); _req(rel, "relations")
-    N, d = nodes.shape
-    dev = nodes.device
-    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
-    dn = torch.empty_like(nodes)
-    with _on(dev), _timed("distmult_bwd_nodes"):
-        _check(lib().rgcn_distmult_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d,
-                                                 _stream(dev)), "distmult_bwd_nodes")
-    return dn
-
-
-# ----------------------------------------------------------------------------- DistMult on a bf16 entity table (DESIGN.md 4.6)
-# nodes bf16; the relation table, the biases, the scores and the parameter gradients fp32 (bf16 parameters are widened by the caller,
-# once per call); dnodes bf16, an fp32 sum per entity rounded once.
-
-
-def distmult_fwd_bf16(triples, nodes, rel, sbias, pbias, obias, ranks=False):
-    """distmult_fwd for bf16 nodes: fp32 scores [T]; ranks=True as there (the CSR counting pass rides along)"""
-    _req_params(nodes, rel, sbias, pbias, obias, bf16=True); _req(triples, "triples", torch.int64)
-    T = triples.shape[0]
-    scores = torch.empty(T, device=nodes.device, dtype=torch.float32)
-    err = _i32(1, nodes.device)
-    counts = rk = None
-    if ranks and T:
-        counts, rk = _i32(2 * nodes.shape[0] + 3, nodes.device), _i32(2 * T, nodes.device)
-    with _on(nodes.device), _timed("distmult_fwd_bf16"):
-        _check(lib().rgcn_distmult_fwd_bf16(_dp(triples), T, _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias),
-                                            _dp(scores), nodes.shape[0], rel.shape[0], nodes.shape[1], _dp(err),
-                                            _dp(counts), _dp(rk), _stream(nodes.device)), "distmult_fwd_bf16")
-    dev_check_err(err, "DistMult triples (s, o < num_nodes, p < num_relations)", IndexError)
-    return (scores, [counts, rk, False]) if ranks else scores
-
-
-def distmult_bwd_all_bf16(triples, ranks, nodes, rel, gs, with_bias):
-    """distmult_bwd_all for bf16 nodes: (dnodes bf16, drel, dsbias, dpbias, dobias fp32) from ONE walk of the two CSRs"""
-    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
-    N, d = nodes.shape
-    R = rel.shape[0]
-    dev = nodes.device
-    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
-    dn, dr = torch.empty_like(nodes), torch.empty_like(rel)
-    dsb = dpb = dob = None
-    if with_bias:
-        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
-        dpb = torch.empty(R, device=dev, dtype=torch.float32)
-    with _on(dev), _timed("distmult_bwd_all_bf16"):
-        _check(lib().rgcn_distmult_bwd_all_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), _dp(dr), _dp(dsb),
-                                                _dp(dpb), _dp(dob), N, R, d, _stream(dev)), "distmult_bwd_all_bf16")
-    return dn, dr, dsb, dpb, dob
+    return _triple_bwd_nodes("distmult", False, triples, ranks, nodes, rel, gs)
 
 
 def distmult_bwd_nodes_bf16(triples, ranks, nodes, rel, gs):
     """distmult_bwd_nodes for bf16 nodes: the entity gradients, bf16, every row written"""
-    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations")
-    N, d = nodes.shape
-    dev = nodes.device
-    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
-    dn = torch.empty_like(nodes)
-    with _on(dev), _timed("distmult_bwd_nodes_bf16"):
-        _check(lib().rgcn_distmult_bwd_nodes_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d,
-                                                  _stream(dev)), "distmult_bwd_nodes_bf16")
-    return dn
+    return _triple_bwd_nodes("distmult", True, triples, ranks, nodes, rel, gs)
 
 
 def distmult_bwd_rel_bf16(triples, nodes, rel, gs, with_bias):
     """(drel, dsbias, dpbias, dobias), fp32, from predicate-sorted triples and bf16 nodes: the relation tables the LDS table of
     distmult_bwd_all_bf16 does not hold; the entity gradients come from distmult_bwd_nodes_bf16"""
-    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16); _req(rel, "relations"); _req(triples, "triples", torch.int64)
-    N, R, dev = nodes.shape[0], rel.shape[0], nodes.device
-    dr = torch.empty_like(rel)
-    dsb = dpb = dob = None
-    if with_bias:
-        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
-        dpb = torch.empty(R, device=dev, dtype=torch.float32)
-    with _on(dev), _timed("distmult_bwd_rel_bf16"):
-        _check(lib().rgcn_distmult_bwd_rel_bf16(_dp(triples), triples.shape[0], _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb),
-                                                _dp(dpb), _dp(dob), N, R, nodes.shape[1], _stream(dev)), "distmult_bwd_rel_bf16")
-    return dr, dsb, dpb, dob
+    return _triple_bwd_rel("distmult", True, triples, nodes, rel, gs, with_bias)
 
 
-# ----------------------------------------------------------------------------- ComplEx on scored triples (DESIGN.md 4.5)
-# nodes [N, d] and rel [R, d] hold d / 2 complex features per row, real halves | imaginary halves; nodes fp32 or bf16 (the wrapper picks the
-# entry by the table's dtype), everything else as in the DistMult wrappers of the same role.  The split route only: entity gradients from
-# the two CSRs, relation and bias gradients from predicate-sorted triples.
-
-
-def complex_fwd(triples, nodes, rel, sbias, pbias, obias, ranks=False):
-    """ComplEx scores [T] (fp32) of `triples`; ranks=True: (scores, [row sizes, ranks]) as distmult_fwd -- distmult_csrs finishes the CSRs"""
-    bf16 = nodes.dtype == torch.bfloat16
-    _req_params(nodes, rel, sbias, pbias, obias, bf16=bf16); _req(triples, "triples", torch.int64)
-    check_decoder("complex", nodes.shape[1])
-    T, N, R, d, dev = triples.shape[0], nodes.shape[0], rel.shape[0], nodes.shape[1], nodes.device
-    scores = torch.empty(T, device=dev, dtype=torch.float32)
-    err = _i32(1, dev)
-    counts = rk = None
-    if ranks and T:
-        counts, rk = _i32(2 * N + 3, dev), _i32(2 * T, dev)
-    tr, nd, rl, sb, pb, ob, sc, st = _dp(triples), _dp(nodes), _dp(rel), _dp(sbias), _dp(pbias), _dp(obias), _dp(scores), _stream(dev)
-    with _on(dev), _timed("complex_fwd_bf16" if bf16 else "complex_fwd"):
-        if bf16:
-            _check(lib().rgcn_complex_fwd_bf16(tr, T, nd, rl, sb, pb, ob, sc, N, R, d, _dp(err), _dp(counts), _dp(rk), st), "complex_fwd_bf16")
-        else:
-            _check(lib().rgcn_complex_fwd_f32(tr, T, nd, rl, sb, pb, ob, sc, N, R, d, _dp(err), _dp(counts), _dp(rk), st), "complex_fwd")
-    dev_check_err(err, "ComplEx triples (s, o < num_nodes, p < num_relations)", IndexError)
-    return (scores, [counts, rk, False]) if ranks else scores
-
-
+# ComplEx has the split route only -- entity gradients from the two CSRs, relation and bias gradients from predicate-sorted triples --
+# and picks the entry by the table's dtype
 def complex_bwd_nodes(triples, ranks, nodes, rel, gs):
     """entity gradients of ComplEx (the table's dtype; bf16: an fp32 sum per entity rounded once) from the two CSRs of the scored triples,
     one wave per entity, no atomics, every row written"""
-    bf16 = nodes.dtype == torch.bfloat16
-    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16 if bf16 else torch.float32); _req(rel, "relations")
-    N, d = nodes.shape
-    dev = nodes.device
-    rp_s, rp_o, entries = distmult_csrs(triples, ranks, nodes, rel, gs)
-    dn = torch.empty_like(nodes)
-    with _on(dev), _timed("complex_bwd_nodes_bf16" if bf16 else "complex_bwd_nodes"):
-        if bf16:
-            _check(lib().rgcn_complex_bwd_nodes_bf16(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d, _stream(dev)),
-                   "complex_bwd_nodes_bf16")
-        else:
-            _check(lib().rgcn_complex_bwd_nodes_f32(_dp(rp_s), _dp(rp_o), _dp(entries), _dp(nodes), _dp(rel), _dp(dn), N, d, _stream(dev)),
-                   "complex_bwd_nodes")
-    return dn
+    return _triple_bwd_nodes("complex", nodes.dtype == torch.bfloat16, triples, ranks, nodes, rel, gs)
 
 
 def complex_bwd_rel(triples, nodes, rel, gs, with_bias):
     """(drel, dsbias, dpbias, dobias), fp32, of ComplEx from predicate-sorted triples; the bias gradients None unless with_bias"""
-    bf16 = nodes.dtype == torch.bfloat16
-    _req(gs, "grad_scores"); _req(nodes, "nodes", torch.bfloat16 if bf16 else torch.float32); _req(rel, "relations")
-    _req(triples, "triples", torch.int64)
-    T, N, R, d, dev = triples.shape[0], nodes.shape[0], rel.shape[0], nodes.shape[1], nodes.device
-    dr = torch.empty_like(rel)
-    dsb = dpb = dob = None
-    if with_bias:
-        dsb, dob = torch.empty(N, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
-        dpb = torch.empty(R, device=dev, dtype=torch.float32)
-    with _on(dev), _timed("complex_bwd_rel_bf16" if bf16 else "complex_bwd_rel"):
-        if bf16:
-            _check(lib().rgcn_complex_bwd_rel_bf16(_dp(triples), T, _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), N, R, d,
-                                                   _stream(dev)), "complex_bwd_rel_bf16")
-        else:
-            _check(lib().rgcn_complex_bwd_rel_f32(_dp(triples), T, _dp(nodes), _dp(rel), _dp(gs), _dp(dr), _dp(dsb), _dp(dpb), _dp(dob), N, R, d,
-                                                  _stream(dev)), "complex_bwd_rel")
-    return dr, dsb, dpb, dob
+    return _triple_bwd_rel("complex", nodes.dtype == torch.bfloat16, triples, nodes, rel, gs, with_bias)
 
 
 def distmult_score_all_bf16(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
@@ -2627,7 +2590,8 @@ def _filter_call_args(filt_q, filt_n, F, filt, head, N, dev):
 
 
 def _filter_tag(tag, filt, bf16):
-    """the profile tag of a filtered call: tag[_index][_bf16]"""
+    """the profile tag of a filtered call: tag[_index][_bf16].  A scheme of its own beside _entry's names (distmult_<role>[_bf16], which
+    _check reports): the tags carry the filter's form, and topk_fused / lse_fused are not their entries' role names -- tests pin both"""
     return tag + ("_index" if filt is not None else "") + ("_bf16" if bf16 else "")
 
 
@@ -2687,13 +2651,10 @@ def distmult_rank_fused(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     ws = torch.empty(max(rank_fused_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    native, name = _entry("distmult_rank_fused", bf16)
     with _on(dev), _timed(_filter_tag("rank_fused", filt, bf16)):
-        if bf16:
-            _check(lib().rgcn_distmult_rank_fused_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
-                                                       _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused_bf16")
-        else:
-            _check(lib().rgcn_distmult_rank_fused_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(greater),
-                                                      _dp(ties), _dp(tscore), N, R, d, st), "distmult_rank_fused")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(greater), _dp(ties), _dp(tscore), N, R, d, st),
+               name)
     return greater, ties, tscore
 
 
@@ -2736,13 +2697,9 @@ def _distmult_topk(batch, head, nodes, rel, sbias, pbias, obias, k, filt_q, filt
     ws = torch.empty(max(topk_workspace_bytes(Q, N, d, k, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    native, name = _entry("distmult_topk", bf16)
     with _on(dev), _timed(_filter_tag("topk_fused", filt, bf16)):
-        if bf16:
-            _check(lib().rgcn_distmult_topk_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
-                                                 _dp(scores), N, R, d, st), "distmult_topk_bf16")
-        else:
-            _check(lib().rgcn_distmult_topk_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids),
-                                                _dp(scores), N, R, d, st), "distmult_topk")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, k, strips, _dp(ws), _dp(ids), _dp(scores), N, R, d, st), name)
     return ids, scores
 
 
@@ -2792,13 +2749,9 @@ def distmult_lse(batch, head, nodes, rel, sbias=None, pbias=None, obias=None, fi
     ws = torch.empty(max(lse_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    native, name = _entry("distmult_lse", bf16)
     with _on(dev), _timed(_filter_tag("lse_fused", filt, bf16)):
-        if bf16:
-            _check(lib().rgcn_distmult_lse_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                                N, R, d, st), "distmult_lse_bf16")
-        else:
-            _check(lib().rgcn_distmult_lse_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore),
-                                               N, R, d, st), "distmult_lse")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore), N, R, d, st), name)
     return lse, tscore
 
 
@@ -2825,13 +2778,10 @@ def distmult_lse_smooth(batch, head, nodes, rel, sbias=None, pbias=None, obias=N
     ws = torch.empty(max(lse_smooth_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
+    native, name = _entry("distmult_lse_smooth", bf16)
     with _on(dev), _timed(_filter_tag("lse_smooth", filt, bf16)):
-        if bf16:
-            _check(lib().rgcn_distmult_lse_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
-                                                       _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth_bf16")
-        else:
-            _check(lib().rgcn_distmult_lse_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse),
-                                                      _dp(tscore), _dp(ssum), _dp(cnt), N, R, d, st), "distmult_lse_smooth")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(lse), _dp(tscore), _dp(ssum), _dp(cnt), N, R,
+                      d, st), name)
     return lse, tscore, ssum, cnt
 
 
@@ -2871,25 +2821,12 @@ def distmult_softmax_grad(batch, head, nodes, rel, sbias, pbias, obias, filt_q, 
     per_query, over = 1 if (gscale.numel() == Q and gscale.dim() == 1) else 0, int(mean_over)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(filt_q, filt_n, F, filt, head, N, dev)
-    with _on(dev), _timed(_filter_tag("softmax_grad_smooth" if smooth else "softmax_grad", filt, bf16)):
-        if smooth:
-            if bf16:
-                _check(lib().rgcn_distmult_softmax_grad_smooth_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                                    _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS),
-                                                                    N, R, d, st), "distmult_softmax_grad_smooth_bf16")
-            else:
-                _check(lib().rgcn_distmult_softmax_grad_smooth_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                                   _dp(keep), _dp(uni), per_query, over, c_first, c_count, _dp(ws), _dp(dS),
-                                                                   N, R, d, st), "distmult_softmax_grad_smooth")
-        else:
-            if bf16:
-                _check(lib().rgcn_distmult_softmax_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                             per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
-                       "distmult_softmax_grad_bf16")
-            else:
-                _check(lib().rgcn_distmult_softmax_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale),
-                                                            per_query, over, c_first, c_count, _dp(ws), _dp(dS), N, R, d, st),
-                       "distmult_softmax_grad")
+    role = "softmax_grad_smooth" if smooth else "softmax_grad"
+    native, name = _entry("distmult_" + role, bf16)
+    smoothing = (_dp(keep), _dp(uni)) if smooth else ()          # the two pointers the smoothed entries take behind gscale
+    with _on(dev), _timed(_filter_tag(role, filt, bf16)):
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(lse), _dp(gscale), *smoothing, per_query, over, c_first, c_count,
+                      _dp(ws), _dp(dS), N, R, d, st), name)
     return dS
 
 
@@ -2924,13 +2861,9 @@ def distmult_bce_sums(batch, head, nodes, rel, sbias=None, pbias=None, obias=Non
     ws = torch.empty(max(bce_sums_workspace_bytes(Q, N, d, strips, bf16), 16), device=dev, dtype=torch.uint8)
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(lab_q, lab_n, F, labels, head, N, dev)
+    native, name = _entry("distmult_bce_sums", bf16)
     with _on(dev), _timed("bce_sums_bf16" if bf16 else "bce_sums"):
-        if bf16:
-            _check(lib().rgcn_distmult_bce_sums_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps),
-                                                     _dp(npos), N, R, d, st), "distmult_bce_sums_bf16")
-        else:
-            _check(lib().rgcn_distmult_bce_sums_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps),
-                                                    _dp(npos), N, R, d, st), "distmult_bce_sums")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, strips, _dp(ws), _dp(sp), _dp(ps), _dp(npos), N, R, d, st), name)
     return sp, ps, npos
 
 
@@ -2959,11 +2892,8 @@ def distmult_bce_grad(batch, head, nodes, rel, sbias, pbias, obias, lab_q, lab_n
     b, h, nd, rl, sb, pb, ob, R, st = _query_prefix(batch, head, nodes, rel, sbias, pbias, obias, decoder)
     fq, fn, F, fk, fp, fv, K = _filter_call_args(lab_q, lab_n, F, labels, head, N, dev)
     sm = None if smooth is None else ctypes.addressof(smooth)
+    native, name = _entry("distmult_bce_grad", bf16)
     with _on(dev), _timed("bce_grad_bf16" if bf16 else "bce_grad"):
-        if bf16:
-            _check(lib().rgcn_distmult_bce_grad_bf16(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(gscale), per_query, over, sm,
-                                                     c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_bce_grad_bf16")
-        else:
-            _check(lib().rgcn_distmult_bce_grad_f32(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(gscale), per_query, over, sm,
-                                                    c_first, c_count, _dp(ws), _dp(dS), N, R, d, st), "distmult_bce_grad")
+        _check(native(b, Q, h, nd, rl, sb, pb, ob, fq, fn, F, fk, fp, fv, K, _dp(gscale), per_query, over, sm, c_first, c_count, _dp(ws), _dp(dS),
+                      N, R, d, st), name)
     return dS

@@ -1148,63 +1148,43 @@ def featureless_mp(table, bias, graph, relu=False):
     return _FeaturelessMP.apply(table, bias, graph, relu)
 
 
-class _DistMultScore(torch.autograd.Function):
+# the _native wrappers of the scored-triples roles per (decoder, bf16 entity table): (score, all-in-one CSR walk or None, relation and bias
+# gradients, entity gradients).  NAMES, looked up on the module at every call.  The ComplEx wrappers pick the storage themselves.
+_TRIPLE_ROLES = {("distmult", False): ("distmult_fwd", "distmult_bwd_all", "distmult_bwd_rel", "distmult_bwd_nodes"),
+                 ("distmult", True): ("distmult_fwd_bf16", "distmult_bwd_all_bf16", "distmult_bwd_rel_bf16", "distmult_bwd_nodes_bf16"),
+                 ("complex", False): ("complex_fwd", None, "complex_bwd_rel", "complex_bwd_nodes"),
+                 ("complex", True): ("complex_fwd", None, "complex_bwd_rel", "complex_bwd_nodes")}
+
+
+class _TripleScore(torch.autograd.Function):
+    """DistMult or ComplEx scores of triples on an fp32 or a bf16 entity table.  On a bf16 table the
+    relations and biases arrive as fp32 (distmult_score / complex_score widened bf16 parameters); scores are fp32, dnodes has the table's
+    dtype -- bf16: an fp32 sum per entity rounded once --, the parameter gradients are fp32.
+
+    The backward walks the scored triples as two CSRs, whose counting pass rides on the scoring kernel when something needs a gradient and
+    there are triples.  DistMult, by the route switch distmult_bwd: csr = every gradient from the CSR walks (fp32: two, bf16: ONE) where the
+    relation table fits the LDS (WN18: 18 x 200; no predicate sort), else as split; split = the entity gradients from the CSRs, one wave
+    per entity and no atomics, + the predicate-sorted kernel for relations and biases; atomic (RGCN_DISTMULT_BWD=atomic) = the
+    predicate-sorted kernel also scatters the entity gradients with fp32 atomics and the scoring kernel counts nothing -- on a bf16 table
+    CORRECTNESS ONLY: bf16 is never accumulated with atomics, so the fp32 scatter kernel runs on the widened table and its dnodes is rounded
+    once.  ComplEx has ONE route, DistMult's split: no LDS-table and no atomic-scatter twin, the switch is ignored, `atomic` included.
+
+    No ranks were counted = DistMult's atomic route, or no triples at all: then DistMult takes the scatter call (of no triples: its zero
+    fills) and ComplEx the relation kernel's zero fills beside a zero dnodes."""
+
     @staticmethod
-    def forward(ctx, triples, nodes, relations, sbias, pbias, obias):
+    def forward(ctx, decoder, triples, nodes, relations, sbias, pbias, obias):
         shape = triples.shape[:-1]
         tr = triples.reshape(-1, 3).contiguous()
         nodes = dense(nodes)
         relations = dense(relations)
-        # the backward pass walks the scored triples as two CSRs (unless routed to the atomic scatter): their counting pass rides on
-        # the scoring kernel
-        ctx.ranks = None
-        if any(ctx.needs_input_grad[1:]) and tr.shape[0] and routes.get("distmult_bwd", "csr") != "atomic":
-            scores, ctx.ranks = _native.distmult_fwd(tr, nodes, relations, sbias, pbias, obias, ranks=True)
-        else:
-            scores = _native.distmult_fwd(tr, nodes, relations, sbias, pbias, obias)
+        ctx.roles = _TRIPLE_ROLES[decoder, nodes.dtype == torch.bfloat16]
+        walks = decoder == "complex" or routes.get("distmult_bwd", "csr") != "atomic"
+        count = bool(any(ctx.needs_input_grad[2:]) and tr.shape[0] and walks)
+        out = getattr(_native, ctx.roles[0])(tr, nodes, relations, sbias, pbias, obias, ranks=count)
+        scores, ctx.ranks = out if count else (out, None)
         ctx.save_for_backward(tr, nodes, relations)
-        ctx.with_bias = sbias is not None
-        ctx.shape = shape
-        return scores.view(shape)
-
-    @staticmethod
-    def backward(ctx, gs):
-        tr, nodes, relations = ctx.saved_tensors
-        gs = gs.reshape(-1)
-        gs = dense(gs)
-        mode = routes.get("distmult_bwd", "csr")
-        scatter = ctx.ranks is None
-        if not scatter and mode != "split" and _native.distmult_bwd_all_supported(relations.shape[0], nodes.shape[1]):
-            # small relation tables (WN18: 18 x 200): every gradient from the two CSR walks, no predicate sort
-            dn, dr, dsb, dpb, dob = _native.distmult_bwd_all(tr, ctx.ranks, nodes, relations, gs, ctx.with_bias)
-            return None, dn, dr, dsb, dpb, dob
-        order = torch.argsort(tr[:, 1], stable=True)   # predicate runs -> relation gradient accumulates in registers
-        dn, dr, dsb, dpb, dob = _native.distmult_bwd(tr[order].contiguous(), nodes, relations, gs[order].contiguous(),
-                                                     ctx.with_bias, nodes_grad=scatter)
-        if not scatter:      # entity gradients: CSR by subject / by object, one wave per entity, no atomics
-            dn = _native.distmult_bwd_nodes(tr, ctx.ranks, nodes, relations, gs)
-        return None, dn, dr, dsb, dpb, dob
-
-
-class _DistMultScoreBF16(torch.autograd.Function):
-    """_DistMultScore on bf16 node embeddings: relations and biases arrive as fp32 (distmult_score widened bf16 parameters),
-    scores are fp32, dnodes is bf16 -- an fp32 sum per entity rounded once --, the parameter gradients fp32.  Routes as in fp32: csr = every
-    gradient from one walk of the two CSRs where the relation table fits the LDS, else split = entity gradients from the CSRs + the
-    predicate-sorted kernel for relations and biases.  atomic (RGCN_DISTMULT_BWD=atomic) is CORRECTNESS ONLY: bf16 is never accumulated
-    with atomics, so the fp32 scatter kernel runs on the widened table and its dnodes is rounded once."""
-
-    @staticmethod
-    def forward(ctx, triples, nodes, relations, sbias, pbias, obias):
-        shape = triples.shape[:-1]
-        tr = triples.reshape(-1, 3).contiguous()
-        nodes = dense(nodes)
-        relations = dense(relations)
-        ctx.ranks = None
-        if any(ctx.needs_input_grad[1:]) and tr.shape[0] and routes.get("distmult_bwd", "csr") != "atomic":
-            scores, ctx.ranks = _native.distmult_fwd_bf16(tr, nodes, relations, sbias, pbias, obias, ranks=True)
-        else:
-            scores = _native.distmult_fwd_bf16(tr, nodes, relations, sbias, pbias, obias)
-        ctx.save_for_backward(tr, nodes, relations)
+        ctx.scatter = decoder == "distmult" and not count
         ctx.with_bias = sbias is not None
         return scores.view(shape)
 
@@ -1212,52 +1192,18 @@ class _DistMultScoreBF16(torch.autograd.Function):
     def backward(ctx, gs):
         tr, nodes, relations = ctx.saved_tensors
         gs = dense(gs.reshape(-1).float())
-        if ctx.ranks is None:                          # atomic route (or no triples)
-            order = torch.argsort(tr[:, 1], stable=True)
-            dn, dr, dsb, dpb, dob = _native.distmult_bwd(tr[order].contiguous(), nodes.float(), relations, gs[order].contiguous(),
-                                                         ctx.with_bias, nodes_grad=True)
-            return None, dn.to(torch.bfloat16), dr, dsb, dpb, dob
-        if routes.get("distmult_bwd", "csr") != "split" and _native.distmult_bwd_all_supported(relations.shape[0], nodes.shape[1]):
-            dn, dr, dsb, dpb, dob = _native.distmult_bwd_all_bf16(tr, ctx.ranks, nodes, relations, gs, ctx.with_bias)
-            return None, dn, dr, dsb, dpb, dob
+        _, bwd_all, bwd_rel, bwd_nodes = ctx.roles
+        if (bwd_all and not ctx.scatter and routes.get("distmult_bwd", "csr") != "split"
+                and _native.distmult_bwd_all_supported(relations.shape[0], nodes.shape[1])):
+            return (None, None) + getattr(_native, bwd_all)(tr, ctx.ranks, nodes, relations, gs, ctx.with_bias)
         order = torch.argsort(tr[:, 1], stable=True)   # predicate runs -> relation gradient accumulates in registers
-        dr, dsb, dpb, dob = _native.distmult_bwd_rel_bf16(tr[order].contiguous(), nodes, relations, gs[order].contiguous(), ctx.with_bias)
-        dn = _native.distmult_bwd_nodes_bf16(tr, ctx.ranks, nodes, relations, gs)
-        return None, dn, dr, dsb, dpb, dob
-
-
-class _ComplExScore(torch.autograd.Function):
-    """ComplEx scores of triples on an fp32 or a bf16 entity table, shaped like _DistMultScore / _DistMultScoreBF16: relations
-    and biases fp32 (complex_score widened bf16 parameters), scores fp32, dnodes in the table's dtype (bf16: an fp32 sum per entity rounded
-    once), the parameter gradients fp32.  ONE route, what DistMult calls "split": the CSR counting pass rides on the scoring kernel, the
-    entity gradients come from the two CSRs without atomics, the relation and bias gradients from the predicate-sorted triples.  There is no
-    LDS-table and no atomic-scatter twin: the route switch distmult_bwd is ignored here, `atomic` included."""
-
-    @staticmethod
-    def forward(ctx, triples, nodes, relations, sbias, pbias, obias):
-        shape = triples.shape[:-1]
-        tr = triples.reshape(-1, 3).contiguous()
-        nodes = dense(nodes)
-        relations = dense(relations)
-        ctx.ranks = None
-        if any(ctx.needs_input_grad[1:]) and tr.shape[0]:
-            scores, ctx.ranks = _native.complex_fwd(tr, nodes, relations, sbias, pbias, obias, ranks=True)
-        else:
-            scores = _native.complex_fwd(tr, nodes, relations, sbias, pbias, obias)
-        ctx.save_for_backward(tr, nodes, relations)
-        ctx.with_bias = sbias is not None
-        return scores.view(shape)
-
-    @staticmethod
-    def backward(ctx, gs):
-        tr, nodes, relations = ctx.saved_tensors
-        gs = dense(gs.reshape(-1).float())
-        order = torch.argsort(tr[:, 1], stable=True)   # predicate runs -> relation gradient accumulates in registers
-        dr, dsb, dpb, dob = _native.complex_bwd_rel(tr[order].contiguous(), nodes, relations, gs[order].contiguous(), ctx.with_bias)
-        if ctx.ranks is None:                          # no triples: nothing was counted
-            return None, torch.zeros_like(nodes), dr, dsb, dpb, dob
-        dn = _native.complex_bwd_nodes(tr, ctx.ranks, nodes, relations, gs)
-        return None, dn, dr, dsb, dpb, dob
+        tr_p, gs_p = tr[order].contiguous(), gs[order].contiguous()
+        if ctx.scatter:
+            dn, dr, dsb, dpb, dob = _native.distmult_bwd(tr_p, nodes.float(), relations, gs_p, ctx.with_bias, nodes_grad=True)
+            return None, None, dn.to(nodes.dtype), dr, dsb, dpb, dob
+        dr, dsb, dpb, dob = getattr(_native, bwd_rel)(tr_p, nodes, relations, gs_p, ctx.with_bias)
+        dn = torch.zeros_like(nodes) if ctx.ranks is None else getattr(_native, bwd_nodes)(tr, ctx.ranks, nodes, relations, gs)
+        return None, None, dn, dr, dsb, dpb, dob
 
 
 def _check_decoder(decoder, nodes):
@@ -1313,8 +1259,7 @@ def _widen_query_params(nodes, relations, sbias, pbias, obias):
 def distmult_score(triples, nodes, relations, sbias=None, pbias=None, obias=None):
     """DistMult scores of `triples` [..., 3].  fp32 nodes: everything fp32.  bf16 nodes: relations and biases fp32 or bf16
     -- bf16 parameters are widened here, once per call, and autograd carries the cast back --, scores fp32, dnodes bf16."""
-    score = _DistMultScoreBF16 if nodes.dtype == torch.bfloat16 else _DistMultScore
-    return score.apply(triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
+    return _TripleScore.apply("distmult", triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
 
 
 def complex_score(triples, nodes, relations, sbias=None, pbias=None, obias=None):
@@ -1325,7 +1270,7 @@ def complex_score(triples, nodes, relations, sbias=None, pbias=None, obias=None)
     here), fp32 scores, dnodes in the table's dtype.  The backward always runs the CSR walk for the entities and the predicate-sorted kernel
     for relations and biases (DistMult's "split" route); the route switch distmult_bwd has no effect on it."""
     _check_decoder("complex", nodes)
-    return _ComplExScore.apply(triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
+    return _TripleScore.apply("complex", triples, nodes, *_widen_query_params(nodes, relations, sbias, pbias, obias))
 
 
 def distmult_score_all(batch, head, nodes, relations, sbias=None, pbias=None, obias=None, out=None, decoder="distmult"):
